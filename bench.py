@@ -7,6 +7,13 @@ the plan of the C2 workload of BASELINE.json: nips-like 1,500 x 12,419 pattern w
 Reordering runs once before timing and is reported separately (the reference's GFLOP/s excludes it
 too, Logger.hpp:178-180). Inputs are resident in HBM when the timed region starts.
 
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) does only that: plan, warm-up, the K timed
+steps (stream launches, then the same K steps as one HIP graph: the line's value), the line.
+`--dump-outputs DIR` also writes the last timed step's P to DIR/P.npy. `--full` adds every other
+leg of the report after the timed steps: in-run PMC traffic and MFMA counters, cold steps, the
+dense/residual split, the rocSPARSE and CPU baselines (N > 1: checkData of the gathered P and the
+strong_C4 block). --config C1 is the CPU path's own line and is the same with or without --full.
+
 Multi-GPU (python -m torch.distributed.run --nproc-per-node N bench.py --gpus N, or plain
 `bench.py --gpus N`, which starts that launcher as a child process; a WORLD_SIZE other than
 --gpus is an error, so the line's n_gpus is always --gpus): S sharded by
@@ -51,7 +58,10 @@ def parse():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--config", default="C2", choices=["C1", "C2", "C3", "C4", "C5"],
-                    help="BASELINE.json config (C1 = the OpenMP host path on nips-like K = 32)")
+                    help="BASELINE.json config (C1 = the OpenMP host path on nips-like K = 32: its "
+                         "line is the CPU leg timed until steady, with the GPU's run of the same "
+                         "workload and their checkData beside it, with or without --full; "
+                         "--steps and --warmup there set the GPU leg's steps only)")
     ap.add_argument("--K", type=int, default=None)
     ap.add_argument("--alpha", type=float, default=0.3)
     ap.add_argument("--delta", type=float, default=0.3)
@@ -59,6 +69,19 @@ def parse():
     ap.add_argument("--mask", default="uniform", choices=["uniform", "block"], help="C5 mask")
     ap.add_argument("--layout", default="auto", choices=["auto", "rowblock", "colmajor"],
                     help="SDDMM launch layout (bsmr_plan_options.layout)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg of the report: the "
+                         "in-run PMC passes (roofline.traffic, mfma.busy), the cold steps, the "
+                         "dense/residual split launches, the forced-MFMA split, the rocSPARSE and "
+                         "CPU baselines; multi-GPU: the checkData of the gathered P and the "
+                         "strong_C4 block. Off by default: a plain run sets up, warms up, times "
+                         "the steps and prints the line. The --no-* / --pmc / --cold-steps "
+                         "options below trim a --full run")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write the P of the last timed step as DIR/P.npy "
+                         "(float32, CSR order; outputs over 64 MB: a fixed seeded sample of the "
+                         "entries). Inputs are the same from run to run, so two builds can be "
+                         "compared output for output")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-vendor", action="store_true",
                     help="skip the rocSPARSE SDDMM baseline leg (vendor_baseline)")
@@ -82,7 +105,7 @@ def parse():
                     help="run the multi-GPU path (torch.distributed, RCCL) even at world size 1")
     ap.add_argument("--strong", default="auto", choices=["auto", "on", "off"],
                     help="strong_C4 block (the north_star reddit row-panel split, both splits, "
-                         "with the global plan's N = 1 point); auto = for C2 at N > 1")
+                         "with the global plan's N = 1 point); auto = for C2 at N > 1 under --full")
     ap.add_argument("--rebalance", type=int, default=2,
                     help="global split: rounds of measured-cost re-cutting "
                          "(bsmr_plan_shard_rebalance) before the timed steps")
@@ -114,6 +137,25 @@ def workload(args):
             f"C4: reddit_like Chung-Lu power law x{args.scale} (seed 20250803), fp32 A/B")
     return synth.dlmc_like(args.mask), args.K or 512, BF16, (
         f"C5: dlmc_like 2048^2 90% sparse {args.mask} mask (seed 7), bf16 A/B, fp32 accumulate")
+
+
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs: everything written stays under this
+DUMP_SAMPLE_SEED = 20250804
+
+
+def dump_outputs(path, P):
+    """--dump-outputs: P of the last timed step as <path>/P.npy (float32, CSR order of the stored
+    entries). A P over DUMP_MAX_BYTES is written as a fixed sample: the entries at
+    sorted(default_rng(DUMP_SAMPLE_SEED).integers(0, nnz, n)), the same positions in every run."""
+    import numpy as np
+
+    P = np.ascontiguousarray(P, np.float32).reshape(-1)
+    n = (DUMP_MAX_BYTES - 4096) // 4  # room for the .npy header
+    if P.size > n:
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).integers(0, P.size, n))
+        P = P[idx]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "P.npy"), P)
 
 
 # the CPUs this process may run on, read at start-up (an OpenMP runtime started with
@@ -718,9 +760,12 @@ def main():
         if not launched and (args.gpus > 1 or args.force_sharded):
             return self_launch(args)
     if os.environ.get("BSMR_BENCH_PROBE") == "1":  # launch-path test: report and stop (no GPU)
-        print(json.dumps({"probe": True, "rank": rank, "world": world, "gpus": args.gpus,
-                          "self_launched": os.environ.get("BSMR_BENCH_SELF_LAUNCHED") == "1"}),
-              flush=True)
+        # line and newline in one write: the ranks share the launcher's pipe, and a print() on an
+        # unbuffered stdout writes them separately, so two ranks' lines could run together
+        sys.stdout.write(json.dumps({"probe": True, "rank": rank, "world": world,
+                                     "gpus": args.gpus, "self_launched":
+                                     os.environ.get("BSMR_BENCH_SELF_LAUNCHED") == "1"}) + "\n")
+        sys.stdout.flush()
         return 0
     from bsmr import set_default_tuning, tuning_from_env
 
@@ -731,8 +776,8 @@ def main():
     if args.config == "C1":
         return main_c1(args)
     sharded = world > 1 or args.force_sharded
-    # in-run PMC traffic (children, before this process touches the GPU; N=1 only)
-    args.pmc_result = pmc_traffic_inrun(args) if not sharded else (None, None)
+    # in-run PMC traffic (--full: children, before this process touches the GPU; N=1 only)
+    args.pmc_result = pmc_traffic_inrun(args) if args.full and not sharded else (None, None)
     import torch
 
     if sharded:
@@ -780,6 +825,8 @@ def main_c1(args):
 
     med, times, steady = steady_runs(run_cpu)
     P_cpu = res["P"]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, P_cpu)
     cpu_ms = med * 1e3
     flops = 2.0 * nnz * K
     torch.cuda.set_device(0)
@@ -925,11 +972,16 @@ def main_single(args):
             timing["sustained_error"] = sus_reps
     if graph_err:
         timing["graph_error"] = graph_err
+    if args.dump_outputs:  # dP holds the last timed step's P (the last replay's, or the stream's)
+        torch.cuda.synchronize()
+        dump_outputs(args.dump_outputs, dP.cpu().numpy())
 
+    # everything below the timed steps is a leg of --full
+    split = args.full and not args.no_split
     # cold: before each step a 512 MiB write evicts the Infinity Cache (MALL) and the L2s, so
     # A, B and the plan come from HBM; only the SDDMM launch is inside the events
     cold_ms = cold_clean_ms = None
-    if args.cold_steps > 0 and not args.no_split:
+    if args.cold_steps > 0 and split:
         junk = torch.empty(512 << 20, dtype=torch.uint8, device=dev)
         evs = []
         for i in range(args.cold_steps):
@@ -962,9 +1014,9 @@ def main_single(args):
         del junk, sink
 
     # the same kernel split into its dense-tile-only and residual-only launches
-    prof = {} if args.no_split else plan.profile(dA.data_ptr(), dB.data_ptr(), K, dP.data_ptr(),
-                                                  iters=20, stream=sp, dtype=dtype)
-    P_gpu = dP.cpu().numpy()
+    prof = {} if not split else plan.profile(dA.data_ptr(), dB.data_ptr(), K, dP.data_ptr(),
+                                             iters=20, stream=sp, dtype=dtype)
+    P_gpu = dP.cpu().numpy() if args.full else None  # the baselines' checkData operand
     st_after = plan.stats()  # the launch layout is built on the first SDDMM call
 
     s = 4 if dtype == F32 else 2
@@ -973,7 +1025,7 @@ def main_single(args):
     bytes_alg = s * K * (M + N) + 4.0 * nnz + 4.0 * (M + 1) + 4.0 * nnz
     achieved = bytes_alg / (ms_per_step * 1e-3) / 1e9
     traffic, traffic_src = args.pmc_result
-    if traffic is None:  # a committed PMC summary measured on these kernel sources, if any
+    if traffic is None and args.full:  # a committed PMC summary measured on these kernel sources, if any
         t2, src2 = traffic_for(args, K)
         if t2 is not None:
             traffic, traffic_src = t2, dict(src2, inrun=traffic_src)
@@ -1019,6 +1071,7 @@ def main_single(args):
         "vs_baseline": None,
         "dtype": {0: "f32", 1: "f16", 2: "bf16"}[dtype],
         "data": "synthetic",
+        "full": bool(args.full),
         "config": {
             "workload": desc + f", K={K}, BSMR alpha={args.alpha} delta={args.delta}",
             "M": M, "N": N, "nnz": nnz, "K": K, "alpha": args.alpha, "delta": args.delta,
@@ -1041,7 +1094,7 @@ def main_single(args):
     mc = (traffic_src or {}).get("mfma_counters") if isinstance(traffic_src, dict) else None
     out["mfma"] = mfma_report(st, st_after, nnz, rby, dtiles, kern, no_tiles,
                               mfma_busy(mc, nnz, K) if mc else None)
-    if (no_tiles and not dtiles and not args.no_split and st["num_dense_tiles"] > 0
+    if (no_tiles and not dtiles and split and st["num_dense_tiles"] > 0
             and nnz <= 20_000_000):
         out["mfma"]["forced_tiles_split"] = forced_mfma_split(
             args, (M, N, rp, ci), K, dtype, dA, dB, dev, stream, P_gpu, flops_rank)
@@ -1056,10 +1109,10 @@ def main_single(args):
             "value": round(flops_rank * world / (cold_clean_ms * 1e-3) / 1e9, 2),
             "note": "median of steps each preceded by a 512 MiB read (MALL evicted, caches clean: "
                     "the launch writes back no dirty lines of the eviction)"}
-    if not args.no_vendor:
+    if args.full and not args.no_vendor:
         out["vendor_baseline"] = vendor_baseline(M, N, K, rp, ci, dA, dB, P_gpu, dtype, stream,
                                                  flops_rank, ms_per_step)
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         if dtype == F32:
             Ar, Br = A, B
         else:  # the oracle runs in fp32 on the same rounded half values
@@ -1458,15 +1511,21 @@ def main_sharded(args, rank, world):
     mode = "global" if args.shard == "global" else "local"
     r = (shard_global(args, rank, world, wl, dev) if mode == "global"
          else shard_local(args, rank, world, wl, dev))
-    do_strong = args.strong == "on" or (args.strong == "auto" and world > 1 and args.config == "C2")
+    do_strong = args.strong == "on" or (args.strong == "auto" and args.full and world > 1
+                                        and args.config == "C2")
     strong = strong_c4(args, rank, world, dev) if do_strong else None
     if rank != 0:
         dist.destroy_process_group()
         return
     tdt = {0: torch.float32, 1: torch.float16, 2: torch.bfloat16}[dtype]
     from bsmr import make_data
-    ref = _host_ref(M, N, rp, ci, K, make_data(M * K), make_data(N * K), dtype, tdt)
-    nerr = check_data(ref, r.pop("_P"))
+    P = r.pop("_P")
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, P)
+    nerr = None
+    if args.full:  # the gathered P against the product's host SDDMM
+        ref = _host_ref(M, N, rp, ci, K, make_data(M * K), make_data(N * K), dtype, tdt)
+        nerr = check_data(ref, P)
     nnz = len(ci)
     ms = r["ms_per_step"]
     s = 4 if dtype == 0 else 2
@@ -1493,6 +1552,7 @@ def main_sharded(args, rank, world):
         "vs_baseline": None,
         "dtype": {0: "f32", 1: "f16", 2: "bf16"}[dtype],
         "data": "synthetic",
+        "full": bool(args.full),
         "config": cfg,
         "shards": r["shards"],
         "roofline": {"bound": "hbm", "achieved": round(achieved, 2),

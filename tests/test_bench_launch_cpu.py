@@ -79,3 +79,34 @@ def test_cpu_leg_pins_one_thread_per_core_in_the_affinity_set():
         assert len(cpus) == min(max(n, 1), len(aff))
         assert len(set(cpus)) == len(cpus) and set(cpus) <= aff
     assert 1 <= bench.host_threads() <= len(aff)
+
+
+def test_dump_outputs_writes_float32_and_samples_large_outputs(tmp_path):
+    """bench.dump_outputs (--dump-outputs): a small P is written whole as float32; a P over the
+    64 MB cap is written as the same seeded sample of its entries every time, under the cap."""
+    import numpy as np
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    P = np.arange(1000, dtype=np.float64) * 0.5
+    bench.dump_outputs(str(tmp_path / "small"), P)
+    got = np.load(tmp_path / "small" / "P.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, P.astype(np.float32))
+    n = bench.DUMP_MAX_BYTES // 4 + 12345  # just over the cap
+    big = np.arange(n, dtype=np.float32)  # value = position (rounded to even past 2^24: monotone)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), big)
+    a, b = np.load(tmp_path / "a" / "P.npy"), np.load(tmp_path / "b" / "P.npy")
+    assert os.path.getsize(tmp_path / "a" / "P.npy") <= bench.DUMP_MAX_BYTES
+    assert a.dtype == np.float32 and np.array_equal(a, b)
+    assert np.all(np.diff(a) >= 0) and a[0] >= 0 and float(a[-1]) < n  # sorted positions of P
+    assert len(np.unique(a)) > 0.5 * len(a)  # spread over P, not one block
+
+
+def test_full_and_dump_outputs_are_options():
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--full", "--dump-outputs", "unused"], capture_output=True, text=True,
+                       timeout=300, env=_env(), cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert len(_probes(r.stdout)) == 1

@@ -165,7 +165,8 @@ def test_bench_sharded_two_ranks_one_gpu(extra):
     env = dict(os.environ, BSMR_DIST_BACKEND="gloo", OMP_NUM_THREADS="4")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1"] + extra
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
+           "--full"] + extra
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=540, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [x for x in r.stdout.splitlines() if x.startswith("{")]
@@ -206,7 +207,7 @@ def test_bench_sharded_rccl_one_rank():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
            os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-sharded", "--steps", "5",
-           "--warmup", "2", "--strong", "on", "--strong-scale", "0.1"]
+           "--warmup", "2", "--full", "--strong", "on", "--strong-scale", "0.1"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=540, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [x for x in r.stdout.splitlines() if x.startswith("{")]
@@ -232,7 +233,7 @@ def test_bench_self_launch_force_sharded_one_gpu():
     for k in ("BSMR_DIST_BACKEND", "WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-sharded",
-           "--steps", "5", "--warmup", "2", "--strong", "on", "--strong-scale", "0.05",
+           "--steps", "5", "--warmup", "2", "--full", "--strong", "on", "--strong-scale", "0.05",
            "--no-vendor", "--pmc", "off"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=540, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]

@@ -5,7 +5,8 @@
 #   smoke                   __graft_entry__.smoke()
 #   tests                   the whole pytest -m gpu suite (-v, per-test timeout)
 #   tests:<a+b+...>         pytest -m gpu -k 'a or b or ...'
-#   bench:<cfg>             bench.py line of one config (C1 C2 C3 C4 C4x1 C5u C5b C2k32 C2k512)
+#   bench:<cfg>             bench.py --full line of one config (C1 C2 C3 C4 C4x1 C5u C5b C2k32
+#                           C2k512): every leg of the report
 #   quick:<cfg>             the same without the CPU / vendor legs and PMC passes
 #   pmc:<cfg>               the same without the CPU / vendor legs, with the in-run PMC traffic
 #   sustained:<cfg>         quick, plus the busy-device time (--sustained: timing.sustained_*)
@@ -22,11 +23,11 @@
 #                           in turn (permutation hash and clustering ms per run)
 #   ablib:<variant.so>:cfg1,cfg2[:swap]   tools/ab_lib.sh: the in-tree library against a variant
 #                           build (swap: the variant runs first in each pair)
-#   driver                  exactly the driver's BENCH command (bench.py --gpus 1 --steps 20
-#                           --warmup 5, every leg: PMC traffic, CPU baseline, vendor)
-#   driverprof              rocprofv3 --kernel-trace --stats of exactly the driver's BENCH command
-#                           (bench.py --gpus 1 --steps 20 --warmup 5; --pmc off: the in-run PMC
-#                           children would run under the tracer too) + tools/rocprof_runs.py
+#   driver                  bench.py --gpus 1 --steps 20 --warmup 5 --full (every leg: PMC traffic,
+#                           CPU baseline, vendor)
+#   driverprof              rocprofv3 --kernel-trace --stats of bench.py --gpus 1 --steps 20
+#                           --warmup 5 (a plain run: only the warm-up and the timed steps are
+#                           traced) + tools/rocprof_runs.py
 #   guard                   tools/perf_guard.py --check profiles/perf_baseline.json: the 20
 #                           published SuiteSparse points + C2-C5 against the committed baseline,
 #                           rc 1 on any > 5 % loss (run after every layout-rule commit)
@@ -52,7 +53,7 @@ cfg_args() {
         *) echo "unknown config $1" >&2; return 1 ;;
     esac
 }
-QUICK="--no-cpu-baseline --no-vendor --pmc off"
+QUICK="--full --no-cpu-baseline --no-vendor --pmc off"
 
 run_step() {
     local s=$1 name=${1%%:*} arg=${1#*:}
@@ -66,16 +67,16 @@ run_step() {
             else
                 timeout -k 10 900 python3 -u -m pytest tests -x -v -m gpu -k "${arg//+/ or }" --timeout 600 --timeout-method thread > "$OUT/${f//+/_}.log" 2>&1
             fi ;;
-        bench) timeout -k 10 900 python3 bench.py $(cfg_args "$arg") > "$OUT/bench_$arg.json" 2> "$OUT/bench_$arg.err" ;;
+        bench) timeout -k 10 900 python3 bench.py $(cfg_args "$arg") --full > "$OUT/bench_$arg.json" 2> "$OUT/bench_$arg.err" ;;
         quick) timeout -k 10 600 python3 bench.py $(cfg_args "$arg") $QUICK > "$OUT/quick_$arg.json" 2> "$OUT/quick_$arg.err" ;;
         sustained) timeout -k 10 600 python3 bench.py $(cfg_args "$arg") $QUICK --sustained > "$OUT/sustained_$arg.json" 2> "$OUT/sustained_$arg.err" ;;
         graph) timeout -k 10 600 python3 bench.py $(cfg_args "$arg") $QUICK --graph > "$OUT/graph_$arg.json" 2> "$OUT/graph_$arg.err" ;;
-        pmc) timeout -k 10 600 python3 bench.py $(cfg_args "$arg") --no-cpu-baseline --no-vendor --pmc on > "$OUT/pmc_$arg.json" 2> "$OUT/pmc_$arg.err" ;;
+        pmc) timeout -k 10 600 python3 bench.py $(cfg_args "$arg") --full --no-cpu-baseline --no-vendor --pmc on > "$OUT/pmc_$arg.json" 2> "$OUT/pmc_$arg.err" ;;
         rocprof) timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_$arg" -o run -- \
                      python3 bench.py $(cfg_args "$arg") $QUICK --no-split > "$OUT/rocprof_$arg.json" 2> "$OUT/rocprof_$arg.err" ;;
         strong) timeout -k 10 1000 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 \
                      --master-addr 127.0.0.1 --master-port 29531 bench.py --gpus 1 --force-sharded \
-                     --strong on --strong-scale "$arg" --no-vendor --pmc off > "$OUT/strong_$arg.json" 2> "$OUT/strong_$arg.err" ;;
+                     --full --strong on --strong-scale "$arg" --no-vendor --pmc off > "$OUT/strong_$arg.json" 2> "$OUT/strong_$arg.err" ;;
         ss) timeout -k 10 1000 python3 -u tools/suitesparse_compare.py --out "$OUT/ss" > "$OUT/ss.log" 2>&1 ;;
         hybrid) timeout -k 10 1100 python3 -u tools/hybrid_table.py --run --out "$OUT/hybrid" > "$OUT/hybrid.log" 2>&1 ;;
         ab) IFS=: read -r _ var vals cfgs <<< "$s"
@@ -87,9 +88,9 @@ run_step() {
                 BSMR_DIAG=$d timeout -k 10 300 python3 tools/plan_time.py --workload reddit_like --scale "$scale" --batches 16384 > "$OUT/plan_${scale}_$d.json" 2>> "$OUT/$f.log" || return $?
                 python3 -c "import json; d=json.load(open('$OUT/plan_${scale}_$d.json')); r=list(d['runs'].values())[0]; print('scale $scale diag $d', r['row_reorder_ms'], r['rows_sha256'], r['num_clusters'], r['wall_s'])" >> "$OUT/planab_summary.txt"
             done ;;
-        driver) timeout -k 10 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/driver.json" 2> "$OUT/driver.err" ;;
+        driver) timeout -k 10 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > "$OUT/driver.json" 2> "$OUT/driver.err" ;;
         driverprof) timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_driver" -o run -- \
-                     python3 bench.py --gpus 1 --steps 20 --warmup 5 --pmc off > "$OUT/driverprof.json" 2> "$OUT/driverprof.err" &&
+                     python3 bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/driverprof.json" 2> "$OUT/driverprof.err" &&
                    python3 tools/rocprof_runs.py "$(ls "$OUT"/prof_driver/*/run_kernel_trace.csv "$OUT"/prof_driver/run_kernel_trace.csv 2>/dev/null | head -1)" > "$OUT/driverprof_runs.json" ;;
         guard)
             if [ "$arg" = "record" ]; then

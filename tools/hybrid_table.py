@@ -20,6 +20,7 @@ Two steps:
 """
 import argparse
 import csv
+import hashlib
 import json
 import os
 import shutil
@@ -65,8 +66,23 @@ def build_analyzer(workdir):
     return exe
 
 
-def analyzer_hybrid(exe, logdir, K, workdir):
-    """Run the reference analyzer over one matrix's K logs; its results_hybrid_<K>.csv rows."""
+def logs_sha256(logdir, K):
+    """sha256 over the names and contents of one matrix's K logs, in sorted order (what the
+    analyzer was given; tests/test_analyze_results_cpu.py checks its stored output against it)."""
+    h = hashlib.sha256()
+    for fn in sorted(os.listdir(logdir)):
+        if fn.startswith(f"BSMR_k_{K}_a_"):
+            h.update(fn.encode() + b"\0")
+            with open(os.path.join(logdir, fn), "rb") as f:
+                h.update(f.read())
+    return h.hexdigest()
+
+
+def analyzer_hybrid(exe, logdir, K, workdir, keep=None):
+    """Run the reference analyzer over one matrix's K logs; its results_hybrid_<K>.csv rows.
+    keep: a directory that receives the analyzer's results_<K>.csv and results_hybrid_<K>.csv,
+    with the `file` column (the .mtx path the log recorded, a directory of the run that wrote the
+    logs) cut down to the file name."""
     d = tempfile.mkdtemp(dir=workdir)
     files = []
     for fn in sorted(os.listdir(logdir)):
@@ -76,6 +92,17 @@ def analyzer_hybrid(exe, logdir, K, workdir):
     r = subprocess.run([exe] + files, capture_output=True, text=True, timeout=120, cwd=d)
     if r.returncode != 0:
         raise RuntimeError(f"analyzer failed on {logdir} K={K}: {r.stderr[-500:]}")
+    if keep:
+        os.makedirs(keep, exist_ok=True)
+        for fn in (f"results_{K}.csv", f"results_hybrid_{K}.csv"):
+            with open(os.path.join(d, fn)) as f:
+                lines = f.read().splitlines()
+            assert lines[0].startswith("file,"), lines[0]
+            with open(os.path.join(keep, fn), "w") as f:
+                f.write(lines[0] + "\n")
+                for line in lines[1:]:
+                    path, rest = line.split(",", 1)
+                    f.write(os.path.basename(path) + "," + rest + "\n")
     return list(csv.DictReader(open(os.path.join(d, f"results_hybrid_{K}.csv"))))
 
 
@@ -93,15 +120,18 @@ def published_rows(name, K):
     return None, None, os.path.relpath(path, REF)
 
 
-def report(logs_root, out, prefix):
+def report(logs_root, out, prefix, fixtures=None):
     os.makedirs(out, exist_ok=True)
+    manifest = {}
     work = tempfile.mkdtemp(prefix="hybrid_")
     exe = build_analyzer(work)
     rows = []
     for name in MATRICES:
         logdir = os.path.join(logs_root, f"{prefix}{name}")
         for K in KS:
-            hyb = analyzer_hybrid(exe, logdir, K, work)
+            hyb = analyzer_hybrid(exe, logdir, K, work,
+                                  os.path.join(fixtures, name) if fixtures else None)
+            manifest[f"{name}/{K}"] = logs_sha256(logdir, K)
             assert len(hyb) == 1, (name, K, hyb)
             h = hyb[0]
             line, pub, src = published_rows(name, K)
@@ -129,6 +159,9 @@ def report(logs_root, out, prefix):
            "rows": rows}
     with open(os.path.join(out, "hybrid_table.json"), "w") as f:
         json.dump(res, f, indent=1)
+    if fixtures:  # which logs the stored analyzer output was computed from
+        with open(os.path.join(fixtures, "logs_sha256.json"), "w") as f:
+            json.dump(manifest, f, indent=1, sort_keys=True)
     print("| matrix | K | MI355X BSMR | δ=0 (MFMA tiles) | δ=1.1 (residual only) | hybrid/δ0 | "
           "hybrid/δ1.1 | RTX 4090 BSMR | δ=0 | δ=1.1 | hybrid/δ0 | hybrid/δ1.1 | published row |")
     print("|---|---|---|---|---|---|---|---|---|---|---|---|---|")
@@ -150,12 +183,16 @@ def main():
     ap.add_argument("--logs", default=None, help="--report: directory holding the log dirs")
     ap.add_argument("--prefix", default="mi355x_testmode_",
                     help="--report: log directory name prefix (logs_ for a --run output)")
+    ap.add_argument("--fixtures", default=None,
+                    help="--report: also keep the analyzer's results_<K>.csv and results_hybrid_<K>.csv "
+                         "per matrix under this directory, with logs_sha256.json (the test fixtures "
+                         "tests/golden/mi355x_analyzer)")
     ap.add_argument("--matrices", default=",".join(MATRICES))
     args = ap.parse_args()
     if args.run:
         run(args.out, args.matrices.split(","))
     if args.report:
-        report(args.logs or args.out, args.out, args.prefix)
+        report(args.logs or args.out, args.out, args.prefix, args.fixtures)
 
 
 if __name__ == "__main__":

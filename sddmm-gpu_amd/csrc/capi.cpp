@@ -98,6 +98,40 @@ extern "C" int bsmr_tuning_from_env(bsmr_tuning* t) {
 
 namespace {
 
+// launch-layout knobs onto a plan's fields; "auto" keeps the defaults. No device involved.
+void apply_tuning(Plan& p, const bsmr_tuning& t) {
+    p.diag = t.diag;
+    if (t.tile_min_f32 >= 0) p.tile_min_f32 = static_cast<u32>(t.tile_min_f32);
+    if (t.tile_min_half >= 0) p.tile_min_half = static_cast<u32>(t.tile_min_half);
+    if (t.piece_max >= 0) p.piece_max = std::min<u32>(RB_PIECE_MAX, std::max(1, t.piece_max));
+    if (t.piece_weight >= 0) p.piece_weight = t.piece_weight;
+    if (t.shard_piece_weight >= 0) p.shard_piece_weight = t.shard_piece_weight;
+    if (t.dense_min >= 0) p.dense_min = t.dense_min;
+    if (t.orig_rows >= 0) p.orig_rows = t.orig_rows ? 1 : 0;
+    if (t.orig_contig >= 0) p.orig_contig = t.orig_contig;
+    if (t.dense_ks >= 0) p.dense_ks = t.dense_ks;
+    if (t.dense_ns >= 0) p.dense_ns = t.dense_ns;
+    if (t.out_staged >= 0) p.out_staged = t.out_staged ? 1 : 0;
+    if (t.out_packed >= 0) p.out_packed = t.out_packed ? 1 : 0;
+    if (t.stage_nt >= 0) p.stage_nt = t.stage_nt ? 1 : 0;
+    if (t.rb_rows > 0) p.rb_rows_force = t.rb_rows;
+    if (t.late_b >= 0) p.late_b = t.late_b;
+    if (t.item_cap >= 0) p.item_cap = t.item_cap;
+    if (t.item_sched >= 0)
+        p.item_cost_cuts = p.item_lpt = p.small_sparse_rb = t.item_sched != 0;
+    if (t.cluster_filter >= 0) p.cluster_filter = t.cluster_filter ? 1 : 0;
+    if (t.pair_min_items >= 0) p.pair_min_items = static_cast<u32>(t.pair_min_items);
+    if (t.batches >= 0) p.batches = t.batches ? 1 : 0;
+    if (t.ptile >= 0) p.ptile_mode = t.ptile ? 1 : 0;
+    if (t.ptile_tpi >= 0) p.ptile_tpi = static_cast<u32>(std::min(64, t.ptile_tpi));
+    if (t.piece_balance >= 0) p.piece_balance = t.piece_balance ? 1 : 0;
+    if (t.col_blocks >= 0) p.col_blocks = std::min(2, t.col_blocks);
+    if (t.l2_range_kb >= 0) {
+        p.l2_range_kb = static_cast<u32>(std::max(64, t.l2_range_kb));
+        p.l2_range_user = true;
+    }
+}
+
 // device, stream and the launch / tuning options shared by bsmr_plan_create and
 // bsmr_plan_import_rows
 int init_plan(Plan& p, const bsmr_plan_options& o) {
@@ -125,38 +159,7 @@ int init_plan(Plan& p, const bsmr_plan_options& o) {
         p.rb_lds_kb = o.lds_budget_kb;
         p.rb_lds_user = true;
     }
-    if (const bsmr_tuning* t = o.tuning) {  // launch-layout knobs; "auto" keeps the defaults
-        p.diag = t->diag;
-        if (t->tile_min_f32 >= 0) p.tile_min_f32 = static_cast<u32>(t->tile_min_f32);
-        if (t->tile_min_half >= 0) p.tile_min_half = static_cast<u32>(t->tile_min_half);
-        if (t->piece_max >= 0) p.piece_max = std::min<u32>(RB_PIECE_MAX, std::max(1, t->piece_max));
-        if (t->piece_weight >= 0) p.piece_weight = t->piece_weight;
-        if (t->shard_piece_weight >= 0) p.shard_piece_weight = t->shard_piece_weight;
-        if (t->dense_min >= 0) p.dense_min = t->dense_min;
-        if (t->orig_rows >= 0) p.orig_rows = t->orig_rows ? 1 : 0;
-        if (t->orig_contig >= 0) p.orig_contig = t->orig_contig;
-        if (t->dense_ks >= 0) p.dense_ks = t->dense_ks;
-        if (t->dense_ns >= 0) p.dense_ns = t->dense_ns;
-        if (t->out_staged >= 0) p.out_staged = t->out_staged ? 1 : 0;
-        if (t->out_packed >= 0) p.out_packed = t->out_packed ? 1 : 0;
-        if (t->stage_nt >= 0) p.stage_nt = t->stage_nt ? 1 : 0;
-        if (t->rb_rows > 0) p.rb_rows_force = t->rb_rows;
-        if (t->late_b >= 0) p.late_b = t->late_b;
-        if (t->item_cap >= 0) p.item_cap = t->item_cap;
-        if (t->item_sched >= 0)
-            p.item_cost_cuts = p.item_lpt = p.small_sparse_rb = t->item_sched != 0;
-        if (t->cluster_filter >= 0) p.cluster_filter = t->cluster_filter ? 1 : 0;
-        if (t->pair_min_items >= 0) p.pair_min_items = static_cast<u32>(t->pair_min_items);
-        if (t->batches >= 0) p.batches = t->batches ? 1 : 0;
-        if (t->ptile >= 0) p.ptile_mode = t->ptile ? 1 : 0;
-        if (t->ptile_tpi >= 0) p.ptile_tpi = static_cast<u32>(std::min(64, t->ptile_tpi));
-        if (t->piece_balance >= 0) p.piece_balance = t->piece_balance ? 1 : 0;
-        if (t->col_blocks >= 0) p.col_blocks = std::min(2, t->col_blocks);
-        if (t->l2_range_kb >= 0) {
-            p.l2_range_kb = static_cast<u32>(std::max(64, t->l2_range_kb));
-            p.l2_range_user = true;
-        }
-    }
+    if (o.tuning) apply_tuning(p, *o.tuning);
     return BSMR_OK;
 }
 
@@ -626,5 +629,85 @@ extern "C" int bsmr_plan_shard_dtype(const bsmr_plan* plan, uint32_t K, int dtyp
     }
     *p0 = cuts[rank];
     *p1 = cuts[rank + 1];
+    return BSMR_OK;
+}
+
+namespace {
+constexpr uint32_t RB_GEOM_WORDS = 13;
+
+RbKnobs debug_knobs(const bsmr_tuning* t) {
+    Plan p;  // defaults; no device, no stream
+    if (t) apply_tuning(p, *t);
+    return rb_knobs(p);
+}
+}  // namespace
+
+// debug: the row-block geometry (rb_schedule.hpp rb_geometry) of rows of rowBytes over Rs staged
+// rows holding n0 entries, NS gathered columns, a plan of nnz entries, original-order (orig) or
+// column (cols) blocks, under tuning t (null: defaults) on a device of cus compute units. Needs no
+// device. out[13] = {rowBytes, orig, cols, RB, NT, nRB, lds bytes, l2Kb, m, stagedWanted, staged,
+// outCap, perBucket}. Not in the header (tests/test_rb_schedule_cpu.py)
+extern "C" int bsmr_debug_rb_geometry(uint32_t rowBytes, uint32_t Rs, uint32_t n0, uint32_t NS,
+                                      uint32_t nnz, int orig, int cols, const bsmr_tuning* t, int cus,
+                                      uint32_t* out) {
+    if (!out || rowBytes == 0 || cus <= 0 || NS > (1u << 22)) return BSMR_ERR_INVALID;
+    const RbGeometry g = rb_geometry(rowBytes, Rs, n0, NS, nnz, cus, orig && !cols, cols != 0, debug_knobs(t));
+    const uint32_t w[RB_GEOM_WORDS] = {g.rowBytes, g.orig, g.cols, g.RB, g.NT, g.nRB, static_cast<uint32_t>(g.lds),
+                                       g.l2Kb, g.m, g.stagedWanted, g.staged, g.outCap, g.perBucket};
+    std::copy(w, w + RB_GEOM_WORDS, out);
+    return BSMR_OK;
+}
+
+// debug: the host-only scheduler (rb_schedule.hpp rb_schedule) on n entries given by their sorted
+// columns (by row block, then column), rbEnd[nRB], the per-block kept-tile prefix keptBegin[nRB +
+// 1] (null: no kept tiles), the geometry words of bsmr_debug_rb_geometry and tuning t (null:
+// defaults); threads = host threads (0: the library's choice; the result does not depend on it).
+// Needs no device. host_out = {n items, p pieces, items (4 u32 each), item ends, pieces (2 u32
+// each), itemStat (4 u32 each), dynamic batches, work items}: *len = 4 + 9 n + 2 p; call with
+// host_out = null for the length. Not in the header (tests/test_rb_schedule_cpu.py)
+extern "C" int bsmr_debug_rb_schedule(const uint32_t* sorted_cols, uint64_t n, const uint32_t* rbEnd,
+                                      const uint32_t* keptBegin, uint32_t NS, const uint32_t* geom,
+                                      const bsmr_tuning* t, int threads, uint32_t* host_out,
+                                      uint64_t* len) {
+    if (!geom || !rbEnd || (n && !sorted_cols) || !len || threads < 0 || n > 0xffffffffull)
+        return BSMR_ERR_INVALID;
+    RbScheduleIn in;
+    RbGeometry& g = in.geom;
+    g.rowBytes = geom[0];
+    g.orig = geom[1];
+    g.cols = geom[2];
+    g.RB = geom[3];
+    g.NT = geom[4];
+    g.nRB = geom[5];
+    g.lds = geom[6];
+    g.l2Kb = geom[7];
+    g.m = geom[8];
+    g.stagedWanted = geom[9];
+    g.staged = geom[10];
+    g.outCap = geom[11];
+    g.perBucket = geom[12];
+    if (g.nRB == 0 || g.m == 0 || g.perBucket == 0 || g.NT == 0 || g.RB == 0 || rbEnd[g.nRB - 1] != n)
+        return BSMR_ERR_INVALID;
+    in.entries = sorted_cols;
+    in.n = n;
+    in.rbEnd = rbEnd;
+    in.keptBegin = keptBegin;
+    in.NS = NS;
+    in.knobs = debug_knobs(t);
+    in.threads = static_cast<unsigned>(threads);
+    RbScheduleOut o;
+    rb_schedule(in, o);
+    const uint64_t ni = o.items.size(), np = o.pieces.size();
+    *len = 4 + 9 * ni + 2 * np;
+    if (!host_out) return BSMR_OK;
+    uint32_t* w = host_out;
+    *w++ = static_cast<uint32_t>(ni);
+    *w++ = static_cast<uint32_t>(np);
+    for (const RbItem& it : o.items) { *w++ = it.x; *w++ = it.y; *w++ = it.z; *w++ = it.w; }
+    for (uint32_t e : o.ends) *w++ = e;
+    for (const RbPiece& pc : o.pieces) { *w++ = pc.x; *w++ = pc.y; }
+    for (const RbItem& it : o.itemStat) { *w++ = it.x; *w++ = it.y; *w++ = it.z; *w++ = it.w; }
+    *w++ = o.dyn;
+    *w++ = o.nWorkItems;
     return BSMR_OK;
 }

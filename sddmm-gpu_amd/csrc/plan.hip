@@ -18,9 +18,8 @@
 
 #include <algorithm>
 #include <chrono>
-#include <queue>
-#include <thread>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstring>
 #include <vector>
@@ -1485,47 +1484,6 @@ u32 kept_warp_mask(u32 B) {
     return reach[0];
 }
 
-// Rows per row block for rows of rowBytes: a multiple of 16 with RB * rowBytes within the LDS
-// budget, at most 1024 (10-bit local row in the entry metadata) and no more than the matrix needs.
-u32 rowblock_rows(u32 rowBytes, u32 lds_kb, u32 R) {
-    // (rows of <= 512 B: the workgroup's last LDS word is the piece-batch counter of k_sddmm_rb /
-    // k_sddmm_rb_pair, so a whole-LDS budget leaves it out; an 80 KiB image is caught where the
-    // block size is final)
-    u64 bytes = static_cast<u64>(lds_kb) * 1024;
-    if (rowBytes <= 512 && bytes >= 160u * 1024u) bytes = 160u * 1024u - 16u;
-    u32 rb = static_cast<u32>(bytes / rowBytes / 16 * 16);
-    rb = std::min<u32>(std::max<u32>(rb, 16), 1024);
-    return std::min<u32>(rb, std::max<u32>((R + 15) / 16 * 16, 16));
-}
-
-namespace {
-// split q chunks over segments by cost (largest remainder); every non-empty segment gets >= 1,
-// and >= ceil(cost / cap) when cap > 0 (no chunk above cap; the total may then exceed q)
-std::vector<u32> apportion(const std::vector<double>& cost, u32 q, double cap = 0.0) {
-    const size_t n = cost.size();
-    std::vector<u32> out(n, 0);
-    double tot = 0;
-    for (double c : cost) tot += c;
-    if (tot <= 0) return out;
-    std::vector<std::pair<double, size_t>> frac;
-    u32 used = 0;
-    for (size_t i = 0; i < n; ++i) {
-        if (cost[i] <= 0) continue;
-        const double ideal = q * cost[i] / tot;
-        out[i] = std::max<u32>(1, static_cast<u32>(std::floor(ideal)));
-        if (cap > 0) out[i] = std::max<u32>(out[i], static_cast<u32>(std::ceil(cost[i] / cap)));
-        used += out[i];
-        // capped: rank by what is still missing; uncapped: by the fractional part (the round-2
-        // rule, so BSMR_ITEM_SCHED=0 BSMR_ITEM_CAP=0 reproduces the round-2 item lists)
-        frac.push_back({cap > 0 ? ideal - out[i] : ideal - std::floor(ideal), i});
-    }
-    std::stable_sort(frac.begin(), frac.end(),
-                     [](const auto& a, const auto& b) { return a.first > b.first; });
-    for (size_t k = 0; used < q && k < frac.size(); ++k, ++used) ++out[frac[k].second];
-    return out;
-}
-}  // namespace
-
 // a candidate layout the launch does not use: its device arrays freed (its counts stay)
 static void release_layout(Plan::RowBlockLayout& L) {
     L.meta.release();
@@ -1595,201 +1553,72 @@ std::shared_ptr<const Plan::RowBlockLayout> Plan::rowblock_layout(u32 rowBytes, 
     return L;
 }
 
-// Row-block launch layout over panels [pa, pb) (the whole plan, or one row-panel shard).
-// the layout's host passes over [0, n) on up to 16 threads: f(thread, begin, end), contiguous
-// ranges, each index visited once (results written per index are independent of the split)
-template <class F>
-static void par_for(size_t n, F&& f, size_t serial_below = 2048) {
-    const unsigned T = std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
-    if (n < serial_below || T == 1) {
-        f(0u, size_t{0}, n);
-        return;
-    }
-    std::vector<std::thread> th;
-    const size_t chunk = (n + T - 1) / T;
-    for (unsigned t = 0; t < T; ++t) {
-        const size_t a = t * chunk, b = std::min(n, a + chunk);
-        if (a < b) th.emplace_back([&f, t, a, b]() { f(t, a, b); });
-    }
-    for (auto& x : th) x.join();
+// The row-block layout build in stages: block geometry and item scheduling are
+// host-only (rb_schedule.cpp); the two stages below are its device work.
+static_assert(sizeof(RbItem) == sizeof(uint4) && alignof(RbItem) == alignof(uint4) &&
+                  offsetof(RbItem, y) == offsetof(uint4, y) && offsetof(RbItem, z) == offsetof(uint4, z) &&
+                  offsetof(RbItem, w) == offsetof(uint4, w),
+              "RbItem is uploaded as uint4");
+static_assert(sizeof(RbPiece) == sizeof(uint2) && alignof(RbPiece) == alignof(uint2) &&
+                  offsetof(RbPiece, y) == offsetof(uint2, y),
+              "RbPiece is uploaded as uint2");
+static_assert(RB_XCDS == XCD_BUCKETS && RB_COL_MASK == (1u << 22) - 1, "rb_schedule.hpp constants");
+
+RbKnobs rb_knobs(const Plan& p) {
+    RbKnobs k;
+    k.diag = p.diag;
+    k.rb_lds_kb = p.rb_lds_kb;
+    k.rb_lds_kb_staged = p.rb_lds_kb_staged;
+    k.l2_range_kb = p.l2_range_kb;
+    k.l2_range_kb_staged = p.l2_range_kb_staged;
+    k.rb_lds_user = p.rb_lds_user;
+    k.l2_range_user = p.l2_range_user;
+    k.out_staged = p.out_staged;
+    k.out_staged_min = p.out_staged_min;
+    k.rb_rows_force = p.rb_rows_force;
+    k.small_sparse_rb = p.small_sparse_rb;
+    k.batches = p.batches;
+    k.item_cost_cuts = p.item_cost_cuts;
+    k.item_lpt = p.item_lpt;
+    k.piece_max = p.piece_max;
+    k.piece_weight = p.piece_weight;
+    k.shard_piece_weight = p.shard_piece_weight;
+    k.item_cap = p.item_cap;
+    k.item_fixed = p.item_fixed;
+    k.orig_contig = p.orig_contig;
+    k.batch_min_phases = p.batch_min_phases;
+    k.piece_balance = p.piece_balance;
+    return k;
 }
 
-// Static piece order of one row-block item (Plan::piece_balance). The kernel deals phase ph's
-// pieces [ph NG, (ph + 1) NG) to row-groups gr, reversed in odd phases (sddmm.hip: piece
-// ph NG + (ph odd ? NG - 1 - gr : gr)); a wave's 64 / G row-groups run a phase in lockstep, so a
-// wave pays per phase its longest piece plus one gather (w entry-steps, the item cost model's
-// piece weight). With the pieces longest first in position order, the waves that also run the
-// short last phase end last. Here the same pieces, sorted longest first, go out in runs — one
-// run per (wave, phase) bucket, as many pieces as that bucket has positions — always to the wave
-// whose running cost is lowest (LPT over the buckets), so waves with two phases get shorter runs.
-static void balance_pieces(std::vector<uint2>& pcs, u32 NT, u32 G, double w) {
-    const u32 NG = NT / G, GW = 64 / G, NW = NT / 64;
-    const u32 np = static_cast<u32>(pcs.size());
-    if (np <= NG) return;  // one phase: every wave has one bucket already in cost order
-    const u32 nph = (np + NG - 1) / NG;
-    struct Bucket {
-        u32 ph, cap;
-        std::vector<u32> pos;  // the positions (piece indices) of its row-groups
-    };
-    std::vector<std::vector<Bucket>> wb(NW);
-    for (u32 ph = 0; ph < nph; ++ph)
-        for (u32 wv = 0; wv < NW; ++wv) {
-            Bucket bk{ph, 0, {}};
-            for (u32 gr = wv * GW; gr < (wv + 1) * GW; ++gr) {
-                const u32 pos = ph * NG + ((ph & 1) ? NG - 1 - gr : gr);
-                if (pos < np) bk.pos.push_back(pos);
-            }
-            bk.cap = static_cast<u32>(bk.pos.size());
-            if (bk.cap) wb[wv].push_back(std::move(bk));
-        }
-    // buckets of a wave largest first
-    for (auto& v : wb)
-        std::stable_sort(v.begin(), v.end(), [](const Bucket& a, const Bucket& b) { return a.cap > b.cap; });
-    std::vector<double> cost(NW, 0.0);
-    std::vector<u32> next(NW, 0);
-    std::vector<uint2> out(np);
-    u32 k = 0;  // pcs sorted longest first
-    while (k < np) {
-        u32 best = NW;
-        for (u32 wv = 0; wv < NW; ++wv)
-            if (next[wv] < wb[wv].size() && (best == NW || cost[wv] < cost[best])) best = wv;
-        const Bucket& bk = wb[best][next[best]++];
-        cost[best] += static_cast<double>((pcs[k].y >> 22) + 1) + w;
-        for (u32 pos : bk.pos) out[pos] = pcs[k++];
-    }
-    pcs.swap(out);
-}
+namespace {
+// what the device sort leaves on the host for the scheduler
+struct SortedEntries {
+    u32 n = 0, nd = 0;              // entries (residual + demoted); demoted
+    std::vector<u32> hmeta, rbEnd;  // the sorted entry words; per row block the end of its entries
+    std::vector<u32> hkept;         // kept tile ids
+    std::vector<u32> keptBegin;     // per row block its first kept tile (nRB + 1; empty: no tiles)
+};
+}  // namespace
 
-int Plan::build_rowblock_layout(RowBlockLayout& L, u32 rowBytes, u32 pa, u32 pb, u32 tileMin,
-                                bool orig, bool cols) const {
-    L.rowBytes = 0;
-    L.orig = orig && !cols;
-    L.cols = cols;
-    orig = orig && !cols;
-    // whole: original-order blocks of rows (orig) or of columns (cols), every entry residual
-    const bool whole = orig || cols;
-    // the gathered index space: columns of S, or (column blocks) its rows
-    const u32 NS = cols ? M : N;
-    hipStream_t s = stream;
-    if (NS > (1u << 22)) {
-        set_error(cols ? "column-block layout needs M <= 2^22" : "row-block layout needs N <= 2^22");
-        return BSMR_ERR_UNSUPPORTED;
-    }
-    if (whole && (pa != 0 || pb != P)) {
-        set_error("original-order row / column blocks cover the whole plan only");
-        return BSMR_ERR_INVALID;
-    }
-    // BSMR_DIAG & 524288: section times of this build to stderr (host-side layout cost)
-    auto lap_t = std::chrono::steady_clock::now();
-    auto lap = [&](const char* what) {
-        if (!(diag & 524288)) return;
-        const auto t = std::chrono::steady_clock::now();
-        std::fprintf(stderr, "[rb layout %u B] %-12s %8.1f ms\n", rowBytes, what,
-                     std::chrono::duration<double, std::milli>(t - lap_t).count());
-        lap_t = t;
-    };
-    const u32 qa = whole ? 0 : 16 * pa, qend = orig ? M : cols ? N : std::min(R, 16 * pb);
-    const u32 Rs = qend > qa ? qend - qa : 0;  // (reordered) rows of the range
-    int cus = 256;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus <= 0)
-        cus = 256;
-    const u32 ebase = whole ? 0 : h_sparseValueOffsets[pa];
-    // residual entries of the range (original order: every stored entry)
-    const u32 n0 = whole ? nnz : h_sparseValueOffsets[pb] - ebase;
-    // staged output (results through LDS, written per item in CSR order) for large P
-    const bool stagedWanted = out_staged == 1 || (out_staged == -1 && 4ull * nnz > out_staged_min);
-    // staged-output budget by row size (item_sched): 1 KiB rows take an 80 KiB image (two
-    // workgroups per CU, results stored directly), 2 KiB rows the whole 160 KiB (mycielskian K =
-    // 256 / 512: 379 -> 358 us and 896 -> 771 us against the 120 KiB staged image;
-    // profiles/r03f/itemcal); 512-byte rows keep the tuned 120 KiB staged image (C4)
-    const u32 stagedKb = !item_cost_cuts || rowBytes <= 512 ? rb_lds_kb_staged : rowBytes <= 1024 ? 80u : 160u;
-    // 2 KiB rows (fp32 K = 512, fp16/bf16 K = 1024) take the whole-LDS image and 8 MiB column
-    // ranges whatever P's size: an item's A image is 80 rows x 2 KiB, and fewer, wider ranges
-    // restage it less (mycielskian14 / 15 / 16 K = 512: 100 -> 87, 253 -> 238, 735 -> 716 us;
-    // 1 KiB rows lose with 8 MiB ranges: mycielskian16 K = 256 358 -> 468 us; profiles/r03u).
-    // Sparse rows (< 64 stored entries per row) keep the small-row-block rule below (Trefethen
-    // K = 512: 48-row blocks 48.1 us, 80-row blocks 51.5 us; profiles/r03v)
-    const bool bigRows = item_cost_cuts && rowBytes >= 2048 && n0 >= 64ull * Rs;
-    const u32 ldsKb = (stagedWanted || bigRows) && !rb_lds_user ? stagedKb : rb_lds_kb;
-    // staged 512-byte rows (C4 reddit-like x1 fp32 K = 128): 8 MiB ranges too, half the A
-    // restaging for a B range twice the L2 (4.01 -> 3.89 ms over three alternating runs,
-    // profiles/r03y; C3 fp16 K = 256 neutral)
-    // ... but at least two ranges per XCD when its B share exceeds its 4 MiB L2: one range of the
-    // whole share ran C4 x0.5 (7.5 MiB per XCD) at 1.33 ms against 1.00 ms with two
-    // (profiles/r04x); x1 keeps two 7.5 MiB ranges; a share that fits the L2 stays one range
-    // (mycielskian16 K = 128, 3 MiB per XCD: 166 us against 181 us with two; profiles/r04zr)
-    const bool staged512 = stagedWanted && item_cost_cuts && rowBytes == 512;
-    const double shareKb = static_cast<double>(NS) * rowBytes / XCD_BUCKETS / 1024.0;
-    const u32 l2Kb = l2_range_user ? l2_range_kb
-                     : staged512 ? (shareKb > 4096.0 ? std::min<u32>(8192u, static_cast<u32>(std::ceil(shareKb / 2)) + 1)
-                                                     : 8192u)
-                     : bigRows ? 8192u
-                     : stagedWanted ? l2_range_kb_staged : l2_range_kb;
-    u32 RBr = rowblock_rows(rowBytes, ldsKb, Rs);
-    {
-        // sparse rows (< 64 stored entries per row: banded / FEM patterns) keep their row blocks
-        // whole, one item each; when there are more row blocks than workgroup slots, use the
-        // smallest row block that needs no more rounds of slots, so the last round is full
-        // (cop20k-like C3: 421 blocks of 288 rows = 1.6 rounds -> 505 blocks of 240 rows)
-        const size_t lds0 = static_cast<size_t>(RBr) * rowBytes;
-        const u32 slots = static_cast<u32>(cus) * (lds0 > 80 * 1024 ? 1u : 2u);
-        const u32 nRB0 = (Rs + RBr - 1) / std::max<u32>(RBr, 1);
-        // (column blocks keep the whole image: their point is long row runs per block)
-        if (cols) {
-        } else if (Rs && n0 < 64ull * Rs && nRB0 > slots) {
-            const u32 rounds = (nRB0 + slots - 1) / slots;
-            const u32 rb = (Rs + rounds * slots - 1) / (rounds * slots);
-            RBr = std::min(RBr, std::max<u32>(16, (rb + 15) / 16 * 16));
-        } else if (Rs && n0 < 64ull * Rs && small_sparse_rb) {
-            // fewer row blocks than slots: a block would be cut into chunks that each restage
-            // its whole image for a few entries (Trefethen_20000 K = 64: 35 blocks of 576 rows in
-            // 257 items, 15.2 us). One block per slot instead, at two workgroups per CU when the
-            // image fits 80 KiB (48-row blocks in 512 items: 8.9 us; profiles/r03e/itemcal)
-            const u32 s2 = static_cast<u32>(cus) * 2u;
-            const u32 rb2 = std::max<u32>(16, ((Rs + s2 - 1) / s2 + 15) / 16 * 16);
-            const u32 rb1 = std::max<u32>(16, ((Rs + cus - 1) / cus + 15) / 16 * 16);
-            if (static_cast<size_t>(rb2) * rowBytes <= 80 * 1024) RBr = std::min(RBr, rb2);
-            else RBr = std::min(RBr, rb1);
-        }
-    }
-    if (Rs && (cols || n0 >= 64ull * Rs) && !(diag & 32768)) {
-        // non-sparse rows: the same number of row blocks, of equal size (a multiple of 16), so
-        // no short last block and every item stages the smallest image that count allows (C2
-        // nips-like: 5 x 288 + 60 rows -> 5 x 256 + 220, 10.80 -> 10.63 us; BSMR_DIAG & 32768
-        // keeps the LDS-budget size)
-        const u32 nb0 = (Rs + RBr - 1) / RBr;
-        RBr = std::min(RBr, std::max<u32>(16, ((Rs + nb0 - 1) / nb0 + 15) / 16 * 16));
-    }
-    // column blocks: the largest image the workgroup's LDS takes (fewer blocks, longer row runs:
-    // C2 nips-like 288 -> 304 columns, 78.7 K -> 75.8 K pieces)
-    // (staged output keeps its budget: the result slots live past the image)
-    if (cols && !rb_lds_user && !stagedWanted && Rs) {
-        // (batches never: no piece-batch counter to keep free, so the image may fill the LDS)
-        const u32 rfull = std::min<u32>(std::min<u32>(160u * 1024u / rowBytes / 16 * 16, 1024),
-                                        std::max<u32>((Rs + 15) / 16 * 16, 16));
-        const u32 rmax = batches == 0 ? rfull : rowblock_rows(rowBytes, 160, Rs), nb0 = (Rs + rmax - 1) / rmax;
-        RBr = std::min(rmax, std::max<u32>(16, ((Rs + nb0 - 1) / nb0 + 15) / 16 * 16));
-    }
-    if (rb_rows_force > 0)  // tuning: rows per block (a multiple of 16 within the LDS budget)
-        RBr = std::min(rowblock_rows(rowBytes, 160, Rs),
-                       std::max<u32>(16, (static_cast<u32>(rb_rows_force) + 15) / 16 * 16));
-    // rows of <= 512 B: an image of exactly 80 KiB would fill a 512-thread workgroup's LDS, whose
-    // last word is the piece-batch counter (160 KiB images are excluded by rowblock_rows)
-    if (rowBytes <= 512 && static_cast<size_t>(RBr) * rowBytes == 80u * 1024u && RBr > 16) RBr -= 16;
-    const u32 nRB = std::max<u32>(1, (Rs + RBr - 1) / RBr);
-    const size_t lds = static_cast<size_t>(RBr) * rowBytes;
-    const u32 NT = lds > 80 * 1024 ? 1024 : 512;
-    // k_sddmm_rb takes 160 KiB (1024 threads) or 80 KiB (512) of LDS per workgroup
-    const u32 wgPerCU = NT == 1024 ? 1 : 2;
-    const u32 perBucket = std::max<u32>(1, static_cast<u32>(cus) * wgPerCU / XCD_BUCKETS);
-    // dense tiles of the range: kept (>= tileMin stored entries) or demoted to entries
-    const u32 T0 = h_blockOffsets[pa], nT = whole ? 0 : h_blockOffsets[pb] - T0;
-    std::vector<u32> tcnt(nT, 0), doff(nT, NULLV), keptPos(nT + 1ull, 0), hkept;
+// Device entry prep of a layout over panels [pa, pb) holding n0 residual entries: the dense tiles
+// kept (>= tileMin stored entries) or demoted to entries, the entries keyed and sorted by (row
+// block, column) and gathered into L.meta / L.out; L.tileIds; the host copies the scheduler reads.
+static int sort_rb_entries(const Plan& p, Plan::RowBlockLayout& L, const RbGeometry& g, u32 pa, u32 pb,
+                           u32 tileMin, u32 n0, SortedEntries& se) {
+    const bool orig = g.orig, cols = g.cols, whole = orig || cols;
+    const u32 RBr = g.RB, nRB = g.nRB, M = p.M, N = p.N, NS = cols ? M : N;
+    hipStream_t s = p.stream;
+    const u32 qa = whole ? 0 : 16 * pa;
+    const u32 ebase = whole ? 0 : p.h_sparseValueOffsets[pa];
+    const u32 T0 = p.h_blockOffsets[pa], nT = whole ? 0 : p.h_blockOffsets[pb] - T0;
+    std::vector<u32> tcnt(nT, 0), doff(nT, NULLV), keptPos(nT + 1ull, 0);
+    std::vector<u32>& hkept = se.hkept;
     u32 nd = 0;
     if (nT && tileMin > 0) {
         DevBuf<u32> dcnt;
         BSMR_CHECK(dcnt.alloc(nT));
-        hipLaunchKernelGGL(k_tile_nnz, dim3(nT), dim3(256), 0, s, blockValues.data(), T0, dcnt.data());
+        hipLaunchKernelGGL(k_tile_nnz, dim3(nT), dim3(256), 0, s, p.blockValues.data(), T0, dcnt.data());
         BSMR_HIP(hipGetLastError());
         BSMR_HIP(hipMemcpyAsync(tcnt.data(), dcnt.data(), nT * sizeof(u32), hipMemcpyDeviceToHost, s));
         BSMR_HIP(hipStreamSynchronize(s));
@@ -1811,7 +1640,10 @@ int Plan::build_rowblock_layout(RowBlockLayout& L, u32 rowBytes, u32 pa, u32 pb,
         BSMR_CHECK(L.tileIds.upload(hkept.data(), hkept.size(), s));
     BSMR_CHECK(L.meta.alloc(std::max<u32>(n, 1)));
     BSMR_CHECK(L.out.alloc(std::max<u32>(n, 1)));
-    std::vector<u32> rbEnd(nRB, 0), hmeta(n);
+    std::vector<u32>& rbEnd = se.rbEnd;
+    std::vector<u32>& hmeta = se.hmeta;
+    rbEnd.assign(nRB, 0);
+    hmeta.resize(n);
     if (n) {
         DevBuf<unsigned long long> keys, skeys;
         DevBuf<u32> vals, order, qOf, dEnd, ddoff, dcol, dout, rowOf;
@@ -1826,31 +1658,31 @@ int Plan::build_rowblock_layout(RowBlockLayout& L, u32 rowBytes, u32 pa, u32 pb,
         BSMR_HIP(hipMemsetAsync(dEnd.data(), 0, nRB * sizeof(u32), s));
         if (cols) {
             BSMR_CHECK(rowOf.alloc(n));
-            hipLaunchKernelGGL(k_rb_keys_cols, dim3(grid_for(M, 256)), dim3(256), 0, s, rowptr.data(),
-                               colidx.data(), M, RBr, keys.data(), vals.data(), qOf.data(), rowOf.data());
+            hipLaunchKernelGGL(k_rb_keys_cols, dim3(grid_for(M, 256)), dim3(256), 0, s, p.rowptr.data(),
+                               p.colidx.data(), M, RBr, keys.data(), vals.data(), qOf.data(), rowOf.data());
         } else if (orig)
-            hipLaunchKernelGGL(k_rb_keys_csr, dim3(grid_for(M, 256)), dim3(256), 0, s, rowptr.data(),
-                               colidx.data(), M, RBr, N, keys.data(), vals.data(), qOf.data());
+            hipLaunchKernelGGL(k_rb_keys_csr, dim3(grid_for(M, 256)), dim3(256), 0, s, p.rowptr.data(),
+                               p.colidx.data(), M, RBr, N, keys.data(), vals.data(), qOf.data());
         else if (pb > pa)
-            hipLaunchKernelGGL(k_rb_keys, dim3(pb - pa), dim3(256), 0, s, sparseValueOffsets.data(),
-                               sparseRel.data(), sparseColIdx.data(), pa, RBr, N, keys.data(),
+            hipLaunchKernelGGL(k_rb_keys, dim3(pb - pa), dim3(256), 0, s, p.sparseValueOffsets.data(),
+                               p.sparseRel.data(), p.sparseColIdx.data(), pa, RBr, N, keys.data(),
                                vals.data(), qOf.data());
         if (nd) {
             BSMR_CHECK(ddoff.upload(doff.data(), nT, s));
-            hipLaunchKernelGGL(k_tile_demote, dim3(nT), dim3(256), 0, s, blockValues.data(),
-                               denseItems.data(), denseCols.data(), T0, ddoff.data(), qa, RBr, N, n0,
+            hipLaunchKernelGGL(k_tile_demote, dim3(nT), dim3(256), 0, s, p.blockValues.data(),
+                               p.denseItems.data(), p.denseCols.data(), T0, ddoff.data(), qa, RBr, N, n0,
                                keys.data(), vals.data(), qOf.data(), dcol.data(), dout.data());
         }
         BSMR_HIP(hipGetLastError());
         BSMR_CHECK(sort_pairs64(keys.data(), skeys.data(), vals.data(), order.data(), n,
-                                bits_for(static_cast<u64>(nRB) * NS), tmp, s));
+                                bits_for(static_cast<u64>(nRB) * NS), p.tmp, s));
         if (whole)  // vals = CSR positions: the output index is the entry itself
             hipLaunchKernelGGL(k_rb_gather_csr, dim3(grid_for(n, 256)), dim3(256), 0, s, order.data(),
-                               qOf.data(), cols ? rowOf.data() : colidx.data(), n, RBr, L.meta.data(),
+                               qOf.data(), cols ? rowOf.data() : p.colidx.data(), n, RBr, L.meta.data(),
                                L.out.data(), dEnd.data());
         else
             hipLaunchKernelGGL(k_rb_gather, dim3(grid_for(n, 256)), dim3(256), 0, s, order.data(),
-                               qOf.data(), sparseColIdx.data() + ebase, sparseValues.data() + ebase,
+                               qOf.data(), p.sparseColIdx.data() + ebase, p.sparseValues.data() + ebase,
                                dcol.data(), dout.data(), n0, n, RBr, L.meta.data(), L.out.data(),
                                dEnd.data());
         BSMR_HIP(hipGetLastError());
@@ -1859,459 +1691,25 @@ int Plan::build_rowblock_layout(RowBlockLayout& L, u32 rowBytes, u32 pa, u32 pb,
         BSMR_HIP(hipStreamSynchronize(s));
         for (u32 b = 1; b < nRB; ++b) rbEnd[b] = std::max(rbEnd[b], rbEnd[b - 1]);
     }
-    lap("sort+meta");
-    // column ranges: NCR = 8 m ranges of (nearly) equal residual count; XCD x owns ranges
-    // [x m, (x + 1) m). m makes one range's B columns (N rowBytes / NCR) fit an L2 budget: the
-    // items of an XCD are ordered by range, so the B columns an item gathers were brought into
-    // that XCD's L2 by the items before it (graph matrices: B is gathered once per row block and
-    // column run, from L2 instead of the Infinity Cache)
-    constexpr u32 CM = (1u << 22) - 1;
-    const u32 rangeKb = l2Kb;
-    const u32 m = std::max<u32>(1, static_cast<u32>(std::ceil(
-        static_cast<double>(NS) * rowBytes / XCD_BUCKETS / (static_cast<double>(rangeKb) * 1024.0))));
-    const u32 NCR = XCD_BUCKETS * m;
-    std::vector<u32> cuts(NCR + 1, NS);
-    cuts[0] = 0;
-    {
-        // column weight: its entries, plus (item_sched) piece_weight per column-run piece it
-        // heads, so the XCDs' ranges carry equal modeled cost rather than equal entry counts
-        // (mycielskian: the last XCD's range carried 10 % more piece work and ended 10 % later)
-        // (integer counts per column — entries, and column-run starts = ceil(run / piece_max) per
-        // row block — then cnt = entries + piece_weight x starts: exact whatever the host's thread
-        // count, so every rank of a multi-GPU run derives the same layout. Each host thread takes a
-        // stripe of columns and finds its part of every row block's column-sorted entries by
-        // binary search: N + 1 counters in all, not one vector per row-block chunk)
-        std::vector<u32> ecount(NS + 1, 0), scount(NS + 1, 0);
-        const u32 NSTR = 64;
-        par_for(NSTR, [&](unsigned, size_t s0, size_t s1) {
-            for (size_t st = s0; st < s1; ++st) {
-                const u32 c0 = static_cast<u32>(static_cast<u64>(NS) * st / NSTR);
-                const u32 c1 = static_cast<u32>(static_cast<u64>(NS) * (st + 1) / NSTR);
-                if (c0 == c1) continue;
-                for (u32 b = 0; b < nRB; ++b) {
-                    const u32* lo = hmeta.data() + (b ? rbEnd[b - 1] : 0u);
-                    const u32* hi = hmeta.data() + rbEnd[b];
-                    const auto byCol = [](u32 m, u32 c) { return (m & CM) < c; };
-                    const u32* p = std::lower_bound(lo, hi, c0, byCol);
-                    const u32* q = std::lower_bound(p, hi, c1, byCol);
-                    for (const u32* i = p; i < q;) {
-                        const u32 c = *i & CM;
-                        const u32* j = i + 1;
-                        while (j < q && (*j & CM) == c) ++j;
-                        const u32 n = static_cast<u32>(j - i);
-                        ecount[c] += n;
-                        scount[c] += (n + piece_max - 1) / piece_max;
-                        i = j;
-                    }
-                }
-            }
-        }, 1);
-        std::vector<double> cnt(NS + 1, 0.0);
-        for (u32 c = 0; c < NS; ++c)
-            cnt[c] = static_cast<double>(ecount[c]) + (item_cost_cuts ? piece_weight * scount[c] : 0.0);
-        double tot = 0;
-        for (u32 c = 0; c < NS; ++c) tot += cnt[c];
-        double run = 0;
-        u32 x = 1;
-        for (u32 c = 0; c < NS && x < NCR; ++c) {
-            while (x < NCR && run >= tot * x / NCR) cuts[x++] = c;
-            run += cnt[c];
-        }
-        for (; x < NCR; ++x) cuts[x] = NS;
+    // kept tiles of row block b: positions [keptBegin[b], keptBegin[b + 1]) of the kept list
+    if (!whole) {
+        se.keptBegin.resize(nRB + 1ull);
+        for (u32 b = 0; b <= nRB; ++b)
+            se.keptBegin[b] = keptPos[p.h_blockOffsets[std::min(pa + b * (RBr / 16), pb)] - T0];
     }
-    lap("cuts");
-    // segments (rb, range k): entries of rb in range k + 1/NCR of rb's tiles; cost = entries +
-    // column-run pieces (one B column each) + 16 per tile
-    const size_t nseg = static_cast<size_t>(nRB) * NCR;
-    std::vector<u32> se0(nseg), se1(nseg), st0(nseg), st1(nseg), spc(nseg, 0);
-    std::vector<double> cost(nseg);
-    std::vector<u64> piecesRB(nRB, 0);
-    par_for(nRB, [&](unsigned, size_t bb0, size_t bb1) {
-    for (u32 b = static_cast<u32>(bb0); b < bb1; ++b) {
-        const u32 eb0 = b ? rbEnd[b - 1] : 0, eb1 = rbEnd[b];
-        const u32 p0 = std::min(pa + b * (RBr / 16), pb), p1 = std::min(pa + (b + 1) * (RBr / 16), pb);
-        // kept tiles of the row block: positions [t0, t0 + nt) of the kept list
-        const u32 t0 = whole ? 0 : keptPos[h_blockOffsets[p0] - T0];
-        const u32 nt = whole ? 0 : keptPos[h_blockOffsets[p1] - T0] - t0;
-        u32 lo = eb0;
-        for (u32 k = 0; k < NCR; ++k) {
-            const size_t i = static_cast<size_t>(b) * NCR + k;
-            const u32 hi = k + 1 < NCR
-                               ? static_cast<u32>(std::lower_bound(hmeta.begin() + lo, hmeta.begin() + eb1,
-                                                                   cuts[k + 1],
-                                                                   [](u32 v, u32 c) { return (v & CM) < c; }) -
-                                                  hmeta.begin())
-                               : eb1;
-            se0[i] = lo;
-            se1[i] = hi;
-            for (u32 e = lo; e < hi;) {  // column runs cut every piece_max entries
-                const u32 col = hmeta[e] & CM;
-                u32 f = e + 1;
-                while (f < hi && f - e < piece_max && (hmeta[f] & CM) == col) ++f;
-                ++spc[i];
-                e = f;
-            }
-            piecesRB[b] += spc[i];
-            lo = hi;
-            st0[i] = t0 + static_cast<u32>(static_cast<u64>(nt) * k / NCR);
-            st1[i] = t0 + static_cast<u32>(static_cast<u64>(nt) * (k + 1) / NCR);
-            cost[i] = (se1[i] - se0[i]) + piece_weight * spc[i] + 16.0 * (st1[i] - st0[i]);
-        }
-    }
-    }, 16);
-    lap("segments");
-    // chunks. A row block is split by the column ranges (its items then read B from their own
-    // XCD's L2) when it is big enough for >= 8 items of a one-round launch, or (m > 1) when its
-    // column runs would gather more B rows than NCR restagings of its A rows cost; a smaller one
-    // (e.g. banded matrices: many row blocks of few entries) is cut along its whole column-sorted
-    // entry list, and its items balance the XCD list lengths. Item counts come from
-    // largest-remainder apportionment; Q is one round of workgroup slots (fewer if items would
-    // drop below ~128 cost units), or whole rounds when the split segments need more items.
-    std::vector<std::vector<uint4>> lists(XCD_BUCKETS);
-    std::vector<std::vector<u32>> lends(XCD_BUCKETS);
-    double total = 0;
-    for (double c : cost) total += c;
-    const u32 Q1 = perBucket * XCD_BUCKETS;
-    u32 Q = std::max<u32>(1, std::min<u32>(Q1, static_cast<u32>(total / 128.0)));
-    const double target = total / Q;
-    // no chunk above item_cap x one slot's share of a round (0: off): a row block of one hub row
-    // (mycielskian: 8 K single-entry pieces in one item against a 6 K-entry median) otherwise
-    // outlasts the whole launch (profiles/r03e/itemcal). 1x would force extra items into a
-    // second round wherever a segment sits just above the mean (C2: 11 -> 17 us)
-    const double cap = (item_cap < 0 ? 2.0 : item_cap) * total / Q1;
-    std::vector<double> cb(nRB, 0.0);
-    std::vector<char> split(nRB, 0);
-    double splitTotal = 0;
-    std::vector<u32> segX(XCD_BUCKETS, 0);  // non-empty split segments per XCD
-    // column blocks whose whole gathered operand (A) fits half an XCD's L2 (C2: 768 KiB): no
-    // block is split by range, so each block's items run on one XCD (contiguous eighths) and its
-    // B image comes into that L2 once — split by range, every XCD would pull every block's image
-    // from the Infinity Cache (8 x B per launch) to save gathers of an A that is L2-resident anyway
-    const bool colsLocal = cols && static_cast<u64>(NS) * rowBytes <= (2ull << 20) && !(diag & 4096);
-    for (u32 b = 0; b < nRB; ++b) {
-        for (u32 k = 0; k < NCR; ++k) cb[b] += cost[static_cast<size_t>(b) * NCR + k];
-        split[b] = !colsLocal && (cb[b] >= XCD_BUCKETS * target ||
-                                  (m > 1 && piecesRB[b] >= static_cast<u64>(NCR) * RBr));
-        if (!split[b]) continue;
-        splitTotal += cb[b];
-        for (u32 k = 0; k < NCR; ++k)
-            segX[k / m] += cost[static_cast<size_t>(b) * NCR + k] > 0;
-    }
-    // the same quota for every XCD (the column cuts balance them): an extra item in one list
-    // would start another round of slots on that XCD
-    const u32 segMax = *std::max_element(segX.begin(), segX.end());
-    if (segMax * XCD_BUCKETS > Q) Q = (segMax * XCD_BUCKETS + Q1 - 1) / Q1 * Q1;
-    const u32 qEach = std::max<u32>(segMax, static_cast<u32>(std::llround(
-        static_cast<double>(Q / XCD_BUCKETS) * (total > 0 ? splitTotal / total : 0.0))));
-    const u32 qSplit = qEach * XCD_BUCKETS;
-    std::vector<double> cu(nRB, 0.0);
-    for (u32 b = 0; b < nRB; ++b) cu[b] = split[b] ? 0.0 : cb[b];
-    std::vector<u32> nu;
-    // staged output: the LDS past the A image (the launch takes 160 / 80 KiB) holds an item's
-    // results when it has room for >= 1024 of them; larger items are cut to fit
-    const size_t ldsDyn = (NT == 1024 ? 160u : 80u) * 1024u;
-    // (the last 16 bytes: the piece-batch counter)
-    const u32 outCap = ldsDyn > lds + 16 ? static_cast<u32>((ldsDyn - lds - 16) / 4) : 0u;
-    const bool staged = stagedWanted && outCap >= 1024;
-    // chunk k of an entry range: cut where the running cost (1 per entry + piece_weight per
-    // column-run piece start) crosses k / nch of the range's cost, so chunks of single-entry
-    // pieces get fewer entries than chunks of long runs; a chunk above the staged-output
-    // capacity is then cut entry-evenly into as many as it needs (an entry-even cut of the whole
-    // range would put a hub row's single-entry run into one chunk of 5x the others' cost)
-    std::vector<u32> ecut, ecut2;
-    // tot = the range's entries + piece_weight per piece (known from its segments' costs), so
-    // one pass finds the cuts; ccost = the chunks' costs (entries + pieces) for the slot model
-    std::vector<double> ccost, ccost2;
-    auto cuts_by_cost = [&](u32 e0, u32 ne, u32 nch, double tot) {
-        ecut.assign(nch + 1, e0 + ne);
-        ecut[0] = e0;
-        ccost.assign(nch, nch ? tot / nch : 0.0);
-        if (nch > 1 && !item_cost_cuts) {
-            for (u32 k = 1; k < nch; ++k) ecut[k] = e0 + static_cast<u32>(static_cast<u64>(ne) * k / nch);
-        } else if (nch > 1) {
-            double acc = 0, last = 0;
-            u32 k = 1, run = 0;
-            for (u32 e = e0; e < e0 + ne && k < nch; ++e) {
-                const bool start = e == e0 || (hmeta[e] & CM) != (hmeta[e - 1] & CM) || run >= piece_max;
-                run = start ? 1 : run + 1;
-                while (k < nch && acc >= tot * k / nch) {
-                    ecut[k] = e;
-                    ccost[k - 1] = acc - last;
-                    last = acc;
-                    ++k;
-                }
-                acc += 1.0 + (start ? piece_weight : 0.0);
-            }
-            // the chunk from the last cut runs to the range's end; cuts never reached (k < nch)
-            // leave empty chunks behind it
-            for (u32 j = k; j < nch; ++j) ccost[j] = 0.0;
-            ccost[k - 1] = std::max(0.0, tot - last);
-        }
-        if (!staged) return;
-        ecut2.assign(1, e0);
-        ccost2.clear();
-        for (u32 j = 0; j < nch; ++j) {
-            const u32 a = ecut[j], len = ecut[j + 1] - a, parts = std::max<u32>(1, (len + outCap - 1) / outCap);
-            for (u32 q = 1; q <= parts; ++q) {
-                ecut2.push_back(a + static_cast<u32>(static_cast<u64>(len) * q / parts));
-                ccost2.push_back(ccost[j] / parts);
-            }
-        }
-        ecut.swap(ecut2);
-        ccost.swap(ccost2);
-    };
-    // lcost: each item's modeled cost (its entries + pieces + 16 per kept tile + staging
-    // (piece_weight per row) + item_fixed), for the slot model
-    std::vector<std::vector<double>> lcost(XCD_BUCKETS);
-    auto emit = [&](u32 xl, u32 b, u32 e0, u32 ne, u32 t0, u32 nt, u32 nch, double rcost) {
-        if (staged) nch = std::max<u32>(nch, (ne + outCap - 1) / outCap);
-        cuts_by_cost(e0, ne, nch, rcost);
-        nch = static_cast<u32>(ecut.size() - 1);
-        for (u32 k = 0; k < nch; ++k) {
-            const u32 ea = ecut[k];
-            const u32 eb = ecut[k + 1];
-            const u32 ta = t0 + static_cast<u32>(static_cast<u64>(nt) * k / nch);
-            const u32 tb = t0 + static_cast<u32>(static_cast<u64>(nt) * (k + 1) / nch);
-            if (ea == eb && ta == tb) continue;
-            lists[xl].push_back(make_uint4(b, ta, tb, ea));
-            lends[xl].push_back(eb);
-            lcost[xl].push_back(ccost[k] + 16.0 * (tb - ta) + piece_weight * RBr + item_fixed);
-        }
-    };
-    using Slot = std::priority_queue<double, std::vector<double>, std::greater<double>>;
-    // the XCD lists for one cost cap (0: none); returns the modeled makespan: each XCD runs its
-    // list on perBucket slots, an item starting when a slot frees (in list order)
-    auto build_lists = [&](const double capv) -> double {
-    lists.assign(XCD_BUCKETS, {});
-    lends.assign(XCD_BUCKETS, {});
-    lcost.assign(XCD_BUCKETS, {});
-    nu = apportion(cu, Q > qSplit ? Q - qSplit : 0u, capv);
-    for (u32 x = 0; x < XCD_BUCKETS; ++x) {
-        // XCD x's segments in (range, row block) order
-        std::vector<double> c(static_cast<size_t>(m) * nRB, 0.0);
-        for (u32 j = 0; j < m; ++j)
-            for (u32 b = 0; b < nRB; ++b)
-                c[static_cast<size_t>(j) * nRB + b] =
-                    split[b] ? cost[static_cast<size_t>(b) * NCR + x * m + j] : 0.0;
-        const std::vector<u32> nch = apportion(c, qEach, capv);
-        for (u32 j = 0; j < m; ++j)
-            for (u32 b = 0; b < nRB; ++b) {
-                const size_t i = static_cast<size_t>(b) * NCR + x * m + j;
-                const u32 q = nch[static_cast<size_t>(j) * nRB + b];
-                if (q)
-                    emit(x, b, se0[i], se1[i] - se0[i], st0[i], st1[i] - st0[i], q,
-                         (se1[i] - se0[i]) + piece_weight * spc[i]);
-            }
-    }
-    // unsplit row blocks: their items, in row-block order, go to the list with the fewest items,
-    // so no XCD runs an extra round (a contiguous range of blocks per XCD, for L2 sharing of
-    // banded columns, measured 7 % slower on the cop20k-like C3 pattern)
-    const u32 spare = XCD_BUCKETS;  // staging list index
-    lists.resize(XCD_BUCKETS + 1);
-    lends.resize(XCD_BUCKETS + 1);
-    lcost.resize(XCD_BUCKETS + 1);
-    for (u32 b = 0; b < nRB; ++b) {
-        if (!nu[b]) continue;
-        const size_t i0 = static_cast<size_t>(b) * NCR, i1 = i0 + NCR - 1;
-        double rc = 0.0;
-        for (size_t i = i0; i <= i1; ++i) rc += (se1[i] - se0[i]) + piece_weight * spc[i];
-        emit(spare, b, se0[i0], se1[i1] - se0[i0], st0[i0], st1[i1] - st0[i0], nu[b], rc);
-    }
-    {
-        const size_t nsp = lists[spare].size();
-        const bool contig = whole && orig_contig && qSplit == 0;
-        if (item_lpt && !contig && nsp) {
-            // list scheduling: each XCD runs its list on perBucket slots, an item starting when a
-            // slot frees (in list order). The XCD lists' split items are simulated first; then
-            // the unsplit items, heaviest first, each go to the XCD where it starts earliest
-            // (ties: fewer items, lower index), appended to that list, which keeps every list in
-            // descending order of its unsplit items' cost
-            std::vector<Slot> free(XCD_BUCKETS);
-            for (u32 x = 0; x < XCD_BUCKETS; ++x) {
-                for (u32 k = 0; k < perBucket; ++k) free[x].push(0.0);
-                for (size_t j = 0; j < lists[x].size(); ++j) {
-                    const double t = free[x].top();
-                    free[x].pop();
-                    free[x].push(t + lcost[x][j]);
-                }
-            }
-            std::vector<std::pair<double, size_t>> ord(nsp);
-            for (size_t i = 0; i < nsp; ++i) ord[i] = {lcost[spare][i], i};
-            std::stable_sort(ord.begin(), ord.end(),
-                             [](const auto& a, const auto& b) { return a.first > b.first; });
-            for (const auto& [c, i] : ord) {
-                u32 x = 0;
-                for (u32 y = 1; y < XCD_BUCKETS; ++y) {
-                    const double ty = free[y].top(), tx = free[x].top();
-                    if (ty < tx || (ty == tx && lists[y].size() < lists[x].size())) x = y;
-                }
-                const double t = free[x].top();
-                free[x].pop();
-                free[x].push(t + c);
-                lists[x].push_back(lists[spare][i]);
-                lends[x].push_back(lends[spare][i]);
-                lcost[x].push_back(c);
-            }
-        } else {
-            for (size_t next = 0; next < nsp; ++next) {
-                u32 x = 0;  // the list with the fewest items (ties: lowest index)
-                for (u32 y = 1; y < XCD_BUCKETS; ++y)
-                    if (lists[y].size() < lists[x].size()) x = y;
-                // original-order blocks (orig_contig): XCD x takes the x-th contiguous eighth, so
-                // the band's B rows of neighbouring blocks stay in one L2
-                if (contig) x = static_cast<u32>(next * XCD_BUCKETS / nsp);
-                lists[x].push_back(lists[spare][next]);
-                lends[x].push_back(lends[spare][next]);
-                lcost[x].push_back(lcost[spare][next]);
-            }
-        }
-        lists.resize(XCD_BUCKETS);
-        lends.resize(XCD_BUCKETS);
-        lcost.resize(XCD_BUCKETS);
-    }
-    double ms = 0.0;
-    for (u32 x = 0; x < XCD_BUCKETS; ++x) {
-        Slot fr;
-        for (u32 k = 0; k < perBucket; ++k) fr.push(0.0);
-        double end = 0.0;
-        for (size_t j = 0; j < lists[x].size(); ++j) {
-            const double t = fr.top() + lcost[x][j];
-            fr.pop();
-            fr.push(t);
-            end = std::max(end, t);
-        }
-        ms = std::max(ms, end);
-    }
-    return ms;
-    };
-    // the cap: item_cap x one slot's share, or (auto, item_sched, up to 32 M entries) the
-    // multiple in {2, 1.5, 1.25, 1} whose lists the slot model runs fastest (a one-round launch
-    // ends with its longest item: mycielskian15 K = 256, 2x cap 144 us; C2's segments sit just
-    // above the mean, where 1x would open a second round)
-    double capUse = cap;
-    if (item_lpt && item_cap < 0 && n <= (1u << 25)) {
-        double best = -1.0;
-        for (const double f : {2.0, 1.5, 1.25, 1.0}) {
-            const double msf = build_lists(f * total / Q1);
-            if (best < 0 || msf < 0.995 * best) {
-                best = msf;
-                capUse = f * total / Q1;
-            }
-        }
-    }
-    const double msUse = build_lists(capUse);
-    if (diag & 1024) {  // layout debug (host stderr)
-        std::fprintf(stderr, "[rb layout] RB %u NT %u nRB %u m %u Q1 %u Q %u total %.0f target %.0f cap %.0f (used %.0f, model makespan %.0f) "
-                     "splitTotal %.0f qEach %u segMax %u\n", RBr, NT, nRB, m, Q1, Q, total, target, cap, capUse, msUse,
-                     splitTotal, qEach, segMax);
-        for (u32 b = 0; b < nRB; ++b)
-            if (cb[b] > 2 * target)
-                std::fprintf(stderr, "[rb layout]   block %u cost %.0f split %d nu %u\n", b, cb[b], split[b], nu[b]);
-    }
-    lap("chunks");
-    std::vector<uint4> items;
-    std::vector<u32> ends;
-    size_t nmax = 0;
-    for (const auto& l : lists) nmax = std::max(nmax, l.size());
-    // staged layouts: an even number of list positions, so the launch can pair them (k_sddmm_rb)
-    if (staged) nmax = (nmax + 1) & ~static_cast<size_t>(1);
-    items.assign(nmax * XCD_BUCKETS, make_uint4(0, 0, 0, 0));
-    ends.assign(nmax * XCD_BUCKETS, 0);
-    for (u32 x = 0; x < XCD_BUCKETS; ++x)
-        for (size_t j = 0; j < lists[x].size(); ++j) {
-            items[j * XCD_BUCKETS + x] = lists[x][j];
-            ends[j * XCD_BUCKETS + x] = lends[x][j];
-        }
-    lap("items");
-    // column-run pieces: each item's entries [e0, e1) cut at column changes and every
-    // piece_max (<= RB_PIECE_MAX) entries; piece {first entry, column | (length - 1) << 22}. A workgroup's NG
-    // row-groups take one piece each per phase, so phase ph runs the item's pieces
-    // [ph NG, (ph + 1) NG). Longest first over the whole item, so the 16 row-groups of a wave get
-    // pieces of similar length
-    std::vector<uint2> ient(items.size());
-    for (size_t i = 0; i < items.size(); ++i)
-        ient[i] = make_uint2(items[i].w, (items[i].y == items[i].z && items[i].w == ends[i]) ? 0u
-                                                                                          : ends[i] - items[i].w);
-    // (per item on the host threads, then placed in item order)
-    std::vector<std::vector<uint2>> ipc(items.size());
-    par_for(items.size(), [&](unsigned, size_t i0, size_t i1) {
-        for (size_t i = i0; i < i1; ++i) {
-            std::vector<uint2>& mine = ipc[i];
-            const u32 ea = items[i].w, eb = ends[i];
-            for (u32 e = ea; e < eb;) {
-                const u32 col = hmeta[e] & CM;
-                u32 f = e + 1;
-                while (f < eb && f - e < piece_max && (hmeta[f] & CM) == col) ++f;
-                mine.push_back(make_uint2(e, col | ((f - e - 1) << 22)));
-                e = f;
-            }
-            std::stable_sort(mine.begin(), mine.end(),
-                             [](const uint2& a, const uint2& b) { return (a.y >> 22) > (b.y >> 22); });
-        }
-    });
-    // dynamic piece batches (Plan::batches; kernels for rows of <= 512 B): after its first batch
-    // of 64 / G pieces a wave takes the next from an LDS counter, which balances the waves of
-    // items with several pieces per row-group. Measured (profiles/r05bt, forced on against off):
-    // 512-byte rows with 2.4 / 6.5 / 6.8 pieces per row-group (mycielskian14 K = 128, C3, C4
-    // x0.5) -4.5 / -2.4 / -2.2 %, C2's 1.4 +5 %; 128- and 256-byte rows (mycielskian15 K = 32,
-    // Trefethen K = 64: little work per entry behind each counter round trip) +2 to +8 %. Auto:
-    // 512-byte rows from batch_min_phases pieces per row-group
-    bool dyn = false;
-    {
-        u64 npAll = 0;
-        u32 nWork = 0;
-        for (size_t i = 0; i < items.size(); ++i) {
-            npAll += ipc[i].size();
-            nWork += !(items[i].y == items[i].z && items[i].w == ends[i]);
-        }
-        const u32 NGl = NT / 4;  // row-groups (G = 4 for rows of <= 512 B)
-        const double perItem = nWork ? static_cast<double>(npAll) / nWork : 0.0;
-        dyn = rowBytes <= 512 &&
-              (batches == 1 || (batches < 0 && rowBytes == 512 && perItem >= batch_min_phases * NGl));
-    }
-    // static phases (no batches): the item's pieces placed so that its waves end together
-    // (balance_pieces; items with kept MFMA tiles keep the longest-first order, whose shortest
-    // pieces sit with the tile waves)
-    if (!dyn && piece_balance == 1) {
-        const u32 G = rowBytes >= 2048 ? 16 : rowBytes >= 1024 ? 8 : 4;  // sddmm.hip RowGeom
-        par_for(items.size(), [&](unsigned, size_t i0, size_t i1) {
-            for (size_t i = i0; i < i1; ++i)
-                if (items[i].y == items[i].z) balance_pieces(ipc[i], NT, G, piece_weight);
-        });
-    }
-    std::vector<size_t> poff(items.size() + 1, 0);
-    for (size_t i = 0; i < items.size(); ++i) poff[i + 1] = poff[i] + ipc[i].size();
-    std::vector<uint2> pieces(poff.back());
-    L.itemStat.assign(items.size(), make_uint4(0, 0, 0, 0));
-    std::vector<u64> ientc(items.size(), 0);
-    std::vector<char> ipad(items.size(), 0);
-    par_for(items.size(), [&](unsigned, size_t i0, size_t i1) {
-        for (size_t i = i0; i < i1; ++i) {
-            const bool pad = items[i].y == items[i].z && items[i].w == ends[i];
-            std::copy(ipc[i].begin(), ipc[i].end(), pieces.begin() + poff[i]);
-            std::vector<uint2>().swap(ipc[i]);
-            items[i].w = static_cast<u32>(poff[i]);
-            ends[i] = static_cast<u32>(poff[i + 1]);
-            ipad[i] = pad;
-            if (pad) continue;
-            u64 ent = 0;
-            for (u32 k = items[i].w; k < ends[i]; ++k) ent += (pieces[k].y >> 22) + 1;
-            ientc[i] = ent;
-            L.itemStat[i] = make_uint4(items[i].x, items[i].z - items[i].y, static_cast<u32>(ent),
-                                       ends[i] - items[i].w);
-        }
-    });
-    L.rbCost.assign(nRB, 0.0);
-    L.nWorkItems = 0;
-    for (size_t i = 0; i < items.size(); ++i) {
-        const uint4 it = items[i];
-        if (ipad[i]) continue;  // padding
-        ++L.nWorkItems;
-        L.rbCost[it.x] += static_cast<double>(ientc[i]) + shard_piece_weight * (ends[i] - it.w) +
-                          16.0 * (it.z - it.y) + RBr;
-    }
-    L.nItems = static_cast<u32>(items.size());
-    L.nPieces = static_cast<u32>(pieces.size());
+    se.n = n;
+    se.nd = nd;
+    return BSMR_OK;
+}
+
+// Staged / packed output tables of a scheduled layout of n entries (ient: per item {first entry,
+// entries}): staged output sorts each item's entries by CSR position on the device (slots) and
+// cuts them into runs; unstaged layouts of small plans pack the position into the metadata.
+static int build_output_tables(const Plan& p, Plan::RowBlockLayout& L, const RbGeometry& g, u32 n,
+                               const std::vector<uint2>& ient) {
+    hipStream_t s = p.stream;
+    const u32 nnz = p.nnz, diag = p.diag, NT = g.NT, outCap = g.outCap;
+    DevBuf<uint8_t>& tmp = p.tmp;
     L.outLds = 0;
     L.outCap = 0;
     L.outPacked = false;
@@ -2320,8 +1718,7 @@ int Plan::build_rowblock_layout(RowBlockLayout& L, u32 rowBytes, u32 pa, u32 pb,
     L.itemEnt.release();
     L.runs.release();
     L.itemRuns.release();
-    lap("pieces");
-    if (staged && n) {
+    if (g.staged && n) {
         // slots: per item, its entries sorted by CSR position (segmented radix sort on the device)
         BSMR_CHECK(L.itemEnt.upload(ient.data(), ient.size(), s));
         std::vector<u32> segb(ient.size()), sege(ient.size());
@@ -2359,7 +1756,7 @@ int Plan::build_rowblock_layout(RowBlockLayout& L, u32 rowBytes, u32 pa, u32 pb,
         BSMR_HIP(hipGetLastError());
         BSMR_HIP(hipStreamSynchronize(s));
         L.out.release();
-        L.outLds = static_cast<u32>(lds);
+        L.outLds = static_cast<u32>(g.lds);
         L.outCap = outCap;
         // run table (BSMR_DIAG & 8192: keep the per-result positions): up to 64 consecutive CSR
         // positions of an item's sorted slots form one run; used when no item has more runs
@@ -2413,7 +1810,7 @@ int Plan::build_rowblock_layout(RowBlockLayout& L, u32 rowBytes, u32 pa, u32 pb,
                 L.outRuns = true;
             }
         }
-    } else if (n && out_packed != 0 && nnz <= (1u << 22)) {
+    } else if (n && p.out_packed != 0 && nnz <= (1u << 22)) {
         hipLaunchKernelGGL(k_pack_out, dim3((n + 255) / 256), dim3(256), 0, s, L.meta.data(),
                            L.out.data(), n);
         BSMR_HIP(hipGetLastError());
@@ -2421,16 +1818,86 @@ int Plan::build_rowblock_layout(RowBlockLayout& L, u32 rowBytes, u32 pa, u32 pb,
         L.out.release();
         L.outPacked = true;
     }
+    return BSMR_OK;
+}
+
+// Row-block launch layout over panels [pa, pb) (the whole plan, or one row-panel shard):
+// geometry -> device entry sort -> host scheduling -> output tables -> upload.
+int Plan::build_rowblock_layout(RowBlockLayout& L, u32 rowBytes, u32 pa, u32 pb, u32 tileMin,
+                                bool orig, bool cols) const {
+    L.rowBytes = 0;
+    L.orig = orig && !cols;
+    L.cols = cols;
+    orig = orig && !cols;
+    // whole: original-order blocks of rows (orig) or of columns (cols), every entry residual
+    const bool whole = orig || cols;
+    // the gathered index space: columns of S, or (column blocks) its rows
+    const u32 NS = cols ? M : N;
+    hipStream_t s = stream;
+    if (NS > (1u << 22)) {
+        set_error(cols ? "column-block layout needs M <= 2^22" : "row-block layout needs N <= 2^22");
+        return BSMR_ERR_UNSUPPORTED;
+    }
+    if (whole && (pa != 0 || pb != P)) {
+        set_error("original-order row / column blocks cover the whole plan only");
+        return BSMR_ERR_INVALID;
+    }
+    // BSMR_DIAG & 524288: section times of this build to stderr (host-side layout cost)
+    auto lap_t = std::chrono::steady_clock::now();
+    auto lap = [&](const char* what) {
+        if (!(diag & 524288)) return;
+        const auto t = std::chrono::steady_clock::now();
+        std::fprintf(stderr, "[rb layout %u B] %-12s %8.1f ms\n", rowBytes, what,
+                     std::chrono::duration<double, std::milli>(t - lap_t).count());
+        lap_t = t;
+    };
+    const u32 qa = whole ? 0 : 16 * pa, qend = orig ? M : cols ? N : std::min(R, 16 * pb);
+    const u32 Rs = qend > qa ? qend - qa : 0;  // (reordered) rows of the range
+    int cus = 256;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus <= 0)
+        cus = 256;
+    // residual entries of the range (original order: every stored entry)
+    const u32 n0 = whole ? nnz : h_sparseValueOffsets[pb] - h_sparseValueOffsets[pa];
+    const RbKnobs knobs = rb_knobs(*this);
+    const RbGeometry g = rb_geometry(rowBytes, Rs, n0, NS, nnz, cus, orig, cols, knobs);
+
+    SortedEntries se;
+    BSMR_CHECK(sort_rb_entries(*this, L, g, pa, pb, tileMin, n0, se));
+    lap("sort+meta");
+
+    RbScheduleIn in;
+    in.entries = se.hmeta.data();
+    in.n = se.n;
+    in.rbEnd = se.rbEnd.data();
+    in.keptBegin = se.keptBegin.empty() ? nullptr : se.keptBegin.data();
+    in.NS = NS;
+    in.geom = g;
+    in.knobs = knobs;
+    in.lap = lap;  // cuts, segments, chunks, items, pieces
+    RbScheduleOut sch;
+    rb_schedule(in, sch);
+    L.itemStat.resize(sch.itemStat.size());
+    for (size_t i = 0; i < sch.itemStat.size(); ++i)
+        L.itemStat[i] = make_uint4(sch.itemStat[i].x, sch.itemStat[i].y, sch.itemStat[i].z, sch.itemStat[i].w);
+    L.rbCost = std::move(sch.rbCost);
+    L.nWorkItems = sch.nWorkItems;
+    L.nItems = static_cast<u32>(sch.items.size());
+    L.nPieces = static_cast<u32>(sch.pieces.size());
+
+    std::vector<uint2> ient(sch.ient.size());
+    for (size_t i = 0; i < ient.size(); ++i) ient[i] = make_uint2(sch.ient[i].x, sch.ient[i].y);
+    BSMR_CHECK(build_output_tables(*this, L, g, se.n, ient));
     lap("staged");
-    L.dynBatches = dyn;  // (decided with the piece order above)
-    BSMR_CHECK(L.items.upload(items.data(), std::max<size_t>(items.size(), 1), s));
-    BSMR_CHECK(L.itemEnd.upload(ends.data(), std::max<size_t>(ends.size(), 1), s));
-    BSMR_CHECK(L.pieces.upload(pieces.data(), std::max<size_t>(pieces.size(), 1), s));
+
+    L.dynBatches = sch.dyn;  // (decided with the piece order)
+    BSMR_CHECK(L.items.upload(reinterpret_cast<const uint4*>(sch.items.data()), std::max<size_t>(sch.items.size(), 1), s));
+    BSMR_CHECK(L.itemEnd.upload(sch.ends.data(), std::max<size_t>(sch.ends.size(), 1), s));
+    BSMR_CHECK(L.pieces.upload(reinterpret_cast<const uint2*>(sch.pieces.data()), std::max<size_t>(sch.pieces.size(), 1), s));
     BSMR_HIP(hipStreamSynchronize(s));
-    L.RB = RBr;
-    L.NT = NT;
-    L.lds = lds;
-    L.nRB = nRB;
+    L.RB = g.RB;
+    L.NT = g.NT;
+    L.lds = g.lds;
+    L.nRB = g.nRB;
     L.pa = pa;
     L.pb = pb;
     L.rowEnd = qend;
@@ -2442,9 +1909,9 @@ int Plan::build_rowblock_layout(RowBlockLayout& L, u32 rowBytes, u32 pa, u32 pb,
     }
     lap("upload");
     L.tileMin = tileMin;
-    L.nTilesKept = static_cast<u32>(hkept.size());
-    L.nDemoted = nd;
-    L.nEntries = n;
+    L.nTilesKept = static_cast<u32>(se.hkept.size());
+    L.nDemoted = se.nd;
+    L.nEntries = se.n;
     L.rowBytes = rowBytes;
     return BSMR_OK;
 }

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "rb_schedule.hpp"
 
 namespace bsmr {
 
@@ -118,7 +119,7 @@ struct Plan {
     // row-group on average
     int batches = -1;
     double batch_min_phases = 2.0;
-    // static piece order of row-block items without dynamic batches (plan.hip balance_pieces;
+    // static piece order of row-block items without dynamic batches (rb_schedule.cpp balance_pieces;
     // bsmr_tuning.piece_balance): 1 = runs dealt to the least-loaded wave, 0 = longest first in
     // position order
     int piece_balance = 0;
@@ -315,6 +316,8 @@ struct Plan {
     }
 };
 
+// the row-block layout tuning of a plan, as the host-only scheduler takes it (plan.hip)
+RbKnobs rb_knobs(const Plan& p);
 // the whole plan's row-block layout for (K, dtype) (sddmm.hip); *out = null for column-major
 int whole_rb_layout(const Plan& p, u32 K, int dtype, const Plan::RowBlockLayout** out,
                     bool reordered = false);

@@ -1,0 +1,118 @@
+// rb_schedule.hpp — the host-only part of the row-block launch layout: block geometry
+// (rb_geometry) and item scheduling (rb_schedule). Standard library only: no HIP, no device, so it
+// builds, runs and is tested on a machine without a GPU. plan.hip (Plan::build_rowblock_layout)
+// sorts the entries on the device, calls these two, and uploads what they return.
+#pragma once
+
+#include <algorithm>
+#include <cstddef>
+#include <cstdint>
+#include <functional>
+#include <thread>
+#include <vector>
+
+namespace bsmr {
+
+constexpr uint32_t RB_XCDS = 8;                    // XCD_BUCKETS (plan.hpp)
+constexpr uint32_t RB_COL_MASK = (1u << 22) - 1;   // the column of a sorted entry word
+
+// an item {row block, kept-tile begin, kept-tile end, piece begin}: layout-compatible with uint4
+struct alignas(16) RbItem {
+    uint32_t x, y, z, w;
+};
+// a piece {first entry, column | (length - 1) << 22}, or an item's {first entry, entries}:
+// layout-compatible with uint2
+struct alignas(8) RbPiece {
+    uint32_t x, y;
+};
+
+// the tuning a layout depends on: the only place this unit learns about Plan's knobs
+// (plan.hip rb_knobs(const Plan&)); the fields are documented at Plan's members of the same name
+struct RbKnobs {
+    uint32_t diag = 0;
+    // geometry
+    uint32_t rb_lds_kb = 144, rb_lds_kb_staged = 120, l2_range_kb = 2048, l2_range_kb_staged = 4096;
+    bool rb_lds_user = false, l2_range_user = false;
+    int out_staged = -1;
+    uint64_t out_staged_min = 8ull << 20;
+    int rb_rows_force = -1;
+    bool small_sparse_rb = true;
+    int batches = -1;
+    // scheduling
+    bool item_cost_cuts = true, item_lpt = true;
+    uint32_t piece_max = 16;
+    double piece_weight = 4.0, shard_piece_weight = 4.0, item_cap = -1.0, item_fixed = 1024.0;
+    int orig_contig = 1;
+    double batch_min_phases = 2.0;
+    int piece_balance = 0;
+};
+
+struct RbGeometry {
+    uint32_t rowBytes = 0;
+    bool orig = false, cols = false;  // original-order row blocks / column blocks (whole plan)
+    uint32_t RB = 0, NT = 0, nRB = 0;  // rows per block, threads per workgroup, blocks
+    size_t lds = 0;                    // the A image: RB * rowBytes
+    uint32_t l2Kb = 0, m = 1;          // column-range budget; ranges per XCD
+    bool stagedWanted = false, staged = false;
+    uint32_t outCap = 0;     // results the LDS past the image holds
+    uint32_t perBucket = 1;  // workgroup slots per XCD
+};
+
+// Rows per row block for rows of rowBytes: a multiple of 16 with RB * rowBytes within the LDS
+// budget, at most 1024 (10-bit local row in the entry metadata) and no more than the matrix needs.
+uint32_t rowblock_rows(uint32_t rowBytes, uint32_t lds_kb, uint32_t R);
+
+// Block geometry of a layout over Rs staged rows holding n0 entries (before tile demotion), the
+// gathered index space of NS columns, on a device of cus compute units; nnz = the plan's.
+RbGeometry rb_geometry(uint32_t rowBytes, uint32_t Rs, uint32_t n0, uint32_t NS, uint32_t nnz, int cus,
+                       bool orig, bool cols, const RbKnobs& k);
+
+struct RbScheduleIn {
+    // the entries sorted by (row block, column): words whose low 22 bits are the column (read in
+    // place, never copied)
+    const uint32_t* entries = nullptr;
+    size_t n = 0;
+    const uint32_t* rbEnd = nullptr;  // per row block: end of its entries (non-decreasing)
+    // kept tiles of row block b: positions [keptBegin[b], keptBegin[b + 1]) of the kept list
+    // (nRB + 1 values); null: no kept tiles
+    const uint32_t* keptBegin = nullptr;
+    uint32_t NS = 0;
+    RbGeometry geom;
+    RbKnobs knobs;
+    unsigned threads = 0;  // host threads (0: up to 16); the result does not depend on it
+    std::function<void(const char*)> lap;  // called after each phase with its name (may be empty)
+};
+
+struct RbScheduleOut {
+    std::vector<RbItem> items;    // launch order: list position j of XCD x at j * 8 + x
+    std::vector<uint32_t> ends;   // per item: piece end
+    std::vector<RbPiece> pieces;
+    std::vector<RbPiece> ient;    // per item {first entry, entries}
+    std::vector<RbItem> itemStat;  // per item {row block, kept tiles, entries, pieces}; padding 0
+    std::vector<double> rbCost;   // per row block: the shard cost model
+    uint32_t nWorkItems = 0;
+    bool dyn = false;  // dynamic piece batches
+};
+
+// Items, pieces and statistics of a layout from its sorted entries. Never touches a device.
+void rb_schedule(const RbScheduleIn& in, RbScheduleOut& out);
+
+// f(thread, begin, end) over [0, n) on up to `threads` host threads (0: up to 16): contiguous
+// ranges, each index visited once (results written per index are independent of the split)
+template <class F>
+void par_for(size_t n, F&& f, size_t serial_below = 2048, unsigned threads = 0) {
+    const unsigned T = threads ? threads : std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
+    if (n < serial_below || T == 1) {
+        f(0u, size_t{0}, n);
+        return;
+    }
+    std::vector<std::thread> th;
+    const size_t chunk = (n + T - 1) / T;
+    for (unsigned t = 0; t < T; ++t) {
+        const size_t a = t * chunk, b = std::min(n, a + chunk);
+        if (a < b) th.emplace_back([&f, t, a, b]() { f(t, a, b); });
+    }
+    for (auto& x : th) x.join();
+}
+
+}  // namespace bsmr

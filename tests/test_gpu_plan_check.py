@@ -95,6 +95,10 @@ LAYOUTS = {
     "batches_orig": (lambda: synth.trefethen(3000), 64, F32, {"tuning": {"orig_rows": 1, "batches": 1}}),
     "batches_scattered": (lambda: synth.random_rows(4000, 60000, 40, seed=12, zipf=0.6), 128, F32,
                           {"tuning": {"batches": 1}}),
+    # static piece order dealt to the least-loaded wave (balance_pieces): items of one phase
+    # (unchanged order) and, staged with 1 KiB rows (G = 8), items of several phases
+    "piece_balance": (ZIPF, 128, F32, {"tuning": {"piece_balance": 1}}),
+    "piece_balance_staged_1k": (WIDE, 256, F32, {"tuning": {"out_staged": 1, "piece_balance": 1}}),
 }
 
 

@@ -35,7 +35,9 @@ extern "C" {
                               launch), piece_balance, stats ptile_items, bsmr_cost_cuts; removed the dropped experiments'
                               knobs piece_order, seg_items, sweep* and stats rb_sweep;
                               13: bsmr_tuning.col_blocks (column-block launch of wide patterns),
-                              stats rb_col_blocks */
+                              stats rb_col_blocks; additive to 13 (no struct changed):
+                              bsmr_plan_prepare, bsmr_plan_prepare_panels, bsmr_plan_prepared,
+                              bsmr_plan_panels_prepared, BSMR_ERR_NOT_PREPARED */
 
 typedef enum {
     BSMR_OK = 0,
@@ -45,7 +47,8 @@ typedef enum {
     BSMR_ERR_HIP = 4,         /* HIP runtime error (message via bsmr_last_error) */
     BSMR_ERR_TIMEOUT = 5,     /* a persistent reorder kernel gave up waiting (never expected) */
     BSMR_ERR_UNSUPPORTED = 6, /* e.g. K not a multiple of 16, dtype not built */
-    BSMR_ERR_CHECK = 7        /* bsmr_plan_check found a structural error (bsmr_last_error) */
+    BSMR_ERR_CHECK = 7,       /* bsmr_plan_check found a structural error (bsmr_last_error) */
+    BSMR_ERR_NOT_PREPARED = 8 /* stream is capturing and the launch layout is not built */
 } bsmr_status;
 
 typedef enum { BSMR_F32 = 0, BSMR_F16 = 1, BSMR_BF16 = 2 } bsmr_dtype;
@@ -335,7 +338,10 @@ int bsmr_check_rphm_arrays(uint32_t M, uint32_t N, uint32_t nnz, const uint32_t*
 /* Replaces sddmm_gpu(M, N, K, dA, dB, rphm, dP, logger) (include/sddmmKernel.cuh:25-30,
  * src/sddmmKernel.cu:2540-2762): device pointers, dA row-major M x K, dB column-major K x N,
  * dP (fp32, nnz, CSR order) overwritten. dtype selects the A/B element type (fp32, or fp16/bf16
- * with fp32 accumulation). stream: a hipStream_t (NULL = default stream). Asynchronous. */
+ * with fp32 accumulation). stream: a hipStream_t (NULL = default stream). Asynchronous once the
+ * launch layout of (K, dtype) exists: the first launch builds it (allocations, copies and a
+ * synchronisation of the plan's own stream) unless bsmr_plan_prepare did. On a capturing stream
+ * an unbuilt layout gives BSMR_ERR_NOT_PREPARED and leaves the capture intact. */
 int bsmr_sddmm(const bsmr_plan* plan, const void* dA, const void* dB, uint32_t K, int dtype,
                float* dP, void* stream);
 /* Replaces sddmm_gpu_batch(numBatch, M, N, K, nnz, dA, dB, rphm, dP, time)
@@ -389,8 +395,30 @@ int bsmr_sddmm_panels_local(const bsmr_plan* plan, const void* dA_local, const v
                             uint32_t K, int dtype, float* dP, uint32_t p0, uint32_t p1,
                             void* stream);
 
+/* Build, now, every launch layout bsmr_sddmm / bsmr_sddmm_batch would build lazily for (K, dtype):
+ * the row-block layout (including the original-order / column-block candidates and the choice
+ * between them), or the panel-tile item list, or the dense-sampled tile list, whichever that
+ * (K, dtype) takes. Synchronous: on return the layouts are resident and any stream may launch,
+ * a capturing one included (so call it before the capture begins: it allocates and synchronises).
+ * Same K / dtype validation and status codes as bsmr_sddmm. A (K, dtype) that runs the
+ * column-major launch has nothing to build: BSMR_OK. Idempotent. bsmr_plan_recolumn drops every
+ * layout that depends on the column split (all but the dense-sampled list and the identity row
+ * list): prepare again after it. */
+int bsmr_plan_prepare(const bsmr_plan* plan, uint32_t K, int dtype);
+/* The same for bsmr_sddmm_panels (local = 0) or bsmr_sddmm_panels_local (local != 0, also the
+ * identity row list) over panels [p0, p1). Same range checks and BSMR_ERR_UNSUPPORTED cases as
+ * those calls. The plan keeps the 16 most recently prepared ranges (a 17th drops the oldest);
+ * ranges built lazily by a launch are cached apart and never evict a prepared one. */
+int bsmr_plan_prepare_panels(const bsmr_plan* plan, uint32_t K, int dtype, uint32_t p0,
+                             uint32_t p1, int local);
+/* 1 when the matching launch would make no allocation, copy or synchronisation, else 0
+ * (also 0 on bad arguments, with bsmr_last_error set). No device call. */
+int bsmr_plan_prepared(const bsmr_plan* plan, uint32_t K, int dtype);
+int bsmr_plan_panels_prepared(const bsmr_plan* plan, uint32_t K, int dtype, uint32_t p0,
+                              uint32_t p1, int local);
+
 /* Timing: run `iters` back-to-back SDDMMs on `stream`, timing each kernel with HIP events on
- * that stream. Outputs average ms per launch of the dense-tile kernel, the residual kernel and
+ * that stream (BSMR_ERR_UNSUPPORTED on a capturing stream). Outputs average ms per launch of the dense-tile kernel, the residual kernel and
  * the whole SDDMM. */
 int bsmr_sddmm_profile(const bsmr_plan* plan, const void* dA, const void* dB, uint32_t K,
                        int dtype, float* dP, int iters, void* stream, float* ms_dense,

@@ -22,6 +22,7 @@ LIB_PATH = os.environ.get("BSMR_LIB_PATH") or os.path.join(PKG_ROOT, "lib", "lib
 
 F32, F16, BF16 = 0, 1, 2
 CHECK_FAILED = 7  # BSMR_ERR_CHECK
+NOT_PREPARED = 8  # BSMR_ERR_NOT_PREPARED: capturing stream, launch layout not built (Plan.prepare)
 
 ARRAYS = {
     "reorderedRows": 0, "denseCols": 1, "denseColOffsets": 2, "sparseCols": 3,
@@ -35,7 +36,12 @@ _f32p = np.ctypeslib.ndpointer(dtype=np.float32, flags="C_CONTIGUOUS")
 
 
 class BsmrError(RuntimeError):
-    pass
+    """status: the library's integer status (include/bsmr.h bsmr_status); None when the binding
+    itself raised."""
+
+    def __init__(self, msg, status=None):
+        super().__init__(msg)
+        self.status = status
 
 
 class Tuning(C.Structure):
@@ -140,6 +146,8 @@ EXPORTS = [
     "bsmr_plan_export_rows", "bsmr_plan_import_rows",
     "bsmr_sddmm_profile", "bsmr_sddmm_cpu", "bsmr_check_one", "bsmr_check_data",
     "bsmr_plan_check", "bsmr_check_rphm_arrays", "bsmr_cost_cuts",
+    "bsmr_plan_prepare", "bsmr_plan_prepare_panels", "bsmr_plan_prepared",
+    "bsmr_plan_panels_prepared",
 ]
 
 _lib = None
@@ -215,6 +223,12 @@ def lib():
     L.bsmr_sddmm_profile.argtypes = [vp, vp, vp, C.c_uint32, C.c_int, vp, C.c_int, vp,
                                      C.POINTER(C.c_float), C.POINTER(C.c_float),
                                      C.POINTER(C.c_float)]
+    for f in ("bsmr_plan_prepare", "bsmr_plan_prepared"):
+        getattr(L, f).argtypes = [vp, C.c_uint32, C.c_int]
+        getattr(L, f).restype = C.c_int
+    for f in ("bsmr_plan_prepare_panels", "bsmr_plan_panels_prepared"):
+        getattr(L, f).argtypes = [vp, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, C.c_int]
+        getattr(L, f).restype = C.c_int
     L.bsmr_plan_check.argtypes = [vp, C.c_uint32, C.c_int, C.c_int]
     L.bsmr_plan_check.restype = C.c_int
     L.bsmr_check_rphm_arrays.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32] + [_u32p] * 2 + \
@@ -227,7 +241,7 @@ def lib():
 def _check(status, what):
     if status != 0:
         msg = lib().bsmr_last_error().decode(errors="replace")
-        raise BsmrError(f"{what} failed with status {status}: {msg}")
+        raise BsmrError(f"{what} failed with status {status}: {msg}", status)
 
 
 _default_tuning = {}
@@ -436,6 +450,26 @@ class Plan:
         if st != CHECK_FAILED:
             raise BsmrError(f"bsmr_plan_check failed with status {st}: {msg}")
         return False, msg
+
+    def prepare(self, K, dtype=F32, panels=None, local=False):
+        """Build now what the first sddmm / sddmm_batch of (K, dtype) would build inside the call
+        (bsmr_plan_prepare); panels=(p0, p1): the same for sddmm_panels over that range, or with
+        local=True for sddmm_panels_local (bsmr_plan_prepare_panels). Synchronous; afterwards the
+        launch touches no host state and can be captured into a HIP graph. recolumn() drops what
+        this built."""
+        if panels is None:
+            _check(lib().bsmr_plan_prepare(self.h, K, dtype), "bsmr_plan_prepare")
+        else:
+            _check(lib().bsmr_plan_prepare_panels(self.h, K, dtype, panels[0], panels[1],
+                                                  1 if local else 0), "bsmr_plan_prepare_panels")
+
+    def prepared(self, K, dtype=F32, panels=None, local=False):
+        """Whether the matching launch would allocate, copy or synchronise nothing
+        (bsmr_plan_prepared / bsmr_plan_panels_prepared; no device call)."""
+        if panels is None:
+            return bool(lib().bsmr_plan_prepared(self.h, K, dtype))
+        return bool(lib().bsmr_plan_panels_prepared(self.h, K, dtype, panels[0], panels[1],
+                                                    1 if local else 0))
 
     def sddmm(self, dA, dB, K, dP, stream=0, dtype=F32):
         """dA, dB, dP: device pointers (int) — e.g. torch tensor .data_ptr()."""

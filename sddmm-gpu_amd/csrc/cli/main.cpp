@@ -64,7 +64,9 @@ void run_sddmm(bsmr_plan* plan, const bsmr_csr* S, uint32_t K, int iters, cli::L
     hipStream_t s;
     HIPCHK(hipStreamCreate(&s));
     float* P = static_cast<float*>(dP.p);
-    int st = bsmr_sddmm(plan, dA.p, dB.p, K, BSMR_F32, P, s);  // warm-up (code object load)
+    int st = bsmr_plan_prepare(plan, K, BSMR_F32);  // the launch layout, built before any launch
+    if (st) die("bsmr_plan_prepare", st);
+    st = bsmr_sddmm(plan, dA.p, dB.p, K, BSMR_F32, P, s);  // warm-up (code object load)
     if (st) die("bsmr_sddmm", st);
     hipEvent_t e0, e1;
     HIPCHK(hipEventCreate(&e0));

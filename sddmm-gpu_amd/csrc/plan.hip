@@ -1499,15 +1499,28 @@ static void release_layout(Plan::RowBlockLayout& L) {
     L.itemRuns.release();
 }
 
+static int rb_layout_slot(u32 rowBytes, bool half) {
+    return (rowBytes == 128 ? 0 : rowBytes == 256 ? 1 : rowBytes == 512 ? 2 : rowBytes == 1024 ? 3 : 4) +
+           (half ? Plan::N_RB_SIZES : 0);
+}
+
 std::shared_ptr<const Plan::RowBlockLayout> Plan::rowblock_layout(u32 rowBytes, bool half,
-                                                                  u32 pa, u32 pb, int* err) const {
+                                                                  u32 pa, u32 pb, int* err,
+                                                                  bool keep) const {
     *err = BSMR_OK;
     const u32 tmin = half ? tile_min_half : tile_min_f32;
     if (pa == 0 && pb == P) {
-        const int slot = (rowBytes == 128 ? 0 : rowBytes == 256 ? 1 : rowBytes == 512 ? 2 : rowBytes == 1024 ? 3 : 4) +
-                         (half ? Plan::N_RB_SIZES : 0);
+        const int slot = rb_layout_slot(rowBytes, half);
         RowBlockLayout& L = rbl[slot];
         if (L.rowBytes != rowBytes || L.tileMin != tmin) {
+            // (a failed candidate build below leaves the slot unbuilt: rowblock_ready reads rbl)
+            struct Unbuilt {
+                RowBlockLayout& L;
+                const int* err;
+                ~Unbuilt() {
+                    if (*err != BSMR_OK) L.rowBytes = 0;
+                }
+            } unbuilt{L, err};
             rb_use_orig[slot] = false;
             rb_use_cols[slot] = false;
             *err = build_rowblock_layout(L, rowBytes, 0, P, tmin);
@@ -1543,14 +1556,58 @@ std::shared_ptr<const Plan::RowBlockLayout> Plan::rowblock_layout(u32 rowBytes, 
         }
         return std::shared_ptr<const RowBlockLayout>(std::shared_ptr<void>(), &rb_whole(slot));
     }
-    for (const auto& L : shard_rbl)
-        if (L->rowBytes == rowBytes && L->pa == pa && L->pb == pb && L->tileMin == tmin) return L;
-    auto L = std::make_shared<RowBlockLayout>();
-    *err = build_rowblock_layout(*L, rowBytes, pa, pb, tmin);
-    if (*err != BSMR_OK) return nullptr;
-    if (shard_rbl.size() >= MAX_SHARD_LAYOUTS) shard_rbl.erase(shard_rbl.begin());
-    shard_rbl.push_back(L);
+    const auto same = [&](const std::shared_ptr<RowBlockLayout>& L) {
+        return L->rowBytes == rowBytes && L->pa == pa && L->pb == pb && L->tileMin == tmin;
+    };
+    for (const auto& L : prep_rbl)
+        if (same(L)) return L;
+    std::shared_ptr<RowBlockLayout> L;
+    const auto it = std::find_if(shard_rbl.begin(), shard_rbl.end(), same);
+    if (it != shard_rbl.end()) {
+        L = *it;
+        if (!keep) return L;
+        shard_rbl.erase(it);  // built lazily before: it moves to the prepared list
+    } else {
+        L = std::make_shared<RowBlockLayout>();
+        *err = build_rowblock_layout(*L, rowBytes, pa, pb, tmin);
+        if (*err != BSMR_OK) return nullptr;
+    }
+    auto& list = keep ? prep_rbl : shard_rbl;
+    if (list.size() >= MAX_SHARD_LAYOUTS) list.erase(list.begin());
+    list.push_back(L);
     return L;
+}
+
+std::shared_ptr<const Plan::RowBlockLayout> Plan::rowblock_ready(u32 rowBytes, bool half, u32 pa,
+                                                                 u32 pb) const {
+    const u32 tmin = half ? tile_min_half : tile_min_f32;
+    if (pa == 0 && pb == P) {
+        const int slot = rb_layout_slot(rowBytes, half);
+        if (rbl[slot].rowBytes != rowBytes || rbl[slot].tileMin != tmin) return nullptr;
+        return std::shared_ptr<const RowBlockLayout>(std::shared_ptr<void>(), &rb_whole(slot));
+    }
+    for (const auto* list : {&prep_rbl, &shard_rbl})
+        for (const auto& L : *list)
+            if (L->rowBytes == rowBytes && L->pa == pa && L->pb == pb && L->tileMin == tmin) return L;
+    return nullptr;
+}
+
+void Plan::drop_launch_layouts() {
+    for (int i = 0; i < N_RB_LAYOUTS; ++i) {
+        for (RowBlockLayout* L : {&rbl[i], &rblo[i], &rblc[i]}) {
+            release_layout(*L);
+            L->rowBytes = 0;
+        }
+        rb_use_orig[i] = rb_use_cols[i] = false;
+    }
+    shard_rbl.clear();
+    prep_rbl.clear();
+    // the panel-tile items name tiles and their columns (the dense-sampled list and the identity
+    // row list depend on S and R only and stay)
+    ptile.built = false;
+    ptile.nItems = ptile.nListed = 0;
+    ptile.items.release();
+    ptile.desc.release();
 }
 
 // The row-block layout build in stages: block geometry and item scheduling are
@@ -2163,8 +2220,10 @@ int Plan::build_columns() {
             s));
         segments_ready = true;
     }
-    for (auto& L : rbl) L.rowBytes = 0;  // launch layouts depend on the column split
-    shard_rbl.clear();
+    {  // launch layouts depend on the column split
+        std::lock_guard<std::mutex> g(layout_mu);
+        drop_launch_layouts();
+    }
     // pass 1
     const u32 thr =static_cast<u32>(std::ceil(delta * static_cast<float>(TILE)));  // colReordering.cu:246
     DevBuf<u32> phist, pnd, pns, psd;

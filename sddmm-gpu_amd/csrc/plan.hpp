@@ -19,15 +19,29 @@ constexpr u32 RB_PIECE_MAX = 16;    // entries per column-run piece (row-block l
 constexpr u32 XCD_BUCKETS = 8;      // MI355X XCDs: column bucket -> workgroups b with b % 8
 
 struct Plan;
+// A launch entry point, as the lazy layout builders see it: the caller's stream, and the names
+// and (K, dtype) of the BSMR_ERR_NOT_PREPARED message (prep = the call that builds the layout)
+struct LaunchSite {
+    hipStream_t s;
+    const char* who;
+    const char* prep;
+    u32 K;
+    int dtype;
+};
+// A launch whose layout is not built asks before it builds: BSMR_ERR_NOT_PREPARED when at.s is
+// capturing, BSMR_ERR_HIP when that query fails, else BSMR_OK (sddmm.hip). Launches whose layout
+// is built never call it
+int lazy_build_guard(const LaunchSite& at);
 // fp16/bf16 SDDMM launch (sddmm_half.hip); mode: 1 dense tiles, 2 residual, 3 both
 int launch_half(const Plan& p, const void* dA, const void* dB, u32 K, int dtype, float* dP,
                 u32 mode, hipStream_t s, u32 nb = 1);
-// fp16/bf16 dense-sampled launch (sddmm_dense.hip): K a multiple of 64
+// fp16/bf16 dense-sampled launch (sddmm_dense.hip): K a multiple of 64. at: the entry point, for
+// the guard of a lazy build (null: build without asking)
 int launch_dense(const Plan& p, const void* dA, const void* dB, u32 K, int dtype, float* dP,
-                 hipStream_t s, u32 nb = 1);
+                 hipStream_t s, u32 nb = 1, const LaunchSite* at = nullptr);
 // fp16/bf16 panel-grouped tile launch (sddmm_half.hip): K in {64, 128, 256, 512}; mode as above
 int launch_ptile(const Plan& p, const void* dA, const void* dB, u32 K, int dtype, float* dP,
-                 u32 mode, hipStream_t s, u32 nb = 1);
+                 u32 mode, hipStream_t s, u32 nb = 1, const LaunchSite* at = nullptr);
 
 // clustering candidate filter (cluster_filter.hip): the bit triangle of pairs (leader q,
 // position p > q) whose similarity bound may reach alpha; W = words per full row
@@ -248,6 +262,9 @@ struct Plan {
     static constexpr size_t MAX_SHARD_LAYOUTS = 16;
     // shared: a caller keeps its layout alive while another thread's request evicts it
     mutable std::vector<std::shared_ptr<RowBlockLayout>> shard_rbl;
+    // layouts of panel ranges built through bsmr_plan_prepare_panels (oldest first, at most
+    // MAX_SHARD_LAYOUTS): lazy builds never evict one; a further prepare drops the oldest
+    mutable std::vector<std::shared_ptr<RowBlockLayout>> prep_rbl;
     int build_rowblock_layout(RowBlockLayout& L, u32 rowBytes, u32 pa, u32 pb, u32 tileMin,
                               bool orig = false, bool cols = false) const;
     // the whole-plan layout a launch of this slot uses (rbl, rblo or rblc)
@@ -256,9 +273,15 @@ struct Plan {
     }
     // the (cached) layout for rows of rowBytes over panels [pa, pb) for fp32 (half = false) or
     // fp16/bf16 operands; null on error. Call with layout_mu held; the whole-plan layouts are
-    // plan members (non-owning pointer), a shard layout is shared with the cache
+    // plan members (non-owning pointer), a shard layout is shared with the cache. keep: a panel
+    // range's layout goes on (or moves to) the prepared list
     std::shared_ptr<const RowBlockLayout> rowblock_layout(u32 rowBytes, bool half, u32 pa, u32 pb,
-                                                          int* err) const;
+                                                          int* err, bool keep = false) const;
+    // the same lookup building nothing: null when a launch would have to build (layout_mu held)
+    std::shared_ptr<const RowBlockLayout> rowblock_ready(u32 rowBytes, bool half, u32 pa,
+                                                         u32 pb) const;
+    // everything that depends on the column split is dropped (build_columns; layout_mu held)
+    void drop_launch_layouts();
 
     mutable DevBuf<uint8_t> tmp;  // scan/sort scratch
     // BSMR_DIAG & 32 debug timeline (4 u64 per wave of the last launch)
@@ -308,6 +331,7 @@ struct Plan {
     // at most n tiles of one panel (C5 block: 4 -> 5.93 us, 2 -> 7.5, 5 -> 7.7)
     u32 ptile_tpi = 0;
     int build_ptile_layout(u32 tpi) const;
+    bool ptile_ready() const { return ptile.built && ptile.tpi == ptile_tpi; }
 
     int build_rows(const u32* h_rowptr, const u32* h_col);
     int build_columns();

@@ -1452,20 +1452,25 @@ KernelFn pick_kernel(u32 K) {
     return pick_k<4, PANELS>(K);
 }
 
+// K / dtype rules of every launch (and of bsmr_plan_prepare, which reports under its own name)
+int validate_kd(const char* who, u32 K, int dtype) {
+    if (K == 0 || K % 16 != 0) {
+        set_error(std::string(who) + ": K must be a positive multiple of 16");
+        return BSMR_ERR_UNSUPPORTED;
+    }
+    if (dtype != BSMR_F32 && dtype != BSMR_F16 && dtype != BSMR_BF16) {
+        set_error(std::string(who) + ": dtype must be BSMR_F32, BSMR_F16 or BSMR_BF16");
+        return BSMR_ERR_UNSUPPORTED;
+    }
+    return BSMR_OK;
+}
+
 int validate(const void* dA, const void* dB, u32 K, int dtype, const float* dP) {
     if (!dA || !dB || !dP) {
         set_error("bsmr_sddmm: null device pointer");
         return BSMR_ERR_INVALID;
     }
-    if (K == 0 || K % 16 != 0) {
-        set_error("bsmr_sddmm: K must be a positive multiple of 16");
-        return BSMR_ERR_UNSUPPORTED;
-    }
-    if (dtype != BSMR_F32 && dtype != BSMR_F16 && dtype != BSMR_BF16) {
-        set_error("bsmr_sddmm: dtype must be BSMR_F32, BSMR_F16 or BSMR_BF16");
-        return BSMR_ERR_UNSUPPORTED;
-    }
-    return BSMR_OK;
+    return validate_kd("bsmr_sddmm", K, dtype);
 }
 
 SddmmArgs make_args(const Plan& p, const void* dA, const void* dB, u32 K, float* dP) {
@@ -1531,13 +1536,44 @@ bool use_ptile(const Plan& p, u32 K, int dtype) {
            static_cast<u64>(p.nres) * 4 < static_cast<u64>(p.numDenseTiles) * 16;
 }
 
-// the row-block layout of panels [pa, pb) for slot's row size (built on first use)
+// the launch bsmr_sddmm / bsmr_sddmm_batch runs for (K, dtype)
+enum class Launch { Ptile, Dense, RowBlock, Half, ColMajor };
+Launch launch_kind(const Plan& p, u32 K, int dtype) {
+    if (use_ptile(p, K, dtype)) return Launch::Ptile;
+    if (use_dense(p, K, dtype)) return Launch::Dense;
+    if (rb_slot(p, K, dtype) >= 0) return Launch::RowBlock;
+    return dtype != BSMR_F32 ? Launch::Half : Launch::ColMajor;
+}
+
+// the row-block layout of panels [pa, pb) for slot's row size. A cached layout is returned as it
+// is (no HIP call); else it is built now: after lazy_build_guard when a launch asks (at), kept on
+// the prepared list when bsmr_plan_prepare_panels does (keep)
 int get_rb_layout(const Plan& p, int slot, int dtype, u32 pa, u32 pb,
-                  std::shared_ptr<const Plan::RowBlockLayout>* out) {
+                  std::shared_ptr<const Plan::RowBlockLayout>* out, const LaunchSite* at = nullptr,
+                  bool keep = false) {
     std::lock_guard<std::mutex> g(p.layout_mu);
+    const u32 rowBytes = 128u << slot;
+    const bool half = dtype != BSMR_F32;
+    if (!keep) {
+        *out = p.rowblock_ready(rowBytes, half, pa, pb);
+        if (*out) return BSMR_OK;
+        if (at) BSMR_CHECK(lazy_build_guard(*at));
+    }
     int err = BSMR_OK;
-    *out = p.rowblock_layout(128u << slot, dtype != BSMR_F32, pa, pb, &err);
+    *out = p.rowblock_layout(rowBytes, half, pa, pb, &err, keep);
     return err;
+}
+
+// the identity row list of bsmr_sddmm_panels_local (built on first use, as above)
+int get_iota(const Plan& p, const LaunchSite* at = nullptr) {
+    std::lock_guard<std::mutex> g(p.layout_mu);
+    if (p.iotaR.size() >= p.R) return BSMR_OK;
+    if (at) BSMR_CHECK(lazy_build_guard(*at));
+    std::vector<u32> id(p.R);
+    for (u32 q = 0; q < p.R; ++q) id[q] = q;
+    BSMR_CHECK(p.iotaR.upload(id.data(), p.R, p.stream));
+    BSMR_HIP(hipStreamSynchronize(p.stream));
+    return BSMR_OK;
 }
 
 // mode: 1 = dense tiles only, 2 = residual only, 3 = both (profiling splits). local: dA holds
@@ -1655,6 +1691,26 @@ int launch_panels(SddmmArgs a, hipStream_t s) {
 
 }  // namespace
 
+static const char* dtype_name(int dtype) {
+    return dtype == BSMR_F32 ? "fp32" : dtype == BSMR_F16 ? "fp16" : "bf16";
+}
+
+// A launch found its layout not built. Building allocates, copies and synchronises, none of which
+// a capturing stream survives, so the launch is refused there (the one HIP call made is the query).
+int lazy_build_guard(const LaunchSite& at) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    const hipError_t e = hipStreamIsCapturing(at.s, &cs);
+    if (e != hipSuccess) {
+        set_error(std::string(at.who) + ": hipStreamIsCapturing: " + hipGetErrorString(e));
+        return BSMR_ERR_HIP;
+    }
+    if (cs == hipStreamCaptureStatusNone) return BSMR_OK;
+    set_error(std::string(at.who) + ": stream is capturing and the layout of (K = " +
+              std::to_string(at.K) + ", " + dtype_name(at.dtype) + ") is not built; call " + at.prep +
+              " first");
+    return BSMR_ERR_NOT_PREPARED;
+}
+
 // pairs (BSMR_DIAG & 16384 off): staged output by runs, rows of >= 512 bytes, at least
 // pair_min_items (4096: 16 rounds of the chip's workgroup slots) items, an even number of list
 // positions per XCD, no kept MFMA tile; not under the profiling ablations (trace, staging only, B
@@ -1692,8 +1748,8 @@ using namespace bsmr;
 
 // one launch per at most 65535 batches (grid.y); batch b reads A + b*M*K, B + b*N*K and writes
 // P + b*nnz (sddmm_gpu_batch, sddmmKernel.cu:2764-2850)
-extern "C" int bsmr_sddmm_batch(const bsmr_plan* plan, uint32_t num_batch, const void* dA,
-                                const void* dB, uint32_t K, int dtype, float* dP, void* stream) {
+static int sddmm_batch(const char* who, const bsmr_plan* plan, uint32_t num_batch, const void* dA,
+                       const void* dB, uint32_t K, int dtype, float* dP, void* stream) {
     if (!plan) {
         set_error("bsmr_sddmm: null plan");
         return BSMR_ERR_INVALID;
@@ -1706,27 +1762,28 @@ extern "C" int bsmr_sddmm_batch(const bsmr_plan* plan, uint32_t num_batch, const
     BSMR_CHECK(validate(dA, dB, K, dtype, dP));
     const hipStream_t s = static_cast<hipStream_t>(stream);
     const size_t es = dtype == BSMR_F32 ? 4 : 2;
+    const LaunchSite at{s, who, "bsmr_plan_prepare", K, dtype};
+    const Launch kind = launch_kind(p, K, dtype);
     for (u32 b0 = 0; b0 < num_batch; b0 += 65535u) {
         const u32 nb = std::min<u32>(num_batch - b0, 65535u);
         const char* A = static_cast<const char*>(dA) + es * b0 * static_cast<size_t>(p.M) * K;
         const char* B = static_cast<const char*>(dB) + es * b0 * static_cast<size_t>(p.N) * K;
         float* P = dP + static_cast<size_t>(b0) * p.nnz;
-        if (use_ptile(p, K, dtype)) {
-            BSMR_CHECK(launch_ptile(p, A, B, K, dtype, P, 3, s, nb));
+        if (kind == Launch::Ptile) {
+            BSMR_CHECK(launch_ptile(p, A, B, K, dtype, P, 3, s, nb, &at));
             continue;
         }
-        if (use_dense(p, K, dtype)) {
-            BSMR_CHECK(launch_dense(p, A, B, K, dtype, P, s, nb));
+        if (kind == Launch::Dense) {
+            BSMR_CHECK(launch_dense(p, A, B, K, dtype, P, s, nb, &at));
             continue;
         }
-        const int slot = rb_slot(p, K, dtype);
-        if (slot >= 0) {
+        if (kind == Launch::RowBlock) {
             std::shared_ptr<const Plan::RowBlockLayout> L;
-            BSMR_CHECK(get_rb_layout(p, slot, dtype, 0, p.P, &L));
+            BSMR_CHECK(get_rb_layout(p, rb_slot(p, K, dtype), dtype, 0, p.P, &L, &at));
             BSMR_CHECK(launch_rb(p, *L, A, B, P, dtype, 3, s, nb));
             continue;
         }
-        if (dtype != BSMR_F32) {
+        if (kind == Launch::Half) {
             BSMR_CHECK(launch_half(p, A, B, K, dtype, P, 3, s, nb));
             continue;
         }
@@ -1738,9 +1795,14 @@ extern "C" int bsmr_sddmm_batch(const bsmr_plan* plan, uint32_t num_batch, const
     return BSMR_OK;
 }
 
+extern "C" int bsmr_sddmm_batch(const bsmr_plan* plan, uint32_t num_batch, const void* dA,
+                                const void* dB, uint32_t K, int dtype, float* dP, void* stream) {
+    return sddmm_batch("bsmr_sddmm_batch", plan, num_batch, dA, dB, K, dtype, dP, stream);
+}
+
 extern "C" int bsmr_sddmm(const bsmr_plan* plan, const void* dA, const void* dB, uint32_t K,
                           int dtype, float* dP, void* stream) {
-    return bsmr_sddmm_batch(plan, 1, dA, dB, K, dtype, dP, stream);
+    return sddmm_batch("bsmr_sddmm", plan, 1, dA, dB, K, dtype, dP, stream);
 }
 
 extern "C" int bsmr_sddmm_panels(const bsmr_plan* plan, const void* dA, const void* dB,
@@ -1760,9 +1822,11 @@ extern "C" int bsmr_sddmm_panels(const bsmr_plan* plan, const void* dA, const vo
     // the row-block kernel over the range's own layout (same kernel as the whole plan)
     const int slot = rb_slot(p, K, dtype);
     if (slot >= 0) {
+        const LaunchSite at{static_cast<hipStream_t>(stream), "bsmr_sddmm_panels",
+                            "bsmr_plan_prepare_panels", K, dtype};
         std::shared_ptr<const Plan::RowBlockLayout> L;  // held until the launch is enqueued
-        BSMR_CHECK(get_rb_layout(p, slot, dtype, p0, p1, &L));
-        return launch_rb(p, *L, dA, dB, dP, dtype, 3, static_cast<hipStream_t>(stream));
+        BSMR_CHECK(get_rb_layout(p, slot, dtype, p0, p1, &L, &at));
+        return launch_rb(p, *L, dA, dB, dP, dtype, 3, at.s);
     }
     if (dtype != BSMR_F32) {
         set_error("bsmr_sddmm_panels: fp16/bf16 panel ranges need the row-block layout "
@@ -1811,23 +1875,117 @@ extern "C" int bsmr_sddmm_panels_local(const bsmr_plan* plan, const void* dA_loc
         set_error("bsmr_sddmm_panels_local: needs the row-block launch (rows of 128 B .. 2 KiB)");
         return BSMR_ERR_UNSUPPORTED;
     }
-    {
-        std::lock_guard<std::mutex> g(p.layout_mu);
-        if (p.iotaR.size() < p.R) {
-            std::vector<u32> id(p.R);
-            for (u32 q = 0; q < p.R; ++q) id[q] = q;
-            BSMR_CHECK(p.iotaR.upload(id.data(), p.R, p.stream));
-            BSMR_HIP(hipStreamSynchronize(p.stream));
-        }
-    }
+    const LaunchSite at{static_cast<hipStream_t>(stream), "bsmr_sddmm_panels_local",
+                        "bsmr_plan_prepare_panels", K, dtype};
+    BSMR_CHECK(get_iota(p, &at));
     std::shared_ptr<const Plan::RowBlockLayout> L;  // held until the launch is enqueued
-    BSMR_CHECK(get_rb_layout(p, slot, dtype, p0, p1, &L));
+    BSMR_CHECK(get_rb_layout(p, slot, dtype, p0, p1, &L, &at));
     if (L->orig || L->cols)  // the whole range may have picked original-order row blocks or
                              // column blocks: use the reordered layout (always built first), whose
                              // rows follow the local A
         L = std::shared_ptr<const Plan::RowBlockLayout>(
             std::shared_ptr<void>(), &p.rbl[slot + (dtype != BSMR_F32 ? Plan::N_RB_SIZES : 0)]);
-    return launch_rb(p, *L, dA_local, dB, dP, dtype, 3, static_cast<hipStream_t>(stream), 1, true);
+    return launch_rb(p, *L, dA_local, dB, dP, dtype, 3, at.s, 1, true);
+}
+
+// ---- explicit layout builds (bsmr.h): what the launches above would build on first use ----
+
+static int prepare_args(const char* who, const bsmr_plan* plan, uint32_t K, int dtype) {
+    if (!plan) {
+        set_error(std::string(who) + ": null plan");
+        return BSMR_ERR_INVALID;
+    }
+    return validate_kd(who, K, dtype);
+}
+
+// the panel-range checks of bsmr_sddmm_panels / _panels_local; *slot = -1 when there is nothing
+// to build (an empty range, or fp32 on the panel-major lists)
+static int prepare_panels_args(const char* who, const bsmr_plan* plan, uint32_t K, int dtype,
+                               uint32_t p0, uint32_t p1, int local, int* slot) {
+    *slot = -1;
+    BSMR_CHECK(prepare_args(who, plan, K, dtype));
+    const Plan& p = plan->p;
+    if (p0 > p1 || p1 > p.P) {
+        set_error(std::string(who) + ": bad panel range");
+        return BSMR_ERR_INVALID;
+    }
+    if (p0 == p1) return BSMR_OK;
+    *slot = rb_slot(p, K, dtype);
+    if (*slot < 0 && local) {
+        set_error(std::string(who) + ": bsmr_sddmm_panels_local needs the row-block launch (rows of "
+                                     "128 B .. 2 KiB)");
+        return BSMR_ERR_UNSUPPORTED;
+    }
+    if (*slot < 0 && dtype != BSMR_F32) {
+        set_error(std::string(who) + ": fp16/bf16 panel ranges need the row-block layout (half K in "
+                                     "128..1024)");
+        return BSMR_ERR_UNSUPPORTED;
+    }
+    return BSMR_OK;
+}
+
+static int half_colmajor_k(const char* who, u32 K) {  // launch_half's rule
+    if (K % 32 == 0) return BSMR_OK;
+    set_error(std::string(who) + ": fp16/bf16 inputs need K to be a positive multiple of 32");
+    return BSMR_ERR_UNSUPPORTED;
+}
+
+extern "C" int bsmr_plan_prepare(const bsmr_plan* plan, uint32_t K, int dtype) {
+    BSMR_CHECK(prepare_args("bsmr_plan_prepare", plan, K, dtype));
+    const Plan& p = plan->p;
+    switch (launch_kind(p, K, dtype)) {
+        case Launch::Ptile: {
+            std::lock_guard<std::mutex> g(p.layout_mu);
+            if (!p.ptile_ready()) BSMR_CHECK(p.build_ptile_layout(p.ptile_tpi));
+            return BSMR_OK;
+        }
+        case Launch::Dense: {
+            std::lock_guard<std::mutex> g(p.layout_mu);
+            if (!p.dense.built) BSMR_CHECK(p.build_dense_layout());
+            return BSMR_OK;
+        }
+        case Launch::RowBlock: {
+            std::shared_ptr<const Plan::RowBlockLayout> L;
+            return get_rb_layout(p, rb_slot(p, K, dtype), dtype, 0, p.P, &L);
+        }
+        case Launch::Half: return half_colmajor_k("bsmr_plan_prepare", K);
+        default: return BSMR_OK;
+    }
+}
+
+extern "C" int bsmr_plan_prepared(const bsmr_plan* plan, uint32_t K, int dtype) {
+    if (prepare_args("bsmr_plan_prepared", plan, K, dtype) != BSMR_OK) return 0;
+    const Plan& p = plan->p;
+    const Launch kind = launch_kind(p, K, dtype);
+    if (kind == Launch::Half) return half_colmajor_k("bsmr_plan_prepared", K) == BSMR_OK;
+    if (kind == Launch::ColMajor) return 1;
+    std::lock_guard<std::mutex> g(p.layout_mu);
+    if (kind == Launch::Ptile) return p.ptile_ready();
+    if (kind == Launch::Dense) return p.dense.built;
+    return p.rowblock_ready(128u << rb_slot(p, K, dtype), dtype != BSMR_F32, 0, p.P) != nullptr;
+}
+
+extern "C" int bsmr_plan_prepare_panels(const bsmr_plan* plan, uint32_t K, int dtype, uint32_t p0,
+                                        uint32_t p1, int local) {
+    int slot = -1;
+    BSMR_CHECK(prepare_panels_args("bsmr_plan_prepare_panels", plan, K, dtype, p0, p1, local, &slot));
+    if (slot < 0) return BSMR_OK;
+    const Plan& p = plan->p;
+    if (local) BSMR_CHECK(get_iota(p));
+    std::shared_ptr<const Plan::RowBlockLayout> L;
+    return get_rb_layout(p, slot, dtype, p0, p1, &L, nullptr, true);
+}
+
+extern "C" int bsmr_plan_panels_prepared(const bsmr_plan* plan, uint32_t K, int dtype, uint32_t p0,
+                                         uint32_t p1, int local) {
+    int slot = -1;
+    if (prepare_panels_args("bsmr_plan_panels_prepared", plan, K, dtype, p0, p1, local, &slot) != BSMR_OK)
+        return 0;
+    if (slot < 0) return 1;
+    const Plan& p = plan->p;
+    std::lock_guard<std::mutex> g(p.layout_mu);
+    if (local && p.iotaR.size() < p.R) return 0;
+    return p.rowblock_ready(128u << slot, dtype != BSMR_F32, p0, p1) != nullptr;
 }
 
 extern "C" int bsmr_sddmm_profile(const bsmr_plan* plan, const void* dA, const void* dB,
@@ -1840,6 +1998,14 @@ extern "C" int bsmr_sddmm_profile(const bsmr_plan* plan, const void* dA, const v
     const Plan& p = plan->p;
     BSMR_CHECK(validate(dA, dB, K, dtype, dP));
     hipStream_t s = static_cast<hipStream_t>(stream);
+    {  // the timing synchronises events: never on a capturing stream
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        BSMR_HIP(hipStreamIsCapturing(s, &cs));
+        if (cs != hipStreamCaptureStatusNone) {
+            set_error("bsmr_sddmm_profile: stream is capturing (the timing synchronises events)");
+            return BSMR_ERR_UNSUPPORTED;
+        }
+    }
     struct Events {  // destroyed on every return path
         hipEvent_t e[4] = {};
         ~Events() {

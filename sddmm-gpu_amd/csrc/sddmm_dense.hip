@@ -278,10 +278,13 @@ int Plan::build_dense_layout() const {
 
 // fp16/bf16, K a multiple of 64: the whole product in 128 x 128 MFMA tiles, sampled
 int launch_dense(const Plan& p, const void* dA, const void* dB, u32 K, int dtype, float* dP,
-                 hipStream_t s, u32 nb) {
+                 hipStream_t s, u32 nb, const LaunchSite* at) {
     {
         std::lock_guard<std::mutex> g(p.layout_mu);
-        if (!p.dense.built) BSMR_CHECK(p.build_dense_layout());
+        if (!p.dense.built) {
+            if (at) BSMR_CHECK(lazy_build_guard(*at));
+            BSMR_CHECK(p.build_dense_layout());
+        }
     }
     const Plan::DenseLayout& D = p.dense;
     DenseArgs a{};

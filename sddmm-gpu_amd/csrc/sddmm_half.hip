@@ -399,7 +399,7 @@ int Plan::build_ptile_layout(u32 tpi) const {
 // tile-dominated fp16/bf16 plans, K in {64, 128, 256, 512}: the panel-grouped tile launch (mode: 1
 // tiles, 2 residual slots, 3 both)
 int launch_ptile(const Plan& p, const void* dA, const void* dB, u32 K, int dtype, float* dP,
-                 u32 mode, hipStream_t s, u32 nb) {
+                 u32 mode, hipStream_t s, u32 nb, const LaunchSite* at) {
     const u32 NK = K / 32;
     if (K % 32 != 0 || (NK != 2 && NK != 4 && NK != 8 && NK != 16)) {
         set_error("bsmr_sddmm: the panel-tile launch needs K in {64, 128, 256, 512}");
@@ -407,7 +407,10 @@ int launch_ptile(const Plan& p, const void* dA, const void* dB, u32 K, int dtype
     }
     {
         std::lock_guard<std::mutex> g(p.layout_mu);
-        if (!p.ptile.built || p.ptile.tpi != p.ptile_tpi) BSMR_CHECK(p.build_ptile_layout(p.ptile_tpi));
+        if (!p.ptile_ready()) {
+            if (at) BSMR_CHECK(lazy_build_guard(*at));
+            BSMR_CHECK(p.build_ptile_layout(p.ptile_tpi));
+        }
     }
     PtileArgs a{};
     a.h.A = static_cast<const uint16_t*>(dA);

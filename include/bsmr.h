@@ -37,7 +37,10 @@ extern "C" {
                               13: bsmr_tuning.col_blocks (column-block launch of wide patterns),
                               stats rb_col_blocks; additive to 13 (no struct changed):
                               bsmr_plan_prepare, bsmr_plan_prepare_panels, bsmr_plan_prepared,
-                              bsmr_plan_panels_prepared, BSMR_ERR_NOT_PREPARED */
+                              bsmr_plan_panels_prepared, BSMR_ERR_NOT_PREPARED; bsmr_spmm,
+                              bsmr_spmm_t, bsmr_plan_prepare_spmm, bsmr_plan_spmm_prepared,
+                              bsmr_plan_spmm_stats, bsmr_spmm_lists (SpMM over the plan's pattern:
+                              the gradients of bsmr_sddmm) */
 
 typedef enum {
     BSMR_OK = 0,
@@ -416,6 +419,62 @@ int bsmr_plan_prepare_panels(const bsmr_plan* plan, uint32_t K, int dtype, uint3
 int bsmr_plan_prepared(const bsmr_plan* plan, uint32_t K, int dtype);
 int bsmr_plan_panels_prepared(const bsmr_plan* plan, uint32_t K, int dtype, uint32_t p0,
                               uint32_t p1, int local);
+
+/* --------------------------------------------------- SpMM / the gradients of SDDMM ---- */
+/* SpMM over the plan's pattern S with caller values V (fp32, nnz, CSR order, as P):
+ *   bsmr_spmm   : Y (M x K fp32, row-major)           = S(V) B     Y[i,:] = sum_j V[idx(i,j)] B[j,:]
+ *   bsmr_spmm_t : Y (N x K fp32, B's layout Y[c*K+k]) = S(V)^T A   Y[j,:] = sum_i V[idx(i,j)] A[i,:]
+ * With V = dP these are dA and dB of bsmr_sddmm; with V the scores of an SDDMM they are the
+ * aggregation that follows it. dB / dA: the dense operand in bsmr_sddmm's layout and dtype (fp32,
+ * or fp16/bf16 accumulated in fp32), 16-byte aligned like dY. Every element of Y is overwritten
+ * (rows / columns without entries with 0), so the caller clears nothing. No atomics: a
+ * destination's terms are added in a fixed order, so two launches give bitwise
+ * equal results. Same K / dtype rules and status codes as bsmr_sddmm. Asynchronous on `stream`
+ * once the side's gather lists exist and its scratch covers K: the first launch builds them
+ * unless bsmr_plan_prepare_spmm did, and on a capturing stream an unbuilt side gives
+ * BSMR_ERR_NOT_PREPARED and leaves the capture intact. Launches of one side of one plan share that
+ * side's scratch: order them on one stream (or with events); the two sides are independent. */
+int bsmr_spmm(const bsmr_plan* plan, const float* dV, const void* dB, uint32_t K, int dtype,
+              float* dY, void* stream);
+int bsmr_spmm_t(const bsmr_plan* plan, const float* dV, const void* dA, uint32_t K, int dtype,
+                float* dY, void* stream);
+/* Build now what the first bsmr_spmm (sides & 1) / bsmr_spmm_t (sides & 2) of K columns would
+ * build inside the call: the side's gather lists and the scratch of its split destinations.
+ * chunk: entries per segment (one wave each; longer lists are split and summed through partial
+ * rows), 0 = keep the lists already built, else the default (512). Synchronous and idempotent; a
+ * larger K grows the scratch, a different non-zero chunk rebuilds the lists. sides outside 1..3:
+ * BSMR_ERR_INVALID. The lists do not depend on the column split: bsmr_plan_recolumn keeps them. */
+int bsmr_plan_prepare_spmm(const bsmr_plan* plan, uint32_t K, int sides, uint32_t chunk);
+/* 1 when the launches of `sides` at K would make no allocation, copy or synchronisation, else 0
+ * (also 0 on bad arguments, with bsmr_last_error set). No device call. */
+int bsmr_plan_spmm_prepared(const bsmr_plan* plan, uint32_t K, int sides);
+typedef struct {
+    uint32_t segments;    /* waves of the launch (every destination has at least one) */
+    uint32_t split_dsts;  /* destinations with more than `chunk` entries */
+    uint32_t partials;    /* their segments = partial rows of scratch */
+    uint32_t max_list;    /* entries of the longest destination */
+    uint32_t chunk;
+} bsmr_spmm_stats;
+/* side 1 (rows) or 2 (columns); zeros when that side is not built. */
+int bsmr_plan_spmm_stats(const bsmr_plan* plan, int side, bsmr_spmm_stats* out);
+
+/* Host-only form of the gather lists (no plan, no device). side 1: destination = row, source =
+ * the entry's column; side 2: destination = column, source = the entry's row. src / vpos (nnz
+ * each): every destination's entries (source index, CSR position) in ascending CSR position,
+ * destinations in ascending index. segs: the lists cut into segments {dst, first, count, part} of
+ * at most `chunk` entries starting at src[first]; a destination without entries has one segment
+ * of count 0; a destination of several segments has consecutive partial slots `part`, any other
+ * 0xFFFFFFFF (it writes Y directly). Segments follow `order` (norder destinations, each at most
+ * once; NULL = none), then the destinations it leaves out in ascending index. segs == NULL:
+ * query *nsegs only. BSMR_ERR_INVALID for chunk 0, a side outside {1, 2}, an order entry out of
+ * range or repeated, a rowptr that is not non-decreasing from 0 to nnz, a column index >= N. */
+typedef struct {
+    uint32_t dst, first, count, part;
+} bsmr_spmm_seg;
+int bsmr_spmm_lists(uint32_t M, uint32_t N, uint32_t nnz, const uint32_t* rowptr,
+                    const uint32_t* colidx, int side, uint32_t chunk, const uint32_t* order,
+                    uint32_t norder, bsmr_spmm_seg* segs, uint64_t* nsegs, uint32_t* src,
+                    uint32_t* vpos);
 
 /* Timing: run `iters` back-to-back SDDMMs on `stream`, timing each kernel with HIP events on
  * that stream (BSMR_ERR_UNSUPPORTED on a capturing stream). Outputs average ms per launch of the dense-tile kernel, the residual kernel and

@@ -6,6 +6,8 @@ Reference interface mirrored (paths relative to the reference root):
   * BSMR(alpha, delta, S) + RPHM(S, bsmr)              -> Plan            (src/BSMR.cpp:16-265)
   * sddmm_gpu(M, N, K, dA, dB, rphm, dP, logger)       -> Plan.sddmm      (src/sddmmKernel.cu:2540)
   * evaluationReordering                               -> Plan.evaluate   (src/BSMR.cpp:826-994)
+Beyond the reference: the gradients of the SDDMM as SpMM over the same plan (Plan.spmm,
+Plan.spmm_t, Plan.sddmm_backward; bsmr.autograd wraps both directions for torch.autograd).
 
 Every call goes through the HIP library; there is no CPU fallback. If the shared library is
 missing the import fails loudly (build it with `make -C sddmm-gpu_amd` or
@@ -130,6 +132,17 @@ class RowStage(C.Structure):
         return cls.from_buffer_copy(np.ascontiguousarray(a, np.uint8).tobytes())
 
 
+class SpmmStats(C.Structure):
+    """bsmr_spmm_stats: one side's gather lists (zeros when not built)."""
+    _fields_ = [("segments", C.c_uint32), ("split_dsts", C.c_uint32), ("partials", C.c_uint32),
+                ("max_list", C.c_uint32), ("chunk", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+SPMM_DIRECT = 0xFFFFFFFF  # bsmr_spmm_seg.part of a segment that writes Y itself
+
 ABI_VERSION = 13  # include/bsmr.h BSMR_ABI_VERSION
 
 # every symbol include/bsmr.h declares (tests check the library exports all of them)
@@ -148,6 +161,8 @@ EXPORTS = [
     "bsmr_plan_check", "bsmr_check_rphm_arrays", "bsmr_cost_cuts",
     "bsmr_plan_prepare", "bsmr_plan_prepare_panels", "bsmr_plan_prepared",
     "bsmr_plan_panels_prepared",
+    "bsmr_spmm", "bsmr_spmm_t", "bsmr_plan_prepare_spmm", "bsmr_plan_spmm_prepared",
+    "bsmr_plan_spmm_stats", "bsmr_spmm_lists",
 ]
 
 _lib = None
@@ -229,6 +244,18 @@ def lib():
     for f in ("bsmr_plan_prepare_panels", "bsmr_plan_panels_prepared"):
         getattr(L, f).argtypes = [vp, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, C.c_int]
         getattr(L, f).restype = C.c_int
+    for f in ("bsmr_spmm", "bsmr_spmm_t"):
+        getattr(L, f).argtypes = [vp, vp, vp, C.c_uint32, C.c_int, vp, vp]
+        getattr(L, f).restype = C.c_int
+    L.bsmr_plan_prepare_spmm.argtypes = [vp, C.c_uint32, C.c_int, C.c_uint32]
+    L.bsmr_plan_prepare_spmm.restype = C.c_int
+    L.bsmr_plan_spmm_prepared.argtypes = [vp, C.c_uint32, C.c_int]
+    L.bsmr_plan_spmm_prepared.restype = C.c_int
+    L.bsmr_plan_spmm_stats.argtypes = [vp, C.c_int, C.POINTER(SpmmStats)]
+    L.bsmr_plan_spmm_stats.restype = C.c_int
+    L.bsmr_spmm_lists.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, _u32p, _u32p, C.c_int,
+                                  C.c_uint32, vp, C.c_uint32, vp, C.POINTER(C.c_uint64), vp, vp]
+    L.bsmr_spmm_lists.restype = C.c_int
     L.bsmr_plan_check.argtypes = [vp, C.c_uint32, C.c_int, C.c_int]
     L.bsmr_plan_check.restype = C.c_int
     L.bsmr_check_rphm_arrays.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32] + [_u32p] * 2 + \
@@ -489,6 +516,37 @@ class Plan:
         _check(lib().bsmr_sddmm_panels_local(self.h, dA_local, dB, K, dtype, dP, p0, p1,
                                              stream or None), "bsmr_sddmm_panels_local")
 
+    def spmm(self, dV, dB, K, dY, stream=0, dtype=F32):
+        """bsmr_spmm: Y (M x K fp32) = S(V) B. dV (fp32, nnz, CSR order), dB (N x K of dtype) and
+        dY are device pointers; with V = dP this is dA of sddmm. Every element of Y is written."""
+        _check(lib().bsmr_spmm(self.h, dV, dB, K, dtype, dY, stream or None), "bsmr_spmm")
+
+    def spmm_t(self, dV, dA, K, dY, stream=0, dtype=F32):
+        """bsmr_spmm_t: Y (N x K fp32) = S(V)^T A; with V = dP this is dB of sddmm."""
+        _check(lib().bsmr_spmm_t(self.h, dV, dA, K, dtype, dY, stream or None), "bsmr_spmm_t")
+
+    def prepare_spmm(self, K, sides=3, chunk=0):
+        """bsmr_plan_prepare_spmm: build now the gather lists and scratch of spmm (sides & 1) and
+        spmm_t (sides & 2) at K, so that their first launch can be captured. chunk: entries per
+        segment, 0 = what is built already, else the default."""
+        _check(lib().bsmr_plan_prepare_spmm(self.h, K, sides, chunk), "bsmr_plan_prepare_spmm")
+
+    def spmm_prepared(self, K, sides=3):
+        return bool(lib().bsmr_plan_spmm_prepared(self.h, K, sides))
+
+    def spmm_stats(self, side):
+        s = SpmmStats()
+        _check(lib().bsmr_plan_spmm_stats(self.h, side, C.byref(s)), "bsmr_plan_spmm_stats")
+        return s.as_dict()
+
+    def sddmm_backward(self, dG, dA, dB, K, dGA, dGB, stream=0, dtype=F32):
+        """The gradients of P = sddmm(A, B) from dG = dL/dP (fp32, nnz): dGA (M x K fp32) =
+        S(G) B and dGB (N x K fp32) = S(G)^T A. Either output may be 0: that side is skipped."""
+        if dGA:
+            self.spmm(dG, dB, K, dGA, stream=stream, dtype=dtype)
+        if dGB:
+            self.spmm_t(dG, dA, K, dGB, stream=stream, dtype=dtype)
+
     def shard(self, K, rank, world, dtype=F32):
         """Panel range [p0, p1) of `rank` (bsmr_plan_shard_dtype)."""
         p0, p1 = C.c_uint32(), C.c_uint32()
@@ -544,6 +602,29 @@ def cost_cuts(block_cost, panels_per_block, P, world, prev_cuts=None, shard_ms=N
     _check(lib().bsmr_cost_cuts(ptr(bc), len(bc), panels_per_block, P, world, ptr(pc), ptr(ms),
                                 cuts), "bsmr_cost_cuts")
     return [int(c) for c in cuts]
+
+
+def spmm_lists(M, N, rowptr, colidx, side, chunk, order=None):
+    """bsmr_spmm_lists (host only): (segs, src, vpos) of the SpMM gather lists of side 1 (rows) or
+    2 (columns). segs: (n, 4) uint32 rows {dst, first, count, part} in launch order (`order`
+    first, then the other destinations ascending); src / vpos: nnz each."""
+    rowptr = np.ascontiguousarray(rowptr, np.uint32)
+    colidx = np.ascontiguousarray(colidx, np.uint32)
+    nnz = len(colidx)
+    if len(rowptr) != M + 1:
+        raise ValueError("spmm_lists: rowptr needs M + 1 entries")
+    ci = colidx if nnz else np.zeros(1, np.uint32)
+    od = None if order is None else np.ascontiguousarray(order, np.uint32)
+    optr, on = (None, 0) if od is None else (od.ctypes.data if len(od) else None, len(od))
+    n = C.c_uint64()
+    args = (M, N, nnz, rowptr, ci, side, chunk, optr, on)
+    _check(lib().bsmr_spmm_lists(*args, None, C.byref(n), None, None), "bsmr_spmm_lists")
+    segs = np.zeros((n.value, 4), np.uint32)
+    src = np.zeros(max(nnz, 1), np.uint32)
+    vpos = np.zeros(max(nnz, 1), np.uint32)
+    _check(lib().bsmr_spmm_lists(*args, segs.ctypes.data, C.byref(n), src.ctypes.data,
+                                 vpos.ctypes.data), "bsmr_spmm_lists")
+    return segs, src[:nnz], vpos[:nnz]
 
 
 def sddmm_cpu(M, N, rowptr, colidx, K, A, B, threads=0):

@@ -588,6 +588,41 @@ extern "C" int bsmr_cost_cuts(const double* block_cost, uint32_t nblocks, uint32
     return BSMR_OK;
 }
 
+// the SpMM gather lists over caller arrays (spmm_schedule.cpp; no plan, no device)
+extern "C" int bsmr_spmm_lists(uint32_t M, uint32_t N, uint32_t nnz, const uint32_t* rowptr,
+                               const uint32_t* colidx, int side, uint32_t chunk, const uint32_t* order,
+                               uint32_t norder, bsmr_spmm_seg* segs, uint64_t* nsegs, uint32_t* src,
+                               uint32_t* vpos) {
+    static_assert(sizeof(bsmr_spmm_seg) == sizeof(SpmmSeg), "bsmr_spmm_seg mirrors SpmmSeg");
+    if (!rowptr || (nnz && !colidx) || !nsegs || (segs && nnz && (!src || !vpos))) {
+        set_error("bsmr_spmm_lists: null argument");
+        return BSMR_ERR_INVALID;
+    }
+    SpmmIn in;
+    in.M = M;
+    in.N = N;
+    in.nnz = nnz;
+    in.rowptr = rowptr;
+    in.colidx = colidx;
+    in.side = side;
+    in.chunk = chunk;
+    in.order = order;
+    in.norder = order ? norder : 0;
+    SpmmLists L;
+    std::string err;
+    if (spmm_lists(in, L, err, segs == nullptr)) {
+        set_error("bsmr_spmm_lists: " + err);
+        return BSMR_ERR_INVALID;
+    }
+    *nsegs = L.nSegs;
+    if (!segs) return BSMR_OK;
+    for (size_t i = 0; i < L.segs.size(); ++i)
+        segs[i] = bsmr_spmm_seg{L.segs[i].dst, L.segs[i].first, L.segs[i].count, L.segs[i].part};
+    std::copy(L.src.begin(), L.src.end(), src);
+    std::copy(L.vpos.begin(), L.vpos.end(), vpos);
+    return BSMR_OK;
+}
+
 extern "C" int bsmr_plan_shard_rebalance(const bsmr_plan* plan, uint32_t K, int dtype, int world,
                                          const uint32_t* prev_cuts, const float* shard_ms,
                                          uint32_t* cuts) {

@@ -8,6 +8,7 @@
 
 #include "common.hpp"
 #include "rb_schedule.hpp"
+#include "spmm_schedule.hpp"
 
 namespace bsmr {
 
@@ -332,6 +333,21 @@ struct Plan {
     u32 ptile_tpi = 0;
     int build_ptile_layout(u32 tpi) const;
     bool ptile_ready() const { return ptile.built && ptile.tpi == ptile_tpi; }
+
+    // plan-based SpMM (spmm.hip; bsmr_spmm / bsmr_spmm_t): one side's gather lists
+    // (spmm_schedule.hpp: segments in launch order, sources, value positions, split
+    // destinations) and the partial rows of its split destinations (partials x scratchK floats).
+    // Built on first use or by bsmr_plan_prepare_spmm, under layout_mu; they depend on S and the
+    // row order only, so build_columns keeps them
+    struct SpmmSide {
+        bool built = false;
+        u32 chunk = 0, nSegs = 0, nReds = 0, splitDsts = 0, partials = 0, maxList = 0, scratchK = 0;
+        DevBuf<SpmmSeg> segs;
+        DevBuf<u32> src, vpos;
+        DevBuf<SpmmRed> reds;
+        DevBuf<float> scratch;
+    };
+    mutable SpmmSide spmm[2];  // [0] rows (bsmr_spmm), [1] columns (bsmr_spmm_t)
 
     int build_rows(const u32* h_rowptr, const u32* h_col);
     int build_columns();

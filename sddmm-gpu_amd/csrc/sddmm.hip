@@ -1722,6 +1722,8 @@ bool rb_uses_pairs(const Plan& p, const Plan::RowBlockLayout& L) {
            !(p.diag & (8u | 32u | 64u | 128u | 16384u));
 }
 
+// the K / dtype rules above for the launches of other units (spmm.hip)
+int launch_validate_kd(const char* who, u32 K, int dtype) { return validate_kd(who, K, dtype); }
 // whether bsmr_sddmm runs the dense-sampled launch for (K, dtype) (plan_check.cpp)
 bool sddmm_uses_dense(const Plan& p, u32 K, int dtype) { return use_dense(p, K, dtype); }
 // whether bsmr_sddmm runs the panel-grouped tile launch for (K, dtype) (plan_check.cpp, stats)

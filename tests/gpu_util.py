@@ -53,7 +53,69 @@ def assert_plans_equal(gpu_plan, orc_plan):
 
 
 def half_values(X, dtype):
-    """X rounded (RNE) to fp16 (dtype 1) or bf16 (2), back in fp32: the values the kernel sees."""
-    torch = torch_cuda()
+    """X rounded (RNE) to fp16 (dtype 1) or bf16 (2), back in fp32: the values the kernel sees.
+    Host only (the device does the same rounding in run_sddmm)."""
+    import torch
     tdt = {1: torch.float16, 2: torch.bfloat16}[dtype]
     return torch.from_numpy(np.ascontiguousarray(X, np.float32)).to(tdt).float().numpy()
+
+
+def torch_dtype(dtype):
+    torch = torch_cuda()
+    return {0: torch.float32, 1: torch.float16, 2: torch.bfloat16}[dtype]
+
+
+def to_device(X, dtype):
+    """X (fp32 on the host) as a device tensor of `dtype`, converted on the host so that the device
+    holds exactly the bits of half_values(X, dtype)."""
+    torch = torch_cuda()
+    return torch.from_numpy(np.array(X, np.float32)).to(torch_dtype(dtype)).cuda()
+
+
+def nan_output(n):
+    torch = torch_cuda()
+    return torch.full((max(int(n), 1),), float("nan"), dtype=torch.float32, device="cuda")
+
+
+def sddmm_once(plan, A, B, K, nnz, dtype=0):
+    """P (numpy fp32, nnz) of one bsmr_sddmm on host operands; P starts as NaN."""
+    torch = torch_cuda()
+    dA, dB, dP = to_device(A, dtype), to_device(B, dtype), nan_output(nnz)
+    plan.sddmm(dA.data_ptr(), dB.data_ptr(), K, dP.data_ptr(),
+               stream=torch.cuda.current_stream().cuda_stream, dtype=dtype)
+    torch.cuda.synchronize()
+    return dP.cpu().numpy()[:nnz]
+
+
+def rb_geometry(plan, K, dtype):
+    """The whole-plan row-block layout of (K, dtype) through the library's debug export (not in the
+    header): rows per block, threads per workgroup, item slots, row bytes; None when that (K, dtype)
+    does not run the row-block launch. Builds the layout if no launch has."""
+    import ctypes as C
+
+    import bsmr
+    L = bsmr.lib()
+    L.bsmr_debug_rb_items.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.POINTER(C.c_uint64)]
+    n = C.c_uint64()
+    assert L.bsmr_debug_rb_items(plan.h, K, dtype, None, C.byref(n)) == 0
+    if n.value == 0:
+        return None
+    buf = np.zeros(n.value, np.uint32)
+    assert L.bsmr_debug_rb_items(plan.h, K, dtype, buf.ctypes.data, C.byref(n)) == 0
+    return dict(rb=int(buf[0]), nt=int(buf[1]), items=int(buf[2]), row_bytes=int(buf[3]))
+
+
+def path_evidence(case, plan):
+    """Failures (strings) of a sddmm_cases.Case's evidence that its launch path ran, after the
+    launch: sddmm_cases.check_stats on the plan's stats and, for the row-block launch, its layout
+    geometry, for the panel-tile launch the plan's tile offsets and the device's CU count."""
+    from sddmm_cases import check_stats
+    geom = None
+    if case.kind == "rowblock":
+        geom = rb_geometry(plan, case.K, case.dtype)
+    elif case.kind == "ptile":
+        cus = torch_cuda().cuda.get_device_properties(0).multi_processor_count
+        geom = dict(block_offsets=plan.array("blockOffsets"), cus=int(cus))
+    bad = check_stats(case, plan.stats(), geom)
+    shown = dict(geom, block_offsets="...") if geom and "block_offsets" in geom else geom
+    return [f"{b} (geometry {shown}, stats {plan.stats()})" for b in bad]

@@ -373,7 +373,7 @@ extern "C" int bsmr_plan_get_stats(const bsmr_plan* plan, bsmr_plan_stats* s) {
         s->rb_work_items[i] = L.rowBytes ? L.nWorkItems : 0;
         if (L.rowBytes && L.orig) s->rb_orig_rows |= 1u << i;
         if (L.rowBytes && L.cols) s->rb_col_blocks |= 1u << i;
-        if (L.rowBytes && rb_uses_pairs(p, L)) s->rb_pairs |= 1u << i;
+        if (L.rowBytes && rb_form(rb_layout_facts(L), rb_launch_knobs(p), 3).pairs) s->rb_pairs |= 1u << i;
         if (L.rowBytes && L.dynBatches) s->rb_batches |= 1u << i;
     }
     s->dense_sampled_tiles = p.dense.built ? p.dense.nonempty : 0;
@@ -744,5 +744,83 @@ extern "C" int bsmr_debug_rb_schedule(const uint32_t* sorted_cols, uint64_t n, c
     for (const RbItem& it : o.itemStat) { *w++ = it.x; *w++ = it.y; *w++ = it.z; *w++ = it.w; }
     *w++ = o.dyn;
     *w++ = o.nWorkItems;
+    return BSMR_OK;
+}
+
+namespace {
+void put_choice(const LaunchChoice& c, uint32_t* out) {
+    out[0] = static_cast<uint32_t>(c.kind);
+    out[1] = static_cast<uint32_t>(c.slot + 1);
+    out[2] = c.rowBytes;
+}
+void put_form(const RbForm& f, uint32_t* out) {
+    const uint32_t w[9] = {f.stageNt, f.lateB, f.pairs, f.lite, f.dyn, f.NT, f.grid, f.ldsBytes, f.stageBlocks};
+    std::copy(w, w + 9, out);
+}
+}  // namespace
+
+// debug: the launch (launch_select.hpp choose_launch) of a plan with facts = {M, N, nnz, residual
+// entries, dense tiles}, layout auto (layout_rowblock 1, force_rowblock 0), row-block (1, 1) or
+// column-major (0, 0), under tuning t (null: defaults). Needs no device. out[3] = {kind (0 panel
+// tile, 1 dense-sampled, 2 row-block, 3 column-major half, 4 column-major fp32), row-block slot +
+// 1 (0: none), row bytes}; returns the status of the K / dtype rules (validate_kd, then the chosen
+// launch's validate_launch_k), their text in bsmr_last_error. Not in the header
+// (tests/test_launch_select_cpu.py)
+extern "C" int bsmr_debug_launch_choice(const uint32_t* facts, int layout_rowblock, int force_rowblock,
+                                        const bsmr_tuning* t, uint32_t K, int dtype, uint32_t* out) {
+    if (!facts || !out) return BSMR_ERR_INVALID;
+    Plan p;  // defaults; no device, no stream
+    if (t) apply_tuning(p, *t);
+    p.M = facts[0];
+    p.N = facts[1];
+    p.nnz = facts[2];
+    p.nres = facts[3];
+    p.numDenseTiles = facts[4];
+    p.use_rowblock = layout_rowblock != 0;
+    p.force_rowblock = force_rowblock != 0;
+    const LaunchChoice c = choose_launch(p, K, dtype);
+    put_choice(c, out);
+    BSMR_CHECK(report(validate_kd("bsmr_debug_launch_choice", K, dtype)));
+    return report(validate_launch_k("bsmr_debug_launch_choice", c.kind, K));
+}
+
+// debug: the panel-range rules (launch_select.hpp check_panel_range) as entry point `who` reports
+// them for a plan of P panels whose (K, dtype) has row-block slot `slot` (-1: none): the status,
+// its text in bsmr_last_error. Needs no device. Not in the header
+extern "C" int bsmr_debug_panel_range(const char* who, uint32_t p0, uint32_t p1, uint32_t P, int slot,
+                                      int dtype, int local) {
+    if (!who) return BSMR_ERR_INVALID;
+    return report(check_panel_range(who, p0, p1, P, slot, dtype, local != 0));
+}
+
+// debug: the form (launch_select.hpp rb_form) of a row-block launch of mode (1 tiles, 2 residual, 3
+// both) over a layout with layoutFacts = {rowBytes, NT, nItems, nTilesKept, outLds, outRuns,
+// dynBatches} under tuning t (null: defaults). Needs no device. out[9] = {stageNt, lateB, pairs,
+// lite, dyn, NT, grid, LDS bytes, stageBlocks (0: the A image's)}. Not in the header
+extern "C" int bsmr_debug_rb_form(const uint32_t* layoutFacts, const bsmr_tuning* t, uint32_t mode,
+                                  uint32_t* out) {
+    if (!layoutFacts || !out) return BSMR_ERR_INVALID;
+    Plan p;
+    if (t) apply_tuning(p, *t);
+    const uint32_t* w = layoutFacts;
+    put_form(rb_form({w[0], w[1], w[2], w[3], w[4], w[5] != 0, w[6] != 0}, rb_launch_knobs(p), mode), out);
+    return BSMR_OK;
+}
+
+// debug: what bsmr_sddmm runs on this plan for (K, dtype): out[12] = the three words of
+// bsmr_debug_launch_choice, then for the row-block kind the nine of bsmr_debug_rb_form for the
+// whole launch of the plan's layout (built on first use, as bsmr_debug_rb_items does; else
+// zeros). Not in the header (tests/sddmm_cases.py)
+extern "C" int bsmr_debug_plan_launch(const bsmr_plan* plan, uint32_t K, int dtype, uint32_t* out) {
+    if (!plan || !out) return BSMR_ERR_INVALID;
+    BSMR_CHECK(report(validate_kd("bsmr_debug_plan_launch", K, dtype)));
+    const Plan& p = plan->p;
+    const LaunchChoice c = choose_launch(p, K, dtype);
+    std::fill(out, out + 12, 0u);
+    put_choice(c, out);
+    if (c.kind != Launch::RowBlock) return BSMR_OK;
+    const Plan::RowBlockLayout* L = nullptr;
+    BSMR_CHECK(whole_rb_layout(p, K, dtype, &L));
+    put_form(rb_form(rb_layout_facts(*L), rb_launch_knobs(p), 3), out + 3);
     return BSMR_OK;
 }

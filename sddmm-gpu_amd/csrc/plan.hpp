@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "launch_select.hpp"
 #include "rb_schedule.hpp"
 #include "spmm_schedule.hpp"
 
@@ -268,6 +269,11 @@ struct Plan {
     mutable std::vector<std::shared_ptr<RowBlockLayout>> prep_rbl;
     int build_rowblock_layout(RowBlockLayout& L, u32 rowBytes, u32 pa, u32 pb, u32 tileMin,
                               bool orig = false, bool cols = false) const;
+    // the whole plan's reordered-row layout of a row size (always built first; panel shards cut
+    // its row blocks, and a local A follows its rows)
+    const RowBlockLayout& rb_reordered(int slot, int dtype) const {
+        return rbl[slot + (dtype != BSMR_F32 ? N_RB_SIZES : 0)];
+    }
     // the whole-plan layout a launch of this slot uses (rbl, rblo or rblc)
     const RowBlockLayout& rb_whole(int slot) const {
         return rb_use_cols[slot] ? rblc[slot] : rb_use_orig[slot] ? rblo[slot] : rbl[slot];
@@ -361,8 +367,29 @@ RbKnobs rb_knobs(const Plan& p);
 // the whole plan's row-block layout for (K, dtype) (sddmm.hip); *out = null for column-major
 int whole_rb_layout(const Plan& p, u32 K, int dtype, const Plan::RowBlockLayout** out,
                     bool reordered = false);
-// whether a full launch of layout L runs two items per workgroup (k_sddmm_rb_pair; sddmm.hip)
-bool rb_uses_pairs(const Plan& p, const Plan::RowBlockLayout& L);
+
+// ---- what launch_select.hpp reads from a plan ----
+static_assert(LS_F32 == BSMR_F32 && LS_F16 == BSMR_F16 && LS_BF16 == BSMR_BF16 && LS_OK == BSMR_OK &&
+                  LS_ERR_INVALID == BSMR_ERR_INVALID && LS_ERR_UNSUPPORTED == BSMR_ERR_UNSUPPORTED &&
+                  LS_XCDS == XCD_BUCKETS,
+              "launch_select.hpp constants");
+inline PlanFacts launch_facts(const Plan& p) {
+    return {p.M, p.N, p.nnz, p.nres, p.numDenseTiles, p.use_rowblock, p.force_rowblock, p.ptile_mode, p.dense_min};
+}
+inline LaunchChoice choose_launch(const Plan& p, u32 K, int dtype) {
+    return choose_launch(launch_facts(p), K, dtype);
+}
+inline RbLayoutFacts rb_layout_facts(const Plan::RowBlockLayout& L) {
+    return {L.rowBytes, L.NT, L.nItems, L.nTilesKept, L.outLds, L.outRuns, L.dynBatches};
+}
+inline RbLaunchKnobs rb_launch_knobs(const Plan& p) {
+    return {p.stage_nt, p.stage_nt_auto, p.late_b, p.pair_min_items, p.diag};
+}
+// a rule's verdict as a status: its message goes to bsmr_last_error
+inline int report(const Verdict& v) {
+    if (v.code != BSMR_OK) set_error(v.msg);
+    return v.code;
+}
 
 }  // namespace bsmr
 

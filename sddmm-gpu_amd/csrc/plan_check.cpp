@@ -36,10 +36,6 @@
 #include "plan.hpp"
 
 namespace bsmr {
-
-bool sddmm_uses_dense(const Plan& p, u32 K, int dtype);  // sddmm.hip
-bool sddmm_uses_ptile(const Plan& p, u32 K, int dtype);  // sddmm.hip
-
 namespace {
 
 constexpr u32 CM22 = (1u << 22) - 1;
@@ -292,34 +288,32 @@ public:
             *ok = fail("Error! The launch layout cannot be checked without a valid row reordering");
             return BSMR_OK;
         }
-        if (sddmm_uses_dense(p_, K, dtype)) {
-            {
-                std::lock_guard<std::mutex> g(p_.layout_mu);
-                if (!p_.dense.built) BSMR_CHECK(p_.build_dense_layout());
-            }
-            *ok = dense_layout();
-            return BSMR_OK;
-        }
-        if (sddmm_uses_ptile(p_, K, dtype)) {
-            {
-                std::lock_guard<std::mutex> g(p_.layout_mu);
-                if (!p_.ptile.built || p_.ptile.tpi != p_.ptile_tpi) BSMR_CHECK(p_.build_ptile_layout(p_.ptile_tpi));
-            }
-            bool r = false;
-            BSMR_CHECK(ptile_layout(&r));
-            *ok = r;
-            return BSMR_OK;
-        }
-        const Plan::RowBlockLayout* L = nullptr;
-        BSMR_CHECK(whole_rb_layout(p_, K, dtype, &L));
-        if (L) {
-            bool r = false;
-            BSMR_CHECK(rb_layout(*L, &r));
-            *ok = r;
-            return BSMR_OK;
-        }
         bool r = false;
-        BSMR_CHECK(cm_layout(&r));
+        switch (choose_launch(p_, K, dtype).kind) {
+            case Launch::Ptile: {
+                {
+                    std::lock_guard<std::mutex> g(p_.layout_mu);
+                    if (!p_.ptile_ready()) BSMR_CHECK(p_.build_ptile_layout(p_.ptile_tpi));
+                }
+                BSMR_CHECK(ptile_layout(&r));
+                break;
+            }
+            case Launch::Dense: {
+                {
+                    std::lock_guard<std::mutex> g(p_.layout_mu);
+                    if (!p_.dense.built) BSMR_CHECK(p_.build_dense_layout());
+                }
+                r = dense_layout();
+                break;
+            }
+            case Launch::RowBlock: {
+                const Plan::RowBlockLayout* L = nullptr;
+                BSMR_CHECK(whole_rb_layout(p_, K, dtype, &L));
+                BSMR_CHECK(rb_layout(*L, &r));
+                break;
+            }
+            default: BSMR_CHECK(cm_layout(&r));  // both column-major launches read the same lists
+        }
         *ok = r;
         return BSMR_OK;
     }

@@ -615,7 +615,7 @@ template <int RBY>
 __device__ __forceinline__ void load_bcol(const RbArgs& a, const u32 col, const u32 sub,
                                           const u32 (&rot)[RowGeom<RBY>::NC],
                                           f32x4 (&bv)[RowGeom<RBY>::NC]) {
-    // B < 4 GiB on this path (rb_slot); BSMR_DIAG & 64 (ablation only): every piece reads
+    // B < 4 GiB on this path (launch_select.cpp); BSMR_DIAG & 64 (ablation only): every piece reads
     // column 0, so the B gathers hit L2
     const u32 bb = ((a.diag & 64) ? 0u : col) * RBY + 16 * sub;
 #pragma unroll
@@ -1452,25 +1452,12 @@ KernelFn pick_kernel(u32 K) {
     return pick_k<4, PANELS>(K);
 }
 
-// K / dtype rules of every launch (and of bsmr_plan_prepare, which reports under its own name)
-int validate_kd(const char* who, u32 K, int dtype) {
-    if (K == 0 || K % 16 != 0) {
-        set_error(std::string(who) + ": K must be a positive multiple of 16");
-        return BSMR_ERR_UNSUPPORTED;
-    }
-    if (dtype != BSMR_F32 && dtype != BSMR_F16 && dtype != BSMR_BF16) {
-        set_error(std::string(who) + ": dtype must be BSMR_F32, BSMR_F16 or BSMR_BF16");
-        return BSMR_ERR_UNSUPPORTED;
-    }
-    return BSMR_OK;
-}
-
 int validate(const void* dA, const void* dB, u32 K, int dtype, const float* dP) {
     if (!dA || !dB || !dP) {
         set_error("bsmr_sddmm: null device pointer");
         return BSMR_ERR_INVALID;
     }
-    return validate_kd("bsmr_sddmm", K, dtype);
+    return report(validate_kd("bsmr_sddmm", K, dtype));
 }
 
 SddmmArgs make_args(const Plan& p, const void* dA, const void* dB, u32 K, float* dP) {
@@ -1495,54 +1482,6 @@ SddmmArgs make_args(const Plan& p, const void* dA, const void* dB, u32 K, float*
     a.sparseCol = p.sparseColIdx.data();
     a.diag = p.diag;
     return a;
-}
-
-// (K, dtype) -> row-block layout slot by row bytes (0..3: 256 B .. 2 KiB); -1: the column-major
-// path
-int rb_slot(const Plan& p, u32 K, int dtype) {
-    if (p.N > (1u << 22) || !p.use_rowblock) return -1;
-    // tile-dominated plans (e.g. 16x16 block masks): one tile per wave with A from L2 beats
-    // staging row blocks (C5 block mask: 8.9 vs 11.1 us); row blocks pay off once the residual
-    // carries a quarter of the work (a tile ~ 16 entries)
-    if (!p.force_rowblock && static_cast<u64>(p.nres) * 4 < static_cast<u64>(p.numDenseTiles) * 16)
-        return -1;
-    const u32 rby = K * (dtype == BSMR_F32 ? 4u : 2u);
-    // the row-block kernel addresses B with 32-bit byte offsets (load_bcol): B < 4 GiB
-    if (static_cast<u64>(p.N) * rby >= (1ull << 32)) return -1;
-    return rby == 128 ? 0 : rby == 256 ? 1 : rby == 512 ? 2 : rby == 1024 ? 3 : rby == 2048 ? 4 : -1;
-}
-
-// fp16/bf16 patterns dense enough for whole MFMA tiles (sddmm_dense.hip)
-bool use_dense(const Plan& p, u32 K, int dtype) {
-    // layout auto only (BSMR_LAYOUT_ROWBLOCK / _COLMAJOR force those launches); bsmr_sddmm asks
-    // use_ptile first (tile-dominated fp16/bf16 plans, K in {64..512}: C5 block 7.8 -> 5.6 us)
-    // tile-dominated plans (16 x 16 block masks) keep the column-major tile launch below K = 512:
-    // a 128 x 128 tile's fixed prologue and epilogue only pay off over long K (C5 block mask,
-    // bf16: dense 8.2 vs 8.9 us at K = 512, 5.95 vs 5.35 at 256, 4.7 vs 3.8 at 128;
-    // profiles/r02c/dense_blockmask_ab.txt)
-    if (K < 512 && static_cast<u64>(p.nres) * 4 < static_cast<u64>(p.numDenseTiles) * 16) return false;
-    return p.use_rowblock && !p.force_rowblock && dtype != BSMR_F32 && K % 64 == 0 &&
-           static_cast<double>(p.nnz) >= static_cast<double>(p.dense_min) * p.M * static_cast<double>(p.N);
-}
-
-// tile-dominated fp16/bf16 plans (16 x 16 block masks: residual under a quarter of the work) with
-// K in {64, 128, 256, 512}: the panel-grouped tile launch (sddmm_half.hip k_sddmm_ptile), every
-// BSMR tile on MFMA with the panel's A rows staged once per item (BSMR_PTILE = 1: whenever the
-// dtype and K allow, also beside a large residual; 0: never)
-bool use_ptile(const Plan& p, u32 K, int dtype) {
-    if (dtype == BSMR_F32 || p.ptile_mode == 0 || !p.use_rowblock || p.force_rowblock) return false;
-    if ((K != 64 && K != 128 && K != 256 && K != 512) || p.numDenseTiles == 0) return false;
-    return p.ptile_mode == 1 ||
-           static_cast<u64>(p.nres) * 4 < static_cast<u64>(p.numDenseTiles) * 16;
-}
-
-// the launch bsmr_sddmm / bsmr_sddmm_batch runs for (K, dtype)
-enum class Launch { Ptile, Dense, RowBlock, Half, ColMajor };
-Launch launch_kind(const Plan& p, u32 K, int dtype) {
-    if (use_ptile(p, K, dtype)) return Launch::Ptile;
-    if (use_dense(p, K, dtype)) return Launch::Dense;
-    if (rb_slot(p, K, dtype) >= 0) return Launch::RowBlock;
-    return dtype != BSMR_F32 ? Launch::Half : Launch::ColMajor;
 }
 
 // the row-block layout of panels [pa, pb) for slot's row size. A cached layout is returned as it
@@ -1583,6 +1522,7 @@ int get_iota(const Plan& p, const LaunchSite* at = nullptr) {
 int launch_rb(const Plan& p, const Plan::RowBlockLayout& L, const void* dA, const void* dB,
               float* dP, int dtype, u32 mode, hipStream_t s, u32 nb = 1, bool local = false) {
     if (L.nItems == 0) return BSMR_OK;
+    const RbForm f = rb_form(rb_layout_facts(L), rb_launch_knobs(p), mode);
     RbArgs a{};
     a.A = static_cast<const char*>(dA);
     if (local)
@@ -1606,25 +1546,14 @@ int launch_rb(const Plan& p, const Plan::RowBlockLayout& L, const void* dA, cons
     a.out = L.out.data();
     a.outLds = (mode & 2) ? L.outLds : 0u;  // (dense-only profiling launches write no slots)
     a.outPacked = L.outPacked ? 1u : 0u;
-    a.stageNt = p.stage_nt == 1 || (p.stage_nt == -1 && L.outLds != 0 && p.stage_nt_auto);
-    a.lateB = p.late_b != 0;
-    // the image's blocks only (BSMR_DIAG & 2097152, A/B only: every block of the launch's LDS but
-    // the last, which holds the piece-batch counter — the filler past the image reading row 0, as
-    // before round 5)
-    a.stageBlocks = (p.diag & 2097152u) ? (L.NT == 1024 ? 159u : 79u)
-                                        : (L.RB * L.rowBytes + 1023) / 1024;
+    a.stageNt = f.stageNt;
+    a.lateB = f.lateB;
+    a.stageBlocks = f.stageBlocks ? f.stageBlocks : (L.RB * L.rowBytes + 1023) / 1024;
     a.sortedPos = L.sortedPos.data();
     a.itemEnt = L.itemEnt.data();
     a.runs = L.outRuns ? L.runs.data() : nullptr;
     a.itemRuns = L.outRuns ? L.itemRuns.data() : nullptr;
-    // pairs (BSMR_DIAG & 16384 off): staged output by runs, rows of >= 512 bytes, at least 4096
-    // items (16 rounds of the chip's workgroup slots), an even number of list positions per XCD;
-    // not under the profiling ablations (trace, staging only, B in L2, no stores). A pair is two
-    // items long, so short lists lose to the tail: mycielskian15 K = 64 / 128 (832 / 728 items)
-    // 56.9 / 74.6 us paired against 50.1 / 66.5 unpaired, mycielskian16 K = 64 114.6 against
-    // 108.9; C4 (8-30 K items) gains (x0.5 1.029 -> 0.984 ms), C3, mycielskian16 K = 128 and
-    // 1-2 KiB rows are neutral (profiles/r04zt, r04zw)
-    a.pairs = mode == 3 && rb_uses_pairs(p, L) ? 1u : 0u;
+    a.pairs = f.pairs;
     a.tilePanel = p.denseItems.data();
     a.tileIds = L.tileIds.data();
     a.denseCols = p.denseCols.data();
@@ -1639,11 +1568,7 @@ int launch_rb(const Plan& p, const Plan::RowBlockLayout& L, const void* dA, cons
     a.bB = static_cast<unsigned long long>(L.cols ? p.M : p.N) * L.rowBytes;
     a.bP = p.nnz;
     void (*fn)(RbArgs) = nullptr;
-    // the LITE single-item kernel: the whole launch (mode 3), no kept tiles, direct stores, default
-    // staging policy, late B, no trace or ablation bits (BSMR_DIAG & 33554432 keeps the full form
-    // for A/B)
-    const bool lite = mode == 3 && L.nTilesKept == 0 && !a.outLds && !a.stageNt && a.lateB && p.diag == 0;
-#define BSMR_RB(DT, RBY) pick_rb<DT, RBY>(L.NT, a.pairs != 0, L.dynBatches, lite)
+#define BSMR_RB(DT, RBY) pick_rb<DT, RBY>(f.NT, f.pairs, f.dyn, f.lite)
 #define BSMR_RB2(DT)                                                                   \
     (L.rowBytes == 128    ? BSMR_RB(DT, 128)                                              \
      : L.rowBytes == 256  ? BSMR_RB(DT, 256)                                              \
@@ -1657,10 +1582,7 @@ int launch_rb(const Plan& p, const Plan::RowBlockLayout& L, const void* dA, cons
     }
 #undef BSMR_RB2
 #undef BSMR_RB
-    // the workgroup's LDS: 160 / 80 KiB (the image, the staged-output slots, the batch counter)
-    const u32 grid = a.pairs ? L.nItems / 2 : L.nItems;
-    hipLaunchKernelGGL(fn, dim3(grid, nb), dim3(L.NT),
-                       (L.NT == 1024 ? 160 : 80) * 1024, s, a);
+    hipLaunchKernelGGL(fn, dim3(f.grid, nb), dim3(f.NT), f.ldsBytes, s, a);
     BSMR_HIP(hipGetLastError());
     return BSMR_OK;
 }
@@ -1711,36 +1633,17 @@ int lazy_build_guard(const LaunchSite& at) {
     return BSMR_ERR_NOT_PREPARED;
 }
 
-// pairs (BSMR_DIAG & 16384 off): staged output by runs, rows of >= 512 bytes, at least
-// pair_min_items (4096: 16 rounds of the chip's workgroup slots) items, an even number of list
-// positions per XCD, no kept MFMA tile; not under the profiling ablations (trace, staging only, B
-// in L2, no stores) nor nt staging / early B loads
-bool rb_uses_pairs(const Plan& p, const Plan::RowBlockLayout& L) {
-    const bool stageNt = p.stage_nt == 1 || (p.stage_nt == -1 && L.outLds != 0 && p.stage_nt_auto);
-    return L.outRuns && L.outLds && L.rowBytes >= 512 && L.nItems >= p.pair_min_items &&
-           L.nTilesKept == 0 && L.nItems % (2 * XCD_BUCKETS) == 0 && !stageNt && p.late_b != 0 &&
-           !(p.diag & (8u | 32u | 64u | 128u | 16384u));
-}
-
-// the K / dtype rules above for the launches of other units (spmm.hip)
-int launch_validate_kd(const char* who, u32 K, int dtype) { return validate_kd(who, K, dtype); }
-// whether bsmr_sddmm runs the dense-sampled launch for (K, dtype) (plan_check.cpp)
-bool sddmm_uses_dense(const Plan& p, u32 K, int dtype) { return use_dense(p, K, dtype); }
-// whether bsmr_sddmm runs the panel-grouped tile launch for (K, dtype) (plan_check.cpp, stats)
-bool sddmm_uses_ptile(const Plan& p, u32 K, int dtype) { return use_ptile(p, K, dtype); }
-
 // the whole plan's row-block layout for (K, dtype), built on first use; *out = null when that
 // (K, dtype) runs the column-major launch
 int whole_rb_layout(const Plan& p, u32 K, int dtype, const Plan::RowBlockLayout** out,
                     bool reordered) {
     *out = nullptr;
-    const int slot = rb_slot(p, K, dtype);
-    if (slot < 0 || use_ptile(p, K, dtype)) return BSMR_OK;
+    const LaunchChoice c = choose_launch(p, K, dtype);
+    if (c.slot < 0 || c.kind == Launch::Ptile) return BSMR_OK;
     std::shared_ptr<const Plan::RowBlockLayout> L;  // the whole plan's: a plan member
-    BSMR_CHECK(get_rb_layout(p, slot, dtype, 0, p.P, &L));
+    BSMR_CHECK(get_rb_layout(p, c.slot, dtype, 0, p.P, &L));
     *out = L.get();
-    // reordered: the reordered-row layout (always built first; panel shards cut its row blocks)
-    if (reordered && (L->orig || L->cols)) *out = &p.rbl[slot + (dtype != BSMR_F32 ? Plan::N_RB_SIZES : 0)];
+    if (reordered && (L->orig || L->cols)) *out = &p.rb_reordered(c.slot, dtype);
     return BSMR_OK;
 }
 
@@ -1765,34 +1668,29 @@ static int sddmm_batch(const char* who, const bsmr_plan* plan, uint32_t num_batc
     const hipStream_t s = static_cast<hipStream_t>(stream);
     const size_t es = dtype == BSMR_F32 ? 4 : 2;
     const LaunchSite at{s, who, "bsmr_plan_prepare", K, dtype};
-    const Launch kind = launch_kind(p, K, dtype);
+    const LaunchChoice c = choose_launch(p, K, dtype);
     for (u32 b0 = 0; b0 < num_batch; b0 += 65535u) {
         const u32 nb = std::min<u32>(num_batch - b0, 65535u);
         const char* A = static_cast<const char*>(dA) + es * b0 * static_cast<size_t>(p.M) * K;
         const char* B = static_cast<const char*>(dB) + es * b0 * static_cast<size_t>(p.N) * K;
         float* P = dP + static_cast<size_t>(b0) * p.nnz;
-        if (kind == Launch::Ptile) {
-            BSMR_CHECK(launch_ptile(p, A, B, K, dtype, P, 3, s, nb, &at));
-            continue;
+        switch (c.kind) {
+            case Launch::Ptile: BSMR_CHECK(launch_ptile(p, A, B, K, dtype, P, 3, s, nb, &at)); break;
+            case Launch::Dense: BSMR_CHECK(launch_dense(p, A, B, K, dtype, P, s, nb, &at)); break;
+            case Launch::RowBlock: {
+                std::shared_ptr<const Plan::RowBlockLayout> L;
+                BSMR_CHECK(get_rb_layout(p, c.slot, dtype, 0, p.P, &L, &at));
+                BSMR_CHECK(launch_rb(p, *L, A, B, P, dtype, 3, s, nb));
+                break;
+            }
+            case Launch::Half: BSMR_CHECK(launch_half(p, A, B, K, dtype, P, 3, s, nb)); break;
+            case Launch::ColMajor: {
+                SddmmArgs a = make_args(p, A, B, K, P);
+                a.nd = p.nDenseItems;
+                a.nslots = p.nSlots;
+                BSMR_CHECK(launch_full(p, a, s, nb));
+            }
         }
-        if (kind == Launch::Dense) {
-            BSMR_CHECK(launch_dense(p, A, B, K, dtype, P, s, nb, &at));
-            continue;
-        }
-        if (kind == Launch::RowBlock) {
-            std::shared_ptr<const Plan::RowBlockLayout> L;
-            BSMR_CHECK(get_rb_layout(p, rb_slot(p, K, dtype), dtype, 0, p.P, &L, &at));
-            BSMR_CHECK(launch_rb(p, *L, A, B, P, dtype, 3, s, nb));
-            continue;
-        }
-        if (kind == Launch::Half) {
-            BSMR_CHECK(launch_half(p, A, B, K, dtype, P, 3, s, nb));
-            continue;
-        }
-        SddmmArgs a = make_args(p, A, B, K, P);
-        a.nd = p.nDenseItems;
-        a.nslots = p.nSlots;
-        BSMR_CHECK(launch_full(p, a, s, nb));
     }
     return BSMR_OK;
 }
@@ -1807,6 +1705,13 @@ extern "C" int bsmr_sddmm(const bsmr_plan* plan, const void* dA, const void* dB,
     return sddmm_batch("bsmr_sddmm", plan, 1, dA, dB, K, dtype, dP, stream);
 }
 
+// the plan's choice for (K, dtype) and the panel-range rules, for the four panel entry points
+static int panel_choice(const char* who, const Plan& p, u32 K, int dtype, u32 p0, u32 p1, bool local,
+                        LaunchChoice* c) {
+    *c = choose_launch(p, K, dtype);
+    return report(check_panel_range(who, p0, p1, p.P, c->slot, dtype, local));
+}
+
 extern "C" int bsmr_sddmm_panels(const bsmr_plan* plan, const void* dA, const void* dB,
                                  uint32_t K, int dtype, float* dP, uint32_t p0, uint32_t p1,
                                  void* stream) {
@@ -1816,24 +1721,16 @@ extern "C" int bsmr_sddmm_panels(const bsmr_plan* plan, const void* dA, const vo
     }
     const Plan& p = plan->p;
     BSMR_CHECK(validate(dA, dB, K, dtype, dP));
-    if (p0 > p1 || p1 > p.P) {
-        set_error("bsmr_sddmm_panels: bad panel range");
-        return BSMR_ERR_INVALID;
-    }
+    LaunchChoice c;
+    BSMR_CHECK(panel_choice("bsmr_sddmm_panels", p, K, dtype, p0, p1, false, &c));
     if (p0 == p1) return BSMR_OK;
     // the row-block kernel over the range's own layout (same kernel as the whole plan)
-    const int slot = rb_slot(p, K, dtype);
-    if (slot >= 0) {
+    if (c.slot >= 0) {
         const LaunchSite at{static_cast<hipStream_t>(stream), "bsmr_sddmm_panels",
                             "bsmr_plan_prepare_panels", K, dtype};
         std::shared_ptr<const Plan::RowBlockLayout> L;  // held until the launch is enqueued
-        BSMR_CHECK(get_rb_layout(p, slot, dtype, p0, p1, &L, &at));
+        BSMR_CHECK(get_rb_layout(p, c.slot, dtype, p0, p1, &L, &at));
         return launch_rb(p, *L, dA, dB, dP, dtype, 3, at.s);
-    }
-    if (dtype != BSMR_F32) {
-        set_error("bsmr_sddmm_panels: fp16/bf16 panel ranges need the row-block layout "
-                  "(half K in 128..1024)");
-        return BSMR_ERR_UNSUPPORTED;
     }
     // items are stored panel-major: ceil(tiles_q / TILES_PER_ITEM) dense and
     // ceil(nres_q / RES_PER_ITEM) residual items per panel q
@@ -1867,26 +1764,18 @@ extern "C" int bsmr_sddmm_panels_local(const bsmr_plan* plan, const void* dA_loc
     }
     const Plan& p = plan->p;
     BSMR_CHECK(validate(dA_local, dB, K, dtype, dP));
-    if (p0 > p1 || p1 > p.P) {
-        set_error("bsmr_sddmm_panels_local: bad panel range");
-        return BSMR_ERR_INVALID;
-    }
+    LaunchChoice c;
+    BSMR_CHECK(panel_choice("bsmr_sddmm_panels_local", p, K, dtype, p0, p1, true, &c));
     if (p0 == p1) return BSMR_OK;
-    const int slot = rb_slot(p, K, dtype);
-    if (slot < 0) {
-        set_error("bsmr_sddmm_panels_local: needs the row-block launch (rows of 128 B .. 2 KiB)");
-        return BSMR_ERR_UNSUPPORTED;
-    }
     const LaunchSite at{static_cast<hipStream_t>(stream), "bsmr_sddmm_panels_local",
                         "bsmr_plan_prepare_panels", K, dtype};
     BSMR_CHECK(get_iota(p, &at));
     std::shared_ptr<const Plan::RowBlockLayout> L;  // held until the launch is enqueued
-    BSMR_CHECK(get_rb_layout(p, slot, dtype, p0, p1, &L, &at));
+    BSMR_CHECK(get_rb_layout(p, c.slot, dtype, p0, p1, &L, &at));
     if (L->orig || L->cols)  // the whole range may have picked original-order row blocks or
-                             // column blocks: use the reordered layout (always built first), whose
-                             // rows follow the local A
-        L = std::shared_ptr<const Plan::RowBlockLayout>(
-            std::shared_ptr<void>(), &p.rbl[slot + (dtype != BSMR_F32 ? Plan::N_RB_SIZES : 0)]);
+                             // column blocks: use the reordered layout, whose rows follow the local A
+        L = std::shared_ptr<const Plan::RowBlockLayout>(std::shared_ptr<void>(),
+                                                        &p.rb_reordered(c.slot, dtype));
     return launch_rb(p, *L, dA_local, dB, dP, dtype, 3, at.s, 1, true);
 }
 
@@ -1897,7 +1786,7 @@ static int prepare_args(const char* who, const bsmr_plan* plan, uint32_t K, int 
         set_error(std::string(who) + ": null plan");
         return BSMR_ERR_INVALID;
     }
-    return validate_kd(who, K, dtype);
+    return report(validate_kd(who, K, dtype));
 }
 
 // the panel-range checks of bsmr_sddmm_panels / _panels_local; *slot = -1 when there is nothing
@@ -1906,36 +1795,18 @@ static int prepare_panels_args(const char* who, const bsmr_plan* plan, uint32_t 
                                uint32_t p0, uint32_t p1, int local, int* slot) {
     *slot = -1;
     BSMR_CHECK(prepare_args(who, plan, K, dtype));
-    const Plan& p = plan->p;
-    if (p0 > p1 || p1 > p.P) {
-        set_error(std::string(who) + ": bad panel range");
-        return BSMR_ERR_INVALID;
-    }
-    if (p0 == p1) return BSMR_OK;
-    *slot = rb_slot(p, K, dtype);
-    if (*slot < 0 && local) {
-        set_error(std::string(who) + ": bsmr_sddmm_panels_local needs the row-block launch (rows of "
-                                     "128 B .. 2 KiB)");
-        return BSMR_ERR_UNSUPPORTED;
-    }
-    if (*slot < 0 && dtype != BSMR_F32) {
-        set_error(std::string(who) + ": fp16/bf16 panel ranges need the row-block layout (half K in "
-                                     "128..1024)");
-        return BSMR_ERR_UNSUPPORTED;
-    }
+    LaunchChoice c;
+    BSMR_CHECK(panel_choice(who, plan->p, K, dtype, p0, p1, local != 0, &c));
+    if (p0 != p1) *slot = c.slot;
     return BSMR_OK;
-}
-
-static int half_colmajor_k(const char* who, u32 K) {  // launch_half's rule
-    if (K % 32 == 0) return BSMR_OK;
-    set_error(std::string(who) + ": fp16/bf16 inputs need K to be a positive multiple of 32");
-    return BSMR_ERR_UNSUPPORTED;
 }
 
 extern "C" int bsmr_plan_prepare(const bsmr_plan* plan, uint32_t K, int dtype) {
     BSMR_CHECK(prepare_args("bsmr_plan_prepare", plan, K, dtype));
     const Plan& p = plan->p;
-    switch (launch_kind(p, K, dtype)) {
+    const LaunchChoice c = choose_launch(p, K, dtype);
+    BSMR_CHECK(report(validate_launch_k("bsmr_plan_prepare", c.kind, K)));
+    switch (c.kind) {
         case Launch::Ptile: {
             std::lock_guard<std::mutex> g(p.layout_mu);
             if (!p.ptile_ready()) BSMR_CHECK(p.build_ptile_layout(p.ptile_tpi));
@@ -1948,23 +1819,23 @@ extern "C" int bsmr_plan_prepare(const bsmr_plan* plan, uint32_t K, int dtype) {
         }
         case Launch::RowBlock: {
             std::shared_ptr<const Plan::RowBlockLayout> L;
-            return get_rb_layout(p, rb_slot(p, K, dtype), dtype, 0, p.P, &L);
+            return get_rb_layout(p, c.slot, dtype, 0, p.P, &L);
         }
-        case Launch::Half: return half_colmajor_k("bsmr_plan_prepare", K);
-        default: return BSMR_OK;
+        default: return BSMR_OK;  // the column-major lists are the plan's own
     }
 }
 
 extern "C" int bsmr_plan_prepared(const bsmr_plan* plan, uint32_t K, int dtype) {
     if (prepare_args("bsmr_plan_prepared", plan, K, dtype) != BSMR_OK) return 0;
     const Plan& p = plan->p;
-    const Launch kind = launch_kind(p, K, dtype);
-    if (kind == Launch::Half) return half_colmajor_k("bsmr_plan_prepared", K) == BSMR_OK;
-    if (kind == Launch::ColMajor) return 1;
+    const LaunchChoice c = choose_launch(p, K, dtype);
+    const Launch kind = c.kind;
+    if (report(validate_launch_k("bsmr_plan_prepared", kind, K)) != BSMR_OK) return 0;
+    if (kind == Launch::Half || kind == Launch::ColMajor) return 1;
     std::lock_guard<std::mutex> g(p.layout_mu);
     if (kind == Launch::Ptile) return p.ptile_ready();
     if (kind == Launch::Dense) return p.dense.built;
-    return p.rowblock_ready(128u << rb_slot(p, K, dtype), dtype != BSMR_F32, 0, p.P) != nullptr;
+    return p.rowblock_ready(c.rowBytes, dtype != BSMR_F32, 0, p.P) != nullptr;
 }
 
 extern "C" int bsmr_plan_prepare_panels(const bsmr_plan* plan, uint32_t K, int dtype, uint32_t p0,
@@ -2017,9 +1888,9 @@ extern "C" int bsmr_sddmm_profile(const bsmr_plan* plan, const void* dA, const v
     } evs;
     hipEvent_t* ev = evs.e;
     for (int i = 0; i < 4; ++i) BSMR_HIP(hipEventCreate(&ev[i]));
-    const int slot = rb_slot(p, K, dtype);
+    const LaunchChoice c = choose_launch(p, K, dtype);
     std::shared_ptr<const Plan::RowBlockLayout> L;
-    if (slot >= 0 && !use_ptile(p, K, dtype)) BSMR_CHECK(get_rb_layout(p, slot, dtype, 0, p.P, &L));
+    if (c.kind == Launch::RowBlock) BSMR_CHECK(get_rb_layout(p, c.slot, dtype, 0, p.P, &L));
     SddmmArgs full = make_args(p, dA, dB, K, dP);
     full.nd = p.nDenseItems;
     full.nslots = p.nSlots;
@@ -2027,13 +1898,14 @@ extern "C" int bsmr_sddmm_profile(const bsmr_plan* plan, const void* dA, const v
     dense.nslots = 0;
     SddmmArgs res = full;
     res.nd = 0;
-    const bool ptile = use_ptile(p, K, dtype), dense_all = !ptile && use_dense(p, K, dtype);
     auto run = [&](u32 mode) -> int {
-        if (ptile) return launch_ptile(p, dA, dB, K, dtype, dP, mode, s);
-        if (dense_all) return launch_dense(p, dA, dB, K, dtype, dP, s);  // no dense/residual split
-        if (L) return launch_rb(p, *L, dA, dB, dP, dtype, mode, s);
-        if (dtype != BSMR_F32) return launch_half(p, dA, dB, K, dtype, dP, mode, s);
-        return launch_full(p, mode == 1 ? dense : mode == 2 ? res : full, s);
+        switch (c.kind) {
+            case Launch::Ptile: return launch_ptile(p, dA, dB, K, dtype, dP, mode, s);
+            case Launch::Dense: return launch_dense(p, dA, dB, K, dtype, dP, s);  // no dense/residual split
+            case Launch::RowBlock: return launch_rb(p, *L, dA, dB, dP, dtype, mode, s);
+            case Launch::Half: return launch_half(p, dA, dB, K, dtype, dP, mode, s);
+            default: return launch_full(p, mode == 1 ? dense : mode == 2 ? res : full, s);
+        }
     };
     BSMR_HIP(hipEventRecord(ev[0], s));
     for (int i = 0; i < iters; ++i) BSMR_CHECK(run(1));

@@ -400,11 +400,8 @@ int Plan::build_ptile_layout(u32 tpi) const {
 // tiles, 2 residual slots, 3 both)
 int launch_ptile(const Plan& p, const void* dA, const void* dB, u32 K, int dtype, float* dP,
                  u32 mode, hipStream_t s, u32 nb, const LaunchSite* at) {
+    BSMR_CHECK(report(validate_launch_k("bsmr_sddmm", Launch::Ptile, K)));
     const u32 NK = K / 32;
-    if (K % 32 != 0 || (NK != 2 && NK != 4 && NK != 8 && NK != 16)) {
-        set_error("bsmr_sddmm: the panel-tile launch needs K in {64, 128, 256, 512}");
-        return BSMR_ERR_UNSUPPORTED;
-    }
     {
         std::lock_guard<std::mutex> g(p.layout_mu);
         if (!p.ptile_ready()) {
@@ -457,10 +454,7 @@ int launch_ptile(const Plan& p, const void* dA, const void* dB, u32 K, int dtype
 // dtype: BSMR_F16 or BSMR_BF16; K a positive multiple of 32. mode: 1 dense, 2 residual, 3 both
 int launch_half(const Plan& p, const void* dA, const void* dB, u32 K, int dtype, float* dP,
                 u32 mode, hipStream_t s, u32 nb) {
-    if (K == 0 || K % 32 != 0) {
-        set_error("bsmr_sddmm: fp16/bf16 inputs need K to be a positive multiple of 32");
-        return BSMR_ERR_UNSUPPORTED;
-    }
+    BSMR_CHECK(report(validate_launch_k("bsmr_sddmm", Launch::Half, K)));
     HalfArgs a{};
     a.A = static_cast<const uint16_t*>(dA);
     a.B = static_cast<const uint16_t*>(dB);

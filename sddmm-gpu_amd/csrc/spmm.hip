@@ -18,10 +18,6 @@
 #include "spmm_schedule.hpp"
 
 namespace bsmr {
-
-// sddmm.hip: the K / dtype rules shared by every launch
-int launch_validate_kd(const char* who, u32 K, int dtype);
-
 namespace {
 
 // Both are macros so that an A/B build can override them (-D...). Measured, dA / dB:
@@ -314,7 +310,7 @@ int launch_side(const bsmr_plan* plan, int side, const float* dV, const void* dX
         set_error(std::string(who) + ": null device pointer");
         return BSMR_ERR_INVALID;
     }
-    BSMR_CHECK(launch_validate_kd(who, K, dtype));
+    BSMR_CHECK(report(validate_kd(who, K, dtype)));
     const Plan& p = plan->p;
     const hipStream_t s = static_cast<hipStream_t>(stream);
     const Plan::SpmmSide& S = p.spmm[side - 1];
@@ -385,7 +381,7 @@ static int spmm_prepare_args(const char* who, const bsmr_plan* plan, uint32_t K,
         set_error(std::string(who) + ": sides must be 1 (rows), 2 (columns) or 3 (both)");
         return BSMR_ERR_INVALID;
     }
-    return launch_validate_kd(who, K, BSMR_F32);
+    return report(validate_kd(who, K, BSMR_F32));
 }
 
 extern "C" int bsmr_plan_prepare_spmm(const bsmr_plan* plan, uint32_t K, int sides, uint32_t chunk) {

@@ -105,17 +105,44 @@ def rb_geometry(plan, K, dtype):
     return dict(rb=int(buf[0]), nt=int(buf[1]), items=int(buf[2]), row_bytes=int(buf[3]))
 
 
+LAUNCH_KINDS = ("ptile", "dense", "rowblock", "half", "colmajor")  # csrc/launch_select.hpp Launch
+RB_FORM = ("stageNt", "lateB", "pairs", "lite", "dyn", "NT", "grid", "ldsBytes", "stageBlocks")
+
+
+def plan_launch(plan, K, dtype):
+    """What bsmr_sddmm runs on `plan` for (K, dtype), as the library decides it (the debug export
+    bsmr_debug_plan_launch, not in the header): dict(kind=a sddmm_cases kind, slot=the row-block
+    slot or -1, row_bytes) and, for the row-block kind, the kernel form of the whole launch: lite,
+    pairs, dyn (booleans), NT, grid, ... (RB_FORM). Builds the row-block layout if no launch has."""
+    import ctypes as C
+
+    import bsmr
+    f = bsmr.lib().bsmr_debug_plan_launch
+    f.argtypes = [C.c_void_p, C.c_uint32, C.c_int, np.ctypeslib.ndpointer(np.uint32, flags="C_CONTIGUOUS")]
+    out = np.zeros(12, np.uint32)
+    assert f(plan.h, K, dtype, out) == 0, bsmr.lib().bsmr_last_error()
+    w = [int(x) for x in out]
+    d = dict(kind=LAUNCH_KINDS[w[0]], slot=w[1] - 1, row_bytes=w[2])
+    if d["kind"] == "rowblock":
+        d.update(zip(RB_FORM, w[3:]))
+        for k in RB_FORM[:5]:
+            d[k] = bool(d[k])
+    return d
+
+
 def path_evidence(case, plan):
     """Failures (strings) of a sddmm_cases.Case's evidence that its launch path ran, after the
-    launch: sddmm_cases.check_stats on the plan's stats and, for the row-block launch, its layout
-    geometry, for the panel-tile launch the plan's tile offsets and the device's CU count."""
+    launch: sddmm_cases.check_stats on the plan's stats, the library's own account of the launch
+    (plan_launch) and, for the row-block launch, its layout geometry, for the panel-tile launch the
+    plan's tile offsets and the device's CU count."""
     from sddmm_cases import check_stats
+    launch = plan_launch(plan, case.K, case.dtype)
     geom = None
     if case.kind == "rowblock":
         geom = rb_geometry(plan, case.K, case.dtype)
     elif case.kind == "ptile":
         cus = torch_cuda().cuda.get_device_properties(0).multi_processor_count
         geom = dict(block_offsets=plan.array("blockOffsets"), cus=int(cus))
-    bad = check_stats(case, plan.stats(), geom)
+    bad = check_stats(case, plan.stats(), launch, geom)
     shown = dict(geom, block_offsets="...") if geom and "block_offsets" in geom else geom
-    return [f"{b} (geometry {shown}, stats {plan.stats()})" for b in bad]
+    return [f"{b} (launch {launch}, geometry {shown}, stats {plan.stats()})" for b in bad]

@@ -21,7 +21,7 @@ from test_gpu_plan_check import LAYOUTS, WIDE, ZIPF
 FREE = 288 * 1024 ** 3
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden",
                       "mi355x_rb_layout_digests.json")
-NOT_ROWBLOCK = ("colmajor", "colmajor_half", "dense_sampled")
+NOT_ROWBLOCK = ("colmajor", "colmajor_half", "dense_sampled", "ptile_over_dense")
 # LAYOUTS rows whose plans are cases of the table below already (zipf/piece_balance,
 # wide_staged/piece_balance_k256)
 SAME_PLAN = ("piece_balance", "piece_balance_staged_1k")

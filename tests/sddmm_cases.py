@@ -26,10 +26,11 @@ Bound: |P - ref| <= min(2 K, 8 sqrt K) 2^-24 S + 1e-6 scale.
   The bound is derived, never widened from what a GPU shows; each GPU test prints its worst
   error / bound ratio (DESIGN.md §11.1 records them).
 
-CASES: one entry per kernel instantiation the dispatch can reach (csrc/sddmm.hip launch_kind,
-rb_slot, pick_kernel / pick_k, pick_rb, launch_rb; csrc/sddmm_half.hip launch_half, launch_ptile;
-csrc/sddmm_dense.hip launch_dense), on the smallest pattern of the suite that takes it, with the
-plan options that select the path and the Plan.stats() evidence that it ran (check_stats):
+CASES: one entry per kernel instantiation the dispatch can reach (csrc/launch_select.cpp
+choose_launch, rb_form; csrc/sddmm.hip pick_kernel / pick_k, pick_rb, launch_rb;
+csrc/sddmm_half.hip launch_half, launch_ptile; csrc/sddmm_dense.hip launch_dense), on the smallest
+pattern of the suite that takes it, with the plan options that select the path, the Plan.stats()
+evidence that it ran and the library's own account of the launch (check_stats):
 
   column-major fp32 (k_sddmm_f32<KT, G>; `colmajor`: no lazily built layout exists afterwards)
     G = 4, generic KT: K = 16, 48       G = 8, generic: K = 96       G = 8, KT = 32: K = 32
@@ -57,9 +58,13 @@ plan options that select the path and the Plan.stats() evidence that it ran (che
     the default equal runs (one tile each on block_mask(512, 16, 0.15); on the larger mask runs of
     two tiles, some over two panels); ptile = 1 on `zipf` (tiles and a residual in one launch)
 
-Not told apart by any evidence the library exposes: whether a row-block launch took the lite or the
-full kernel (it follows from out_staged and rb_tiles == 0, which is checked), and the panel-tile
-workgroup size (it follows from ptile_tpi). k_sddmm_dense's NS at four waves is always 2.
+The launch kind and, for a row-block launch, the kernel form (lite or full, single or pair, fixed
+phases or dynamic batches, threads per workgroup) are read from the library (the debug export
+bsmr_debug_plan_launch: the choose_launch and rb_form the launch itself goes through) and held to
+what the case names: the `rbx_lite_*` / `rbx_full_*` / `rbx_pair_*` cases by their names, every
+row-block case by the documented lite rule (no kept tile, direct stores, default staging). Not told
+apart by any evidence the library exposes: the panel-tile workgroup size (it follows from
+ptile_tpi). k_sddmm_dense's NS at four waves is always 2.
 
 bsmr_sddmm_panels reaches the row-block kernels (a range's own layout) and, for fp32 without a
 row-block slot, k_sddmm_panels_f32<KT, G>; sddmm_half.hip and sddmm_dense.hip have no panels
@@ -185,7 +190,7 @@ def reference(name, K, dtype, data, seed=0):
     return A, B, P, S
 
 
-# kind: the launch (csrc/sddmm.hip launch_kind): colmajor (fp32), half (column-major fp16/bf16),
+# kind: the launch (csrc/launch_select.hpp Launch): colmajor (fp32), half (column-major fp16/bf16),
 # rowblock, dense, ptile. proof: {evidence: value} checked by check_stats on top of the kind's own
 # evidence: rb_pairs / rb_batches / rb_orig_rows / rb_col_blocks (the stats bit of the row size set
 # or clear), rb_tiles (kept tiles > 0), rb_rows (rows per block), nt (threads per workgroup, from
@@ -371,10 +376,12 @@ def plan_kwargs(case):
     return dict(alpha=0.3, delta=0.3, free_mem_bytes=FREE, layout=case.layout, tuning=case.tuning)
 
 
-def check_stats(case, st, geom=None):
+def check_stats(case, st, launch, geom=None):
     """Failures (strings) of the evidence that `case` ran the path it names. st: Plan.stats() after
-    the launch; geom: gpu_util.rb_geometry of the launched layout (needed by an `nt` proof), or for
-    the panel-tile launch dict(block_offsets=the plan's blockOffsets, cus=the device's CU count)."""
+    the launch; launch: gpu_util.plan_launch, the library's account of the launch and of the
+    row-block kernel's form; geom: gpu_util.rb_geometry of the launched layout (needed by an `nt`
+    proof), or for the panel-tile launch dict(block_offsets=the plan's blockOffsets, cus=the
+    device's CU count)."""
     bad = []
 
     def want(cond, what):
@@ -387,6 +394,7 @@ def check_stats(case, st, geom=None):
         want(st["num_dense_tiles"] == 0, "pattern must have no dense tile")
     elif case.need == "no_residual":
         want(st["num_dense_tiles"] > 0 and st["num_residual"] == 0, "pattern must be tiles only")
+    want(launch["kind"] == case.kind, f"the library runs the {launch['kind']} launch, not {case.kind}")
     built = dict(rowblock=any(st["rb_items"]), dense=st["dense_sampled_tiles"] > 0,
                  ptile=st["ptile_items"] > 0)
     for kind, on in built.items():
@@ -429,4 +437,27 @@ def check_stats(case, st, geom=None):
         want(st["rb_rows"][slot] == proof["rb_rows"], f"rb_rows[{slot}] = {st['rb_rows'][slot]}")
     if "nt" in proof:
         want(geom is not None and geom["nt"] == proof["nt"], f"geometry {geom}: not {proof['nt']} threads")
+    # the kernel form the launch took (csrc/launch_select.cpp rb_form), against what the case names
+    if launch["kind"] != "rowblock":
+        return bad
+    want(launch["slot"] == slot, f"launch slot {launch['slot']}, not {slot}")
+    for f, key in (("rb_pairs", "pairs"), ("rb_batches", "dyn")):
+        want(launch[key] == bool(st[f] & bit), f"launch {key} = {launch[key]} against the stats bit")
+        if f in proof:
+            want(launch[key] == proof[f], f"launch {key} = {launch[key]}")
+    if geom is not None:
+        want(launch["NT"] == geom["nt"], f"launch NT = {launch['NT']} against the geometry's {geom['nt']}")
+    if "nt" in proof:
+        want(launch["NT"] == proof["nt"], f"launch NT = {launch['NT']}")
+    want(launch["grid"] == st["rb_items"][slot] // (2 if launch["pairs"] else 1),
+         f"launch grid {launch['grid']} of {st['rb_items'][slot]} items")
+    # lite: no kept tile, direct stores (the suite's outputs stay under the 8 MiB of the staged
+    # auto rule, so staged means out_staged = 1), default staging policy, late B, no diag bit
+    lite = (st["rb_tiles"][slot] == 0 and case.tuning.get("out_staged") != 1 and
+            not any(k in case.tuning for k in ("stage_nt", "late_b", "diag")))
+    if case.name.startswith("rbx_"):
+        named = case.name.startswith("rbx_lite")
+        want(lite == named, f"the case's knobs give lite = {lite}, its name {named}")
+    want(launch["lite"] == lite, f"launch lite = {launch['lite']}, the case names {lite}")
+    want(not (launch["lite"] and launch["pairs"]), "a launch both lite and paired")
     return bad

@@ -83,6 +83,9 @@ LAYOUTS = {
     "colmajor": (ZIPF, 128, F32, {"layout": "colmajor"}),
     "colmajor_half": (ZIPF, 128, F16, {"layout": "colmajor"}),
     "dense_sampled": (lambda: synth.uniform_mask(512, 0.1, 7), 512, BF16, {}),
+    # sddmm_cases' `blockmask`: tile-dominated and 16 % dense, so at K = 512 both the panel-tile and
+    # the dense-sampled rule hold; the launch asks the panel-tile rule first, and so must the check
+    "ptile_over_dense": (lambda: synth.block_mask(512, 16, 0.15, seed=11), 512, BF16, {}),
     # dynamic piece batches (rows of <= 512 B; waves take batches from an LDS counter): forced on
     # packed / staged / paired / half / 128- and 256-byte-row / original-order layouts, and on a
     # pattern of many single-entry pieces per item (several batches per wave)
@@ -126,6 +129,9 @@ def test_plan_and_launch_layout_pass(name, capfd):
         assert st["rb_batches"] != 0, st
     if name == "batches_pairs":
         assert st["rb_pairs"] & (1 << 2), st
+    if name == "ptile_over_dense":  # the check looked at the launch's layout and built no other
+        assert st["ptile_items"] > 0, st
+        assert st["dense_sampled_tiles"] == 0, st
 
 
 def test_pairs_with_padding_inside_a_pair():

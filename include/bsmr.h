@@ -441,7 +441,7 @@ int bsmr_spmm_t(const bsmr_plan* plan, const float* dV, const void* dA, uint32_t
 /* Build now what the first bsmr_spmm (sides & 1) / bsmr_spmm_t (sides & 2) of K columns would
  * build inside the call: the side's gather lists and the scratch of its split destinations.
  * chunk: entries per segment (one wave each; longer lists are split and summed through partial
- * rows), 0 = keep the lists already built, else the default (512). Synchronous and idempotent; a
+ * rows), 0 = keep the lists already built, else the default (128). Synchronous and idempotent; a
  * larger K grows the scratch, a different non-zero chunk rebuilds the lists. sides outside 1..3:
  * BSMR_ERR_INVALID. The lists do not depend on the column split: bsmr_plan_recolumn keeps them. */
 int bsmr_plan_prepare_spmm(const bsmr_plan* plan, uint32_t K, int sides, uint32_t chunk);

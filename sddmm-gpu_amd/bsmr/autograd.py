@@ -38,6 +38,11 @@ def _validate(plan, A, B):
         raise ValueError(f"sddmm: A has K = {K}, B has K = {B.shape[1]}")
     if K == 0 or K % 16:
         raise ValueError(f"sddmm: K = {K} must be a positive multiple of 16")
+    # the forward launch's own rule (csrc/launch_select.cpp validate_launch_k): every fp16 / bf16
+    # launch takes a multiple of 32 only (the column-major half launch by that rule; row-block,
+    # panel-tile and dense-sampled launches exist at multiples of 64 only)
+    if A.dtype != torch.float32 and K % 32:
+        raise ValueError(f"sddmm: K = {K}: float16 / bfloat16 inputs need K to be a positive multiple of 32")
     return K, _DTYPES[A.dtype]
 
 
@@ -73,7 +78,8 @@ class _Sddmm(torch.autograd.Function):
 def sddmm(plan, A, B):
     """P (nnz,) float32 = the plan's sampled A @ B.T, differentiable in A and B. A: (M, K), B:
     (N, K) (the header's column-major K x N), contiguous device tensors of one dtype out of
-    float32, float16 and bfloat16. Shape, dtype, device and contiguity errors raise ValueError
-    before any launch."""
+    float32, float16 and bfloat16; K a positive multiple of 16 (float32) or 32 (float16 /
+    bfloat16: what the forward launch takes). Shape, dtype, device, contiguity and K errors raise
+    ValueError before any launch and before any gather list is built."""
     _validate(plan, A, B)
     return _Sddmm.apply(A, B, plan)

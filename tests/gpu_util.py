@@ -87,6 +87,33 @@ def sddmm_once(plan, A, B, K, nnz, dtype=0):
     return dP.cpu().numpy()[:nnz]
 
 
+def spmm_launch(plan, side, dV, dX, K, dtype, dY, stream=None):
+    """One bsmr_spmm (side 1) / bsmr_spmm_t (side 2) on device tensors, on `stream` (a torch
+    stream) or the current one; no synchronisation."""
+    torch = torch_cuda()
+    s = (stream or torch.cuda.current_stream()).cuda_stream
+    fn = plan.spmm if side == 1 else plan.spmm_t
+    fn(dV.data_ptr(), dX.data_ptr(), K, dY.data_ptr(), stream=s, dtype=dtype)
+
+
+def spmm_device(plan, side, dV, dX, K, dtype):
+    """Y (numpy fp32, destinations x K) of one launch on device operands; Y starts as NaN."""
+    torch = torch_cuda()
+    rows = plan.M if side == 1 else plan.N
+    dY = torch.full((rows, K), float("nan"), dtype=torch.float32, device="cuda")
+    spmm_launch(plan, side, dV, dX, K, dtype, dY)
+    torch.cuda.synchronize()
+    return dY.cpu().numpy()
+
+
+def spmm_once(plan, side, V, X, K, dtype=0):
+    """Y (numpy fp32) of one launch on host operands: V (fp32, nnz) and X (fp32 on the host,
+    converted there so that the device holds exactly the bits of half_values(X, dtype))."""
+    torch = torch_cuda()
+    dV = torch.from_numpy(np.ascontiguousarray(V, np.float32)).cuda()
+    return spmm_device(plan, side, dV, to_device(X, dtype), K, dtype)
+
+
 def rb_geometry(plan, K, dtype):
     """The whole-plan row-block layout of (K, dtype) through the library's debug export (not in the
     header): rows per block, threads per workgroup, item slots, row bytes; None when that (K, dtype)

@@ -5,6 +5,11 @@ CPU torch autograd of ((A @ B.T)[rows, cols] * W).sum() on the same (fp16 / bf16
 operands. Bound per element: 2 n 2^-24 sum|w x| + 1e-6 (n the destination's list length: an
 n-term fp32 sum of once-rounded products, as tests/test_gpu_spmm.py), plus eps |ref| for the
 final cast of half gradients (eps = 2^-11 fp16, 2^-8 bf16: half an ulp of the result format).
+
+On grid data (tests/spmm_cases.py) the gradients are exact: fp32 equals the float64 reference bit
+for bit, fp16 / bf16 equal it cast once by torch; also for an expanded and a strided grad_output
+and accumulated over two backward passes. fp16 / bf16 at K = 48 (no forward launch) raise
+ValueError from sddmm() before any launch or list build.
 """
 import numpy as np
 import pytest
@@ -72,6 +77,111 @@ def test_gradients_match_float64_autograd(name, K, dtype):
         print(f"{name} K={K} dtype={dtype} {what}: max err / bound = {float((err / bound).max()):.3f}")
         assert np.isfinite(err).all()
         assert (err <= bound).all(), f"{what}: {int((err > bound).sum())} elements over the bound"
+
+
+ROW_BLOCK_KD = [(64, F32), (128, F16), (128, BF16)]  # rows of 256 bytes: the row-block forward launch
+KD_IDS = ["K64_f32", "K128_f16", "K128_bf16"]
+
+
+def _grid_leaves(torch, name, K, dtype):
+    from sddmm_cases import grid_data
+    M, N, _, _ = pattern(name)
+    A = grid_data(M * K, 41).reshape(M, K)
+    B = grid_data(N * K, 42).reshape(N, K)
+    dA = torch.from_numpy(A).cuda().to(_tdt(torch, dtype)).requires_grad_()
+    dB = torch.from_numpy(B).cuda().to(_tdt(torch, dtype)).requires_grad_()
+    return A, B, dA, dB
+
+
+def _assert_grad_exact(torch, got, pat, side, G, X, dtype, what, times=1):
+    """got == times x the exact S(G) X (side 1) / S(G)^T X (side 2), cast to the operand's type by
+    torch: on grid data the fp32 value is exact, so that cast is the only rounding (|value| <=
+    16 x 2048 stays inside fp16's range)."""
+    Yr, _, _ = spmm_ref(pat, side, G, X)
+    exact = (times * Yr).astype(np.float32)
+    assert np.array_equal(exact.astype(np.float64), times * Yr)
+    want = torch.from_numpy(exact).to(_tdt(torch, dtype))
+    assert got.dtype == want.dtype and got.shape == want.shape, what
+    bad = int((got.cpu() != want).sum())
+    assert bad == 0, f"{what}: {bad} elements differ from the exact gradient"
+
+
+@pytest.mark.parametrize("K,dtype", ROW_BLOCK_KD, ids=KD_IDS)
+@pytest.mark.parametrize("name", ["zipf", "hub"])
+def test_grid_gradients_are_exact(name, K, dtype):
+    torch = torch_cuda()
+    import bsmr.autograd as BA
+    from spmm_cases import grid_values
+
+    pat = pattern(name)
+    A, B, dA, dB = _grid_leaves(torch, name, K, dtype)
+    W = grid_values(len(pat[3]), 43)
+    plan = _plan(name)
+    (BA.sddmm(plan, dA, dB) * torch.from_numpy(W).cuda()).sum().backward()
+    torch.cuda.synchronize()
+    assert any(plan.stats()["rb_items"])
+    _assert_grad_exact(torch, dA.grad, pat, 1, W, B, dtype, f"{name} K={K} dtype={dtype} dA")
+    _assert_grad_exact(torch, dB.grad, pat, 2, W, A, dtype, f"{name} K={K} dtype={dtype} dB")
+
+
+@pytest.mark.parametrize("K,dtype", ROW_BLOCK_KD, ids=KD_IDS)
+def test_backward_takes_any_grad_output_layout(K, dtype):
+    torch = torch_cuda()
+    import bsmr.autograd as BA
+    from spmm_cases import grid_values
+
+    name = "zipf"
+    pat = pattern(name)
+    nnz = len(pat[3])
+    A, B, dA, dB = _grid_leaves(torch, name, K, dtype)
+    plan = _plan(name)
+    # an expanded grad_output (every stride 0)
+    BA.sddmm(plan, dA, dB).sum().backward()
+    ones = np.ones(nnz, np.float32)
+    _assert_grad_exact(torch, dA.grad, pat, 1, ones, B, dtype, "expanded dA")
+    _assert_grad_exact(torch, dB.grad, pat, 2, ones, A, dtype, "expanded dB")
+    # a non-contiguous one
+    G2 = grid_values(2 * nnz, 44)
+    dG2 = torch.from_numpy(G2).cuda()
+    assert not dG2[::2].is_contiguous()
+    gA, gB = torch.autograd.grad(BA.sddmm(plan, dA, dB), (dA, dB), dG2[::2])
+    _assert_grad_exact(torch, gA, pat, 1, G2[::2], B, dtype, "strided dA")
+    _assert_grad_exact(torch, gB, pat, 2, G2[::2], A, dtype, "strided dB")
+    # two backward passes over one graph accumulate exactly twice the gradient
+    dA.grad = dB.grad = None
+    W = G2[1::2].copy()
+    loss = (BA.sddmm(plan, dA, dB) * torch.from_numpy(W).cuda()).sum()
+    loss.backward(retain_graph=True)
+    loss.backward()
+    torch.cuda.synchronize()
+    _assert_grad_exact(torch, dA.grad, pat, 1, W, B, dtype, "accumulated dA", times=2)
+    _assert_grad_exact(torch, dB.grad, pat, 2, W, A, dtype, "accumulated dB", times=2)
+
+
+@pytest.mark.parametrize("dtype", [F16, BF16])
+def test_half_k48_is_refused_before_any_launch(dtype):
+    """fp16 / bf16 at K = 48 pass the K % 16 rule of the gradients, but no forward launch takes
+    them (launch_select.cpp validate_launch_k: a multiple of 32): sddmm() raises ValueError itself,
+    no P is returned, neither side's lists are built and no forward layout exists."""
+    torch = torch_cuda()
+    import bsmr.autograd as BA
+
+    name, K = "empty", 48
+    M, N, _, _ = pattern(name)
+    plan = _plan(name)
+    A = torch.zeros((M, K), dtype=_tdt(torch, dtype), device="cuda", requires_grad=True)
+    B = torch.zeros((N, K), dtype=_tdt(torch, dtype), device="cuda", requires_grad=True)
+    P = None
+    with pytest.raises(ValueError, match="multiple of 32"):
+        P = BA.sddmm(plan, A, B)
+    assert P is None
+    empty = dict(segments=0, split_dsts=0, partials=0, max_list=0, chunk=0)
+    assert plan.spmm_stats(1) == empty and plan.spmm_stats(2) == empty
+    assert not plan.spmm_prepared(K, 1) and not plan.spmm_prepared(K, 2) and not plan.prepared(K, dtype)
+    # the same K in fp32 is a column-major launch and differentiates
+    A32 = torch.zeros((M, K), device="cuda", requires_grad=True)
+    BA.sddmm(plan, A32, torch.zeros((N, K), device="cuda")).sum().backward()
+    assert A32.grad.shape == (M, K) and plan.spmm_prepared(K, 1)
 
 
 def test_only_the_needed_side_runs():

@@ -23,6 +23,7 @@ from bsmr import BF16, F16, F32, Plan
 from gpu_util import nan_output, path_evidence, sddmm_once, to_device, torch_cuda, torch_dtype
 from sddmm_cases import (BY_NAME, DTYPE_NAME, FREE, ONE_PER_KIND, Case, as_seen, assert_bound, assert_exact,
                          grid_data, pattern, plan_kwargs, reference, sddmm_ref, signed_data)
+from small_patterns import SMALL
 from spmm_cases import entry_rows
 
 pytestmark = pytest.mark.gpu
@@ -30,30 +31,6 @@ pytestmark = pytest.mark.gpu
 UNSUPPORTED = 6  # BSMR_ERR_UNSUPPORTED
 GUARD = 4096
 P_GUARD_BITS = 0x5A5AC3C3
-
-
-def _csr(M, N, mask):
-    mask = np.asarray(mask, bool).reshape(M, N)
-    rp = np.concatenate([[0], np.cumsum(mask.sum(axis=1))]).astype(np.uint32)
-    return M, N, rp, np.nonzero(mask)[1].astype(np.uint32)
-
-
-def _ragged(M, N=5):
-    """Rows of 0 .. N entries (every other row empty), and one in the last row's last column."""
-    r = np.arange(M)[:, None]
-    c = np.arange(N)[None, :]
-    return _csr(M, N, (c < (r * 3) % (N + 1)) | ((r == M - 1) & (c == N - 1)))
-
-
-SMALL = {
-    "1x2": _csr(1, 2, [[1, 1]]),
-    "2x1": _csr(2, 1, [[1], [1]]),
-    "15x5": _ragged(15),
-    "16x5": _ragged(16),
-    "17x5": _ragged(17),
-    "row130": _csr(1, 130, np.ones((1, 130))),
-    "full17": _csr(17, 17, np.ones((17, 17))),
-}
 
 
 @pytest.mark.parametrize("layout", ["auto", "rowblock", "colmajor"])

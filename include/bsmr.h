@@ -40,7 +40,11 @@ extern "C" {
                               bsmr_plan_panels_prepared, BSMR_ERR_NOT_PREPARED; bsmr_spmm,
                               bsmr_spmm_t, bsmr_plan_prepare_spmm, bsmr_plan_spmm_prepared,
                               bsmr_plan_spmm_stats, bsmr_spmm_lists (SpMM over the plan's pattern:
-                              the gradients of bsmr_sddmm) */
+                              the gradients of bsmr_sddmm); bsmr_softmax, bsmr_softmax_backward,
+                              bsmr_plan_prepare_softmax, bsmr_plan_softmax_prepared,
+                              bsmr_plan_softmax_stats, bsmr_softmax_items, bsmr_softmax_limits (row
+                              softmax over the plan's pattern: the step between bsmr_sddmm and
+                              bsmr_spmm) */
 
 typedef enum {
     BSMR_OK = 0,
@@ -475,6 +479,62 @@ int bsmr_spmm_lists(uint32_t M, uint32_t N, uint32_t nnz, const uint32_t* rowptr
                     const uint32_t* colidx, int side, uint32_t chunk, const uint32_t* order,
                     uint32_t norder, bsmr_spmm_seg* segs, uint64_t* nsegs, uint32_t* src,
                     uint32_t* vpos);
+
+/* ------------------------------------------- row softmax over the plan's pattern ---- */
+/* Per row i of S, over its stored entries e (P and W: fp32, nnz, CSR order):
+ *   bsmr_softmax          : W_e = t_e / sum_i t,  t_e = exp((P_e - max_i P) scale)
+ *   bsmr_softmax_backward : dP_e = scale W_e (G_e - sum_i W G),  G = dL/dW
+ * the step between bsmr_sddmm's scores and the aggregation bsmr_spmm. scale must be finite and
+ * > 0 (with scale log2(e) finite in fp32), else BSMR_ERR_INVALID and the output is untouched, as
+ * for a null plan or pointer. The maximum is subtracted before the scaling: W is invariant under
+ * a shift of a row, and rounding errors grow with |d_e|, not with |P|. fp32 throughout, no atomics
+ * and no plan-owned scratch: a row's terms are reduced in an order that depends on its length
+ * alone, so results are bitwise reproducible, a row's result is the same in any
+ * plan that holds a row of that length, and launches on different streams need no ordering.
+ * Conventions:
+ *   a row that holds a NaN or a +inf is NaN in all of its entries; no other row is affected;
+ *   -inf entries get weight 0; a row whose entries are all -inf gets all zeros (the fully masked
+ *   row), and its backward gives zeros; entries of empty rows do not exist, nothing is written;
+ *   dW == dP (forward) and dGP == dG (backward), the exact same pointer, are allowed (in place);
+ *   any other overlap is the caller's error.
+ * Asynchronous on `stream` once the plan's item list exists: the first launch builds it (a copy
+ * of rowptr and a synchronisation of the plan's stream) unless bsmr_plan_prepare_softmax did, and
+ * on a capturing stream an unbuilt list gives BSMR_ERR_NOT_PREPARED and leaves the capture intact.
+ * At most two kernel launches per call. */
+int bsmr_softmax(const bsmr_plan* plan, const float* dP, float scale, float* dW, void* stream);
+int bsmr_softmax_backward(const bsmr_plan* plan, const float* dW, const float* dG, float scale,
+                          float* dGP, void* stream);
+/* Build the item list now. Synchronous and idempotent. The list depends on rowptr only:
+ * bsmr_plan_recolumn keeps it. */
+int bsmr_plan_prepare_softmax(const bsmr_plan* plan);
+/* 1 when a launch would make no allocation, copy or synchronisation, else 0 (also 0 for a null
+ * plan, with bsmr_last_error set). No device call. */
+int bsmr_plan_softmax_prepared(const bsmr_plan* plan);
+typedef struct {
+    uint32_t items;        /* packed_runs + wave_rows + block_rows */
+    uint32_t packed_runs;  /* waves that take up to 64 / L rows of at most L <= 64 entries each */
+    uint32_t wave_rows;    /* rows of 65 .. wave_max entries: one wave, P read once */
+    uint32_t block_rows;   /* rows above wave_max: one workgroup, passes of block_pass entries */
+    uint32_t max_row;      /* entries of the longest row */
+    uint32_t wave_max, block_pass; /* the library's constants (always filled) */
+} bsmr_softmax_stats;
+/* Counts are zeros while the list is not built; wave_max and block_pass are always filled. */
+int bsmr_plan_softmax_stats(const bsmr_plan* plan, bsmr_softmax_stats* out);
+
+/* Host-only form of the item list (no plan, no device), from rowptr[M + 1] alone, in ascending
+ * row order; every non-empty row is in exactly one item and empty rows in none (a pattern without
+ * entries has no item). kind 1 .. 64 (a power of two L): a packed run of rows row .. row + count - 1
+ * (count <= 64 / L), each empty or of L / 2 < length <= L entries, first and last non-empty;
+ * BSMR_SOFTMAX_WAVE: one row of 64 < count <= wave_max entries; BSMR_SOFTMAX_BLOCK: one row of
+ * count > wave_max entries. first = rowptr[row]. items == NULL: query *nitems only.
+ * BSMR_ERR_INVALID for a null rowptr or nitems, or a rowptr that is not non-decreasing from 0. */
+enum { BSMR_SOFTMAX_WAVE = 0x100, BSMR_SOFTMAX_BLOCK = 0x200 };
+typedef struct {
+    uint32_t row, first, count, kind;
+} bsmr_softmax_item;
+int bsmr_softmax_items(uint32_t M, const uint32_t* rowptr, bsmr_softmax_item* items, uint64_t* nitems);
+/* The constants of bsmr_softmax_stats without a plan (either pointer may be NULL). */
+void bsmr_softmax_limits(uint32_t* wave_max, uint32_t* block_pass);
 
 /* Timing: run `iters` back-to-back SDDMMs on `stream`, timing each kernel with HIP events on
  * that stream (BSMR_ERR_UNSUPPORTED on a capturing stream). Outputs average ms per launch of the dense-tile kernel, the residual kernel and

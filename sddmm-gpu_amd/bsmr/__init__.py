@@ -7,7 +7,9 @@ Reference interface mirrored (paths relative to the reference root):
   * sddmm_gpu(M, N, K, dA, dB, rphm, dP, logger)       -> Plan.sddmm      (src/sddmmKernel.cu:2540)
   * evaluationReordering                               -> Plan.evaluate   (src/BSMR.cpp:826-994)
 Beyond the reference: the gradients of the SDDMM as SpMM over the same plan (Plan.spmm,
-Plan.spmm_t, Plan.sddmm_backward; bsmr.autograd wraps both directions for torch.autograd).
+Plan.spmm_t, Plan.sddmm_backward), the row softmax over the plan's pattern (Plan.softmax,
+Plan.softmax_backward), and bsmr.autograd, which wraps SDDMM, softmax and SpMM for torch.autograd
+and composes them into sparse attention.
 
 Every call goes through the HIP library; there is no CPU fallback. If the shared library is
 missing the import fails loudly (build it with `make -C sddmm-gpu_amd` or
@@ -143,6 +145,22 @@ class SpmmStats(C.Structure):
 
 SPMM_DIRECT = 0xFFFFFFFF  # bsmr_spmm_seg.part of a segment that writes Y itself
 
+
+class SoftmaxStats(C.Structure):
+    """bsmr_softmax_stats: the row softmax's item list (counts zero when not built) and the
+    library's constants wave_max / block_pass."""
+    _fields_ = [("items", C.c_uint32), ("packed_runs", C.c_uint32), ("wave_rows", C.c_uint32),
+                ("block_rows", C.c_uint32), ("max_row", C.c_uint32), ("wave_max", C.c_uint32),
+                ("block_pass", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+# bsmr_softmax_item.kind beside a packed run's lane-group width 1 .. 64
+SOFTMAX_WAVE = 0x100
+SOFTMAX_BLOCK = 0x200
+
 ABI_VERSION = 13  # include/bsmr.h BSMR_ABI_VERSION
 
 # every symbol include/bsmr.h declares (tests check the library exports all of them)
@@ -163,6 +181,9 @@ EXPORTS = [
     "bsmr_plan_panels_prepared",
     "bsmr_spmm", "bsmr_spmm_t", "bsmr_plan_prepare_spmm", "bsmr_plan_spmm_prepared",
     "bsmr_plan_spmm_stats", "bsmr_spmm_lists",
+    "bsmr_softmax", "bsmr_softmax_backward", "bsmr_plan_prepare_softmax",
+    "bsmr_plan_softmax_prepared", "bsmr_plan_softmax_stats", "bsmr_softmax_items",
+    "bsmr_softmax_limits",
 ]
 
 _lib = None
@@ -256,6 +277,19 @@ def lib():
     L.bsmr_spmm_lists.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, _u32p, _u32p, C.c_int,
                                   C.c_uint32, vp, C.c_uint32, vp, C.POINTER(C.c_uint64), vp, vp]
     L.bsmr_spmm_lists.restype = C.c_int
+    L.bsmr_softmax.argtypes = [vp, vp, C.c_float, vp, vp]
+    L.bsmr_softmax.restype = C.c_int
+    L.bsmr_softmax_backward.argtypes = [vp, vp, vp, C.c_float, vp, vp]
+    L.bsmr_softmax_backward.restype = C.c_int
+    for f in ("bsmr_plan_prepare_softmax", "bsmr_plan_softmax_prepared"):
+        getattr(L, f).argtypes = [vp]
+        getattr(L, f).restype = C.c_int
+    L.bsmr_plan_softmax_stats.argtypes = [vp, C.POINTER(SoftmaxStats)]
+    L.bsmr_plan_softmax_stats.restype = C.c_int
+    L.bsmr_softmax_items.argtypes = [C.c_uint32, vp, vp, C.POINTER(C.c_uint64)]
+    L.bsmr_softmax_items.restype = C.c_int
+    L.bsmr_softmax_limits.argtypes = [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    L.bsmr_softmax_limits.restype = None
     L.bsmr_plan_check.argtypes = [vp, C.c_uint32, C.c_int, C.c_int]
     L.bsmr_plan_check.restype = C.c_int
     L.bsmr_check_rphm_arrays.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32] + [_u32p] * 2 + \
@@ -539,6 +573,32 @@ class Plan:
         _check(lib().bsmr_plan_spmm_stats(self.h, side, C.byref(s)), "bsmr_plan_spmm_stats")
         return s.as_dict()
 
+    def softmax(self, dP, dW, scale=1.0, stream=0):
+        """bsmr_softmax: per row of S, W = softmax(scale * P) over the row's stored entries (dP,
+        dW: device pointers to nnz fp32 in CSR order; dW == dP works in place). The maximum is
+        subtracted before the scaling. scale: finite and > 0. -inf entries get weight 0, a row of
+        nothing but -inf all zeros, a row with a NaN or +inf all NaN; empty rows write nothing."""
+        _check(lib().bsmr_softmax(self.h, dP, scale, dW, stream or None), "bsmr_softmax")
+
+    def softmax_backward(self, dW, dG, dGP, scale=1.0, stream=0):
+        """bsmr_softmax_backward: dGP = scale * W * (G - sum_row W G), the gradient of
+        Plan.softmax at the same scale from its result W and G = dL/dW (dGP == dG works in place)."""
+        _check(lib().bsmr_softmax_backward(self.h, dW, dG, scale, dGP, stream or None),
+               "bsmr_softmax_backward")
+
+    def prepare_softmax(self):
+        """bsmr_plan_prepare_softmax: build the softmax item list now, so that the first softmax
+        launch can be captured."""
+        _check(lib().bsmr_plan_prepare_softmax(self.h), "bsmr_plan_prepare_softmax")
+
+    def softmax_prepared(self):
+        return bool(lib().bsmr_plan_softmax_prepared(self.h))
+
+    def softmax_stats(self):
+        s = SoftmaxStats()
+        _check(lib().bsmr_plan_softmax_stats(self.h, C.byref(s)), "bsmr_plan_softmax_stats")
+        return s.as_dict()
+
     def sddmm_backward(self, dG, dA, dB, K, dGA, dGB, stream=0, dtype=F32):
         """The gradients of P = sddmm(A, B) from dG = dL/dP (fp32, nnz): dGA (M x K fp32) =
         S(G) B and dGB (N x K fp32) = S(G)^T A. Either output may be 0: that side is skipped."""
@@ -625,6 +685,29 @@ def spmm_lists(M, N, rowptr, colidx, side, chunk, order=None):
     _check(lib().bsmr_spmm_lists(*args, segs.ctypes.data, C.byref(n), src.ctypes.data,
                                  vpos.ctypes.data), "bsmr_spmm_lists")
     return segs, src[:nnz], vpos[:nnz]
+
+
+def softmax_items(M, rowptr):
+    """bsmr_softmax_items (host only): (n, 4) uint32 rows {row, first, count, kind} of the row
+    softmax's item list in ascending row order. kind 1 .. 64: a packed run of `count` rows from
+    `row`, lane groups of `kind` lanes; SOFTMAX_WAVE / SOFTMAX_BLOCK: one row of `count` entries."""
+    rowptr = np.ascontiguousarray(rowptr, np.uint32)
+    if len(rowptr) != M + 1:
+        raise ValueError("softmax_items: rowptr needs M + 1 entries")
+    n = C.c_uint64()
+    _check(lib().bsmr_softmax_items(M, rowptr.ctypes.data, None, C.byref(n)), "bsmr_softmax_items")
+    items = np.zeros((n.value, 4), np.uint32)
+    _check(lib().bsmr_softmax_items(M, rowptr.ctypes.data, items.ctypes.data if n.value else None,
+                                    C.byref(n)), "bsmr_softmax_items")
+    return items
+
+
+def softmax_limits():
+    """bsmr_softmax_limits (host only): dict(wave_max, block_pass), the constants of
+    Plan.softmax_stats without a plan."""
+    w, b = C.c_uint32(), C.c_uint32()
+    lib().bsmr_softmax_limits(C.byref(w), C.byref(b))
+    return dict(wave_max=w.value, block_pass=b.value)
 
 
 def sddmm_cpu(M, N, rowptr, colidx, K, A, B, threads=0):

@@ -3,7 +3,14 @@
     forward   P[idx(i,j)] = dot(A[i,:], B[j,:])                 Plan.sddmm
     backward  dA = S(G) B (Plan.spmm), dB = S(G)^T A (Plan.spmm_t), G = dL/dP
 
-Both directions are the library's HIP kernels on torch.cuda.current_stream(); torch only owns the
+and, over the same plan, the row softmax, the SpMM and their composition into sparse attention:
+
+    softmax(plan, P, scale)      W = per-row softmax(scale P)     Plan.softmax / softmax_backward
+    spmm(plan, V, X)             Y = S(V) X                        Plan.spmm; dV = Plan.sddmm(dY, X),
+                                                                   dX = Plan.spmm_t(V, dY)
+    attention(plan, Q, K, V)     spmm(softmax(sddmm(Q, K), scale), V)
+
+Every direction is the library's HIP kernels on torch.cuda.current_stream(); torch only owns the
 tensors. Importing this module imports torch (`import bsmr` alone does not).
 """
 import torch
@@ -83,3 +90,143 @@ def sddmm(plan, A, B):
     ValueError before any launch and before any gather list is built."""
     _validate(plan, A, B)
     return _Sddmm.apply(A, B, plan)
+
+
+def _valid_scale(who, scale):
+    try:
+        s = float(scale)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: scale must be a number, got {scale!r}") from None
+    if not (s > 0.0) or s == float("inf"):
+        raise ValueError(f"{who}: scale = {scale!r} must be finite and > 0")
+    return s
+
+
+def _validate_values(who, name, plan, P):
+    """A vector of one fp32 value per stored entry, in CSR order."""
+    if not isinstance(P, torch.Tensor):
+        raise ValueError(f"{who}: {name} must be a torch tensor")
+    if not P.is_cuda:
+        raise ValueError(f"{who}: {name} must be a device tensor, got {P.device}")
+    if P.dtype != torch.float32:
+        raise ValueError(f"{who}: {name} must be float32, got {P.dtype}")
+    if P.dim() != 1 or P.shape[0] != plan.nnz:
+        raise ValueError(f"{who}: {name} must be ({plan.nnz},), got {tuple(P.shape)}")
+    if not P.is_contiguous():
+        raise ValueError(f"{who}: {name} must be contiguous")
+
+
+def _launchable(t):
+    """The launch wants a valid pointer even for a plan without entries."""
+    return t if t.shape[0] else torch.zeros(1, dtype=torch.float32, device=t.device)
+
+
+class _Softmax(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, P, plan, scale):
+        W = torch.empty(max(plan.nnz, 1), dtype=torch.float32, device=P.device)
+        plan.softmax(_launchable(P).data_ptr(), W.data_ptr(), scale, stream=_stream())
+        W = W[:plan.nnz]
+        ctx.plan, ctx.scale = plan, scale
+        ctx.save_for_backward(W)
+        return W
+
+    @staticmethod
+    def backward(ctx, grad):
+        (W,) = ctx.saved_tensors
+        plan = ctx.plan
+        G = grad.contiguous().float()
+        gP = torch.empty(max(plan.nnz, 1), dtype=torch.float32, device=W.device)
+        plan.softmax_backward(_launchable(W).data_ptr(), _launchable(G).data_ptr(), gP.data_ptr(), ctx.scale,
+                              stream=_stream())
+        return gP[:plan.nnz], None, None
+
+
+def softmax(plan, P, scale=1.0):
+    """W (nnz,) float32 = per row of the plan's pattern, softmax(scale * P) over the row's stored
+    entries (Plan.softmax), differentiable in P (Plan.softmax_backward). P: (nnz,) float32
+    contiguous device tensor in CSR order; scale finite and > 0. Errors raise ValueError before
+    any launch."""
+    _validate_values("softmax", "P", plan, P)
+    return _Softmax.apply(P, plan, _valid_scale("softmax", scale))
+
+
+def _validate_dense(plan, X):
+    """The dense operand of spmm: (N, K) of a supported dtype; returns (K, dtype)."""
+    if not isinstance(X, torch.Tensor):
+        raise ValueError("spmm: X must be a torch tensor")
+    if not X.is_cuda:
+        raise ValueError(f"spmm: X must be a device tensor, got {X.device}")
+    if X.dtype not in _DTYPES:
+        raise ValueError(f"spmm: X must be float32, float16 or bfloat16, got {X.dtype}")
+    if X.dim() != 2 or X.shape[0] != plan.N:
+        raise ValueError(f"spmm: X must be ({plan.N}, K), got {tuple(X.shape)}")
+    if not X.is_contiguous():
+        raise ValueError("spmm: X must be contiguous")
+    K = X.shape[1]
+    if K == 0 or K % 16:
+        raise ValueError(f"spmm: K = {K} must be a positive multiple of 16")
+    return K, _DTYPES[X.dtype]
+
+
+def _validate_spmm(plan, V, X):
+    _validate_values("spmm", "V", plan, V)
+    K, dtype = _validate_dense(plan, X)
+    if V.device != X.device:
+        raise ValueError(f"spmm: V ({V.device}) and X ({X.device}) must share one device")
+    return K, dtype
+
+
+class _Spmm(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, V, X, plan):
+        K, dtype = _validate_spmm(plan, V, X)
+        Y = torch.empty((plan.M, K), dtype=torch.float32, device=X.device)
+        plan.spmm(_launchable(V).data_ptr(), X.data_ptr(), K, Y.data_ptr(), stream=_stream(), dtype=dtype)
+        ctx.plan, ctx.K = plan, K
+        ctx.save_for_backward(V, X)
+        return Y
+
+    @staticmethod
+    def backward(ctx, grad):
+        V, X = ctx.saved_tensors
+        plan, K = ctx.plan, ctx.K
+        dY = grad.contiguous().float()
+        gV = gX = None
+        if ctx.needs_input_grad[0]:
+            # fp32 SDDMM of dY (fp32) with X: a half X is cast up once
+            gV = torch.empty(max(plan.nnz, 1), dtype=torch.float32, device=X.device)
+            plan.sddmm(dY.data_ptr(), X.float().data_ptr(), K, gV.data_ptr(), stream=_stream())
+            gV = gV[:plan.nnz]
+        if ctx.needs_input_grad[1]:
+            gX = torch.empty((plan.N, K), dtype=torch.float32, device=X.device)
+            plan.spmm_t(_launchable(V).data_ptr(), dY.data_ptr(), K, gX.data_ptr(), stream=_stream())
+            gX = gX.to(X.dtype)
+        return gV, gX, None
+
+
+def spmm(plan, V, X):
+    """Y (M, K) float32 = S(V) X, the plan's pattern with values V times the dense X (Plan.spmm),
+    differentiable in both: dV = the plan's sampled dY @ X.T (Plan.sddmm, in fp32: a float16 /
+    bfloat16 X is cast up to float32 once for it), dX = S(V)^T dY (Plan.spmm_t, returned in X's
+    dtype). V: (nnz,) float32 in CSR order; X: (N, K) float32, float16 or bfloat16, K a positive
+    multiple of 16; contiguous tensors of one device. Errors raise ValueError before any launch."""
+    _validate_spmm(plan, V, X)
+    return _Spmm.apply(V, X, plan)
+
+
+def attention(plan, Q, K, V, scale=None):
+    """O (M, Dv) float32 = softmax(scale * S .* (Q @ K.T)) @ V over the plan's pattern, exactly
+    spmm(plan, softmax(plan, sddmm(plan, Q, K), scale), V) and nothing more; scale = 1 / sqrt(D)
+    by default (D = Q.shape[1]). Q: (M, D), K: (N, D), V: (N, Dv); each op's own rules apply."""
+    if scale is None:
+        if not isinstance(Q, torch.Tensor) or Q.dim() != 2 or Q.shape[1] == 0:
+            raise ValueError("attention: Q must be an (M, D) tensor with D > 0")
+        scale = Q.shape[1] ** -0.5
+    scale = _valid_scale("attention", scale)
+    # every operand is checked before the first launch (each op checks its own again)
+    _validate(plan, Q, K)
+    _validate_dense(plan, V)
+    if V.device != Q.device:
+        raise ValueError(f"spmm: V ({V.device}) and Q ({Q.device}) must share one device")
+    return spmm(plan, softmax(plan, sddmm(plan, Q, K), scale), V)

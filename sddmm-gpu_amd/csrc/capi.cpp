@@ -623,6 +623,32 @@ extern "C" int bsmr_spmm_lists(uint32_t M, uint32_t N, uint32_t nnz, const uint3
     return BSMR_OK;
 }
 
+// the row softmax's item list over a caller's rowptr (softmax_schedule.cpp; no plan, no device)
+extern "C" int bsmr_softmax_items(uint32_t M, const uint32_t* rowptr, bsmr_softmax_item* items,
+                                  uint64_t* nitems) {
+    static_assert(sizeof(bsmr_softmax_item) == sizeof(SoftmaxItem), "bsmr_softmax_item mirrors SoftmaxItem");
+    static_assert(BSMR_SOFTMAX_WAVE == SOFTMAX_WAVE && BSMR_SOFTMAX_BLOCK == SOFTMAX_BLOCK, "item kinds");
+    if (!rowptr || !nitems) {
+        set_error("bsmr_softmax_items: null argument");
+        return BSMR_ERR_INVALID;
+    }
+    SoftmaxItems L;
+    std::string err;
+    if (softmax_items(M, rowptr, L, err, items == nullptr)) {
+        set_error("bsmr_softmax_items: " + err);
+        return BSMR_ERR_INVALID;
+    }
+    *nitems = L.nItems;
+    for (size_t i = 0; items && i < L.items.size(); ++i)
+        items[i] = bsmr_softmax_item{L.items[i].row, L.items[i].first, L.items[i].count, L.items[i].kind};
+    return BSMR_OK;
+}
+
+extern "C" void bsmr_softmax_limits(uint32_t* wave_max, uint32_t* block_pass) {
+    if (wave_max) *wave_max = SOFTMAX_WAVE_MAX;
+    if (block_pass) *block_pass = SOFTMAX_BLOCK_PASS;
+}
+
 extern "C" int bsmr_plan_shard_rebalance(const bsmr_plan* plan, uint32_t K, int dtype, int world,
                                          const uint32_t* prev_cuts, const float* shard_ms,
                                          uint32_t* cuts) {

@@ -9,6 +9,7 @@
 #include "common.hpp"
 #include "launch_select.hpp"
 #include "rb_schedule.hpp"
+#include "softmax_schedule.hpp"
 #include "spmm_schedule.hpp"
 
 namespace bsmr {
@@ -354,6 +355,17 @@ struct Plan {
         DevBuf<float> scratch;
     };
     mutable SpmmSide spmm[2];  // [0] rows (bsmr_spmm), [1] columns (bsmr_spmm_t)
+
+    // row softmax (softmax.hip; bsmr_softmax / bsmr_softmax_backward): the item list
+    // (softmax_schedule.hpp), packed runs and wave rows apart from block rows. Built on first use
+    // or by bsmr_plan_prepare_softmax, under layout_mu; it depends on rowptr only, so
+    // build_columns keeps it
+    struct SoftmaxList {
+        bool built = false;
+        u32 nRows = 0, nBlocks = 0, packedRuns = 0, waveRows = 0, maxRow = 0;
+        DevBuf<SoftmaxItem> rows, blocks;
+    };
+    mutable SoftmaxList softmax;
 
     int build_rows(const u32* h_rowptr, const u32* h_col);
     int build_columns();

@@ -202,7 +202,13 @@ void bsmr_plan_options_default(bsmr_plan_options* o);
 /* Replaces BSMR::BSMR(alpha, delta, S) + RPHM::RPHM(S, bsmr) (src/BSMR.cpp:16-265;
  * include/BSMR.hpp:25-28, 83-159): row reordering (rowReordering.cu:1027-1095), column
  * reordering (colReordering.cu:274-404) and the dense-tile / residual layout, all built on the
- * GPU. Host CSR in, device-resident plan out. */
+ * GPU. Host CSR in, device-resident plan out.
+ * CSR contract (also bsmr_plan_import_rows): rowptr and colidx non-NULL, M, N > 0, rowptr[0] == 0,
+ * rowptr non-decreasing, rowptr[M] == nnz >= 2 (the reference loaders refuse smaller matrices),
+ * every colidx[k] < N. Columns need not be sorted inside a row; a repeated column is the
+ * caller's concern (the loaders reject it). Checked on the host in O(M + nnz) before any device
+ * call: a violation returns BSMR_ERR_INVALID, bsmr_last_error naming the first offending row or
+ * entry, and nothing reaches the device. */
 int bsmr_plan_create(const uint32_t* rowptr, const uint32_t* colidx, uint32_t M, uint32_t N,
                      uint32_t nnz, const bsmr_plan_options* opt, bsmr_plan** out);
 /* Row stage of a plan (BSMR::rowReordering, BSMR.cpp:27-50 / rowReordering.cu:1027-1095): the

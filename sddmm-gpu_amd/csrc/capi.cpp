@@ -163,9 +163,35 @@ int init_plan(Plan& p, const bsmr_plan_options& o) {
     return BSMR_OK;
 }
 
-bool valid_csr(const uint32_t* rowptr, const uint32_t* colidx, uint32_t M, uint32_t N,
-               uint32_t nnz) {
-    return rowptr && colidx && M != 0 && N != 0 && rowptr[M] == nnz && nnz >= 2;
+// The CSR contract of bsmr_plan_create / bsmr_plan_import_rows (include/bsmr.h), checked on the
+// host in O(M + nnz) before any device call: k_encode indexes an LDS histogram of nbpr words by
+// col / bs and walks rowptr[r] .. rowptr[r + 1], so a column >= N or a decreasing rowptr would
+// write out of bounds on the device. Returns false with the first offender in bsmr_last_error.
+bool valid_csr(const char* who, const uint32_t* rowptr, const uint32_t* colidx, uint32_t M,
+               uint32_t N, uint32_t nnz) {
+    if (!(rowptr && colidx && M != 0 && N != 0 && rowptr[M] == nnz && nnz >= 2)) {
+        set_error(std::string(who) + ": invalid CSR (need rowptr[M] == nnz >= 2)");
+        return false;
+    }
+    if (rowptr[0] != 0) {
+        set_error(std::string(who) + ": invalid CSR (rowptr[0] = " + std::to_string(rowptr[0]) +
+                  ", need 0)");
+        return false;
+    }
+    for (uint32_t r = 0; r < M; ++r)
+        if (rowptr[r] > rowptr[r + 1]) {
+            set_error(std::string(who) + ": invalid CSR (rowptr decreases at row " +
+                      std::to_string(r) + ": " + std::to_string(rowptr[r]) + " > " +
+                      std::to_string(rowptr[r + 1]) + ")");
+            return false;
+        }
+    for (uint32_t k = 0; k < nnz; ++k)
+        if (colidx[k] >= N) {
+            set_error(std::string(who) + ": invalid CSR (colidx[" + std::to_string(k) + "] = " +
+                      std::to_string(colidx[k]) + " >= N = " + std::to_string(N) + ")");
+            return false;
+        }
+    return true;
 }
 
 }  // namespace
@@ -174,10 +200,7 @@ extern "C" int bsmr_plan_create(const uint32_t* rowptr, const uint32_t* colidx, 
                                 uint32_t N, uint32_t nnz, const bsmr_plan_options* opt,
                                 bsmr_plan** out) {
     *out = nullptr;
-    if (!valid_csr(rowptr, colidx, M, N, nnz)) {
-        set_error("bsmr_plan_create: invalid CSR (need rowptr[M] == nnz >= 2)");
-        return BSMR_ERR_INVALID;
-    }
+    if (!valid_csr("bsmr_plan_create", rowptr, colidx, M, N, nnz)) return BSMR_ERR_INVALID;
     bsmr_plan_options o;
     if (opt)
         o = *opt;
@@ -252,8 +275,13 @@ extern "C" int bsmr_plan_import_rows(const uint32_t* rowptr, const uint32_t* col
                                      const bsmr_row_stage* hdr, const uint32_t* rows,
                                      const bsmr_plan_options* opt, bsmr_plan** out) {
     *out = nullptr;
-    if (!hdr || !valid_csr(rowptr, colidx, hdr->M, hdr->N, hdr->nnz) ||
-        hdr->num_reordered_rows > hdr->M || hdr->num_zero_rows > hdr->M ||
+    if (!hdr) {
+        set_error("bsmr_plan_import_rows: invalid CSR or row-stage header");
+        return BSMR_ERR_INVALID;
+    }
+    if (!valid_csr("bsmr_plan_import_rows", rowptr, colidx, hdr->M, hdr->N, hdr->nnz))
+        return BSMR_ERR_INVALID;
+    if (hdr->num_reordered_rows > hdr->M || hdr->num_zero_rows > hdr->M ||
         hdr->num_reordered_rows + hdr->num_zero_rows != hdr->M ||
         (hdr->num_reordered_rows && !rows)) {
         set_error("bsmr_plan_import_rows: invalid CSR or row-stage header");

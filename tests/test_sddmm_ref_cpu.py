@@ -197,3 +197,58 @@ def test_plan_create_rejects_fewer_than_two_entries(nnz):
         bsmr.Plan(2, 3, rp, ci)
     assert ei.value.status == 1  # BSMR_ERR_INVALID
     assert "nnz >= 2" in str(ei.value)
+
+
+def _plan_status(M, N, rp, ci):
+    """(status, message) of bsmr_plan_create on the host CSR; (0, "") when a plan was built."""
+    try:
+        bsmr.Plan(M, N, np.asarray(rp, np.uint32), np.asarray(ci, np.uint32))
+    except bsmr.BsmrError as e:
+        return e.status, str(e)
+    return 0, ""
+
+
+# 3 rows, N = 8, 6 entries; each case breaks one rule of the CSR contract (include/bsmr.h)
+@pytest.mark.parametrize("rp,ci,N,needle", [
+    ([0, 4, 2, 6], [0, 1, 2, 3, 4, 5], 8, "rowptr decreases at row 1"),
+    ([0, 7, 6, 6], [0, 1, 2, 3, 4, 5], 8, "rowptr decreases at row 1"),   # rowptr[1] > nnz as well
+    ([1, 2, 4, 6], [0, 1, 2, 3, 4, 5], 8, "rowptr[0] = 1"),
+    ([0, 2, 4, 6], [0, 1, 2, 3, 8, 5], 8, "colidx[4] = 8 >= N = 8"),
+    ([0, 2, 4, 6], [0, 1, 2, 3, 4, 2 ** 32 - 1], 8, "colidx[5] = 4294967295 >= N = 8"),
+    ([0, 2, 4, 6], [0, 9, 2, 3, 8, 5], 8, "colidx[1] = 9"),               # the first offender
+])
+def test_plan_create_rejects_invalid_csr(rp, ci, N, needle):
+    """include/bsmr.h bsmr_plan_create: rowptr[0] == 0, rowptr non-decreasing, colidx < N; refused
+    with BSMR_ERR_INVALID and the first offending row or entry, before any device call (a column
+    block index past the row's LDS histogram would otherwise be written by k_encode)."""
+    st, msg = _plan_status(3, N, rp, ci)
+    assert st == 1, (st, msg)  # BSMR_ERR_INVALID
+    assert "bsmr_plan_create" in msg and needle in msg, msg
+
+
+@pytest.mark.parametrize("rp,ci,needle", [
+    ([0, 4, 2, 6], [0, 1, 2, 3, 4, 5], "rowptr decreases at row 1"),
+    ([1, 2, 4, 6], [0, 1, 2, 3, 4, 5], "rowptr[0] = 1"),
+    ([0, 2, 4, 6], [0, 1, 2, 3, 8, 5], "colidx[4] = 8 >= N = 8"),
+    ([0, 2, 4, 6], [0, 1, 2, 3, 4, 2 ** 32 - 1], "colidx[5] = 4294967295"),
+])
+def test_plan_import_rows_rejects_invalid_csr(rp, ci, needle):
+    """bsmr_plan_import_rows applies the same CSR contract before its own header checks and before
+    any device call."""
+    hdr = bsmr.RowStage(M=3, N=8, nnz=6, block_size=16, num_blocks_per_row=1, cluster_block_dim=32,
+                        num_zero_rows=0, num_reordered_rows=3, num_clusters=1, alpha=0.3)
+    with pytest.raises(bsmr.BsmrError) as ei:
+        bsmr.Plan.from_row_stage(np.asarray(rp, np.uint32), np.asarray(ci, np.uint32), hdr,
+                                 np.arange(3, dtype=np.uint32))
+    assert ei.value.status == 1, str(ei.value)
+    assert "bsmr_plan_import_rows" in str(ei.value) and needle in str(ei.value), str(ei.value)
+
+
+def test_plan_create_accepts_unsorted_columns_up_to_the_device_step():
+    """A legal CSR whose columns are not sorted inside a row (the loaders keep file order) passes
+    the host validation: the call gets as far as the device (BSMR_ERR_HIP without one, a plan
+    with one), never BSMR_ERR_INVALID."""
+    st, msg = _plan_status(3, 8, [0, 2, 4, 6], [7, 0, 3, 2, 5, 1])
+    assert st in (0, 4), (st, msg)  # BSMR_OK or BSMR_ERR_HIP
+    if st == 4:
+        assert "hip" in msg.lower(), msg

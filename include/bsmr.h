@@ -44,7 +44,9 @@ extern "C" {
                               bsmr_plan_prepare_softmax, bsmr_plan_softmax_prepared,
                               bsmr_plan_softmax_stats, bsmr_softmax_items, bsmr_softmax_limits (row
                               softmax over the plan's pattern: the step between bsmr_sddmm and
-                              bsmr_spmm) */
+                              bsmr_spmm); bsmr_attention, bsmr_plan_prepare_attention,
+                              bsmr_plan_attention_prepared, bsmr_plan_attention_stats,
+                              bsmr_attention_limits (fused sparse attention forward) */
 
 typedef enum {
     BSMR_OK = 0,
@@ -541,6 +543,62 @@ typedef struct {
 int bsmr_softmax_items(uint32_t M, const uint32_t* rowptr, bsmr_softmax_item* items, uint64_t* nitems);
 /* The constants of bsmr_softmax_stats without a plan (either pointer may be NULL). */
 void bsmr_softmax_limits(uint32_t* wave_max, uint32_t* block_pass);
+
+/* ------------------------------------------------- fused sparse attention forward ---- */
+/* Per row i of S, over its stored entries e = (i, j_e) in CSR order, in one launch (two when a row
+ * is split) and without the nnz-sized scores and weights of the chain bsmr_sddmm, bsmr_softmax,
+ * bsmr_spmm:
+ *   p_e = dot(Q[i,:], K[j_e,:])                    fp32 accumulation
+ *   m_i = max_e p_e,  t_e = 2^((p_e - m_i) c),  l_i = sum_e t_e,  c = scale log2(e) rounded once
+ *   O[i,:] = (sum_e t_e V[j_e,:]) (1 / l_i)        fp32, M x Dv row-major
+ *   LSE[i] = m_i scale + ln(l_i)                   fp32, natural logarithm
+ * dQ (M x D), dK (N x D) and dV (N x Dv) are row-major and share one dtype (fp32, or fp16 / bf16
+ * accumulated in fp32); D and Dv may differ and follow the rules of the chain: D is a positive
+ * multiple of 16 (fp32) or 32 (fp16 / bf16), Dv a positive multiple of 16; rows of K and V hold at
+ * most 1024 bytes; else BSMR_ERR_UNSUPPORTED (as for an unknown dtype). scale follows
+ * bsmr_softmax's rule. dQ, dK, dV and dO are 16-byte aligned; dLse (M fp32) may be NULL; a null
+ * plan or other pointer, a misaligned pointer or a bad scale give BSMR_ERR_INVALID. On every error
+ * the outputs are untouched. dO must not alias an input.
+ * Conventions:
+ *   every element of O and LSE is written, so the caller clears nothing; an empty row gives O = 0
+ *   and LSE = -inf;
+ *   a row with a NaN or +inf score (a NaN / inf in its Q row or in a K row it references) is NaN
+ *   in O and LSE; -inf scores get weight 0, and a row whose scores are all -inf gives O = 0 and
+ *   LSE = -inf; a NaN / inf in a V row reaches the O rows that reference it; no other row changes
+ *   by a bit.
+ * A row's entries are cut into consecutive CSR ranges of at most `chunk` entries (256), one wave
+ * each; a row of several segments goes through plan-owned scratch of partials x (Dv + 2) floats,
+ * where each partial is rescaled exactly once against the row's maximum and added in segment order.
+ * No atomics: the summation order is a function of the row's length, D, Dv and dtype alone
+ * (DESIGN.md §13), so results are bitwise reproducible, equal between a lazily built and a
+ * prepared plan, and equal between two plans that hold a row of that length. Launches of one plan
+ * share the scratch: order them on one stream (or with events), as for one SpMM side.
+ * Asynchronous on `stream` once the plan's attention lists exist and the scratch covers Dv: the
+ * first launch builds them unless bsmr_plan_prepare_attention did, and on a capturing stream an
+ * unprepared plan gives BSMR_ERR_NOT_PREPARED and leaves the capture intact. At most two kernel
+ * launches per call. */
+int bsmr_attention(const bsmr_plan* plan, const void* dQ, const void* dK, const void* dV, uint32_t D,
+                   uint32_t Dv, int dtype, float scale, float* dO, float* dLse, void* stream);
+/* Build now what the first bsmr_attention at Dv would build inside the call: the segment lists and
+ * the scratch of the split rows. Synchronous and idempotent; a larger Dv grows the scratch. D and
+ * Dv must be legal for some dtype. The lists are the attention path's own: bsmr_plan_prepare_spmm
+ * (whatever its chunk) does not change them, and bsmr_plan_recolumn keeps them. */
+int bsmr_plan_prepare_attention(const bsmr_plan* plan, uint32_t D, uint32_t Dv);
+/* 1 when a launch at (D, Dv) would make no allocation, copy or synchronisation, else 0 (also 0 on
+ * bad arguments, with bsmr_last_error set). No device call. */
+int bsmr_plan_attention_prepared(const bsmr_plan* plan, uint32_t D, uint32_t Dv);
+typedef struct {
+    uint32_t segments;    /* waves of the launch (every row has at least one) */
+    uint32_t split_rows;  /* rows with more than `chunk` entries */
+    uint32_t partials;    /* their segments = partial slots of scratch */
+    uint32_t max_row;     /* entries of the longest row */
+    uint32_t chunk;       /* the library's constant (always filled) */
+} bsmr_attention_stats;
+/* Counts are zeros while the lists are not built. */
+int bsmr_plan_attention_stats(const bsmr_plan* plan, bsmr_attention_stats* out);
+/* The constants of the attention path without a plan (either pointer may be NULL): entries per
+ * segment and the largest K / V row in bytes. */
+void bsmr_attention_limits(uint32_t* chunk, uint32_t* max_row_bytes);
 
 /* Timing: run `iters` back-to-back SDDMMs on `stream`, timing each kernel with HIP events on
  * that stream (BSMR_ERR_UNSUPPORTED on a capturing stream). Outputs average ms per launch of the dense-tile kernel, the residual kernel and

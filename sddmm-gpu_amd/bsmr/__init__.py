@@ -8,8 +8,8 @@ Reference interface mirrored (paths relative to the reference root):
   * evaluationReordering                               -> Plan.evaluate   (src/BSMR.cpp:826-994)
 Beyond the reference: the gradients of the SDDMM as SpMM over the same plan (Plan.spmm,
 Plan.spmm_t, Plan.sddmm_backward), the row softmax over the plan's pattern (Plan.softmax,
-Plan.softmax_backward), and bsmr.autograd, which wraps SDDMM, softmax and SpMM for torch.autograd
-and composes them into sparse attention.
+Plan.softmax_backward), the fused sparse attention forward (Plan.attention), and bsmr.autograd,
+which wraps SDDMM, softmax and SpMM for torch.autograd and composes them into sparse attention.
 
 Every call goes through the HIP library; there is no CPU fallback. If the shared library is
 missing the import fails loudly (build it with `make -C sddmm-gpu_amd` or
@@ -157,6 +157,16 @@ class SoftmaxStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class AttentionStats(C.Structure):
+    """bsmr_attention_stats: the fused attention's segment lists (counts zero when not built) and
+    the library's constant chunk."""
+    _fields_ = [("segments", C.c_uint32), ("split_rows", C.c_uint32), ("partials", C.c_uint32),
+                ("max_row", C.c_uint32), ("chunk", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 # bsmr_softmax_item.kind beside a packed run's lane-group width 1 .. 64
 SOFTMAX_WAVE = 0x100
 SOFTMAX_BLOCK = 0x200
@@ -184,6 +194,8 @@ EXPORTS = [
     "bsmr_softmax", "bsmr_softmax_backward", "bsmr_plan_prepare_softmax",
     "bsmr_plan_softmax_prepared", "bsmr_plan_softmax_stats", "bsmr_softmax_items",
     "bsmr_softmax_limits",
+    "bsmr_attention", "bsmr_plan_prepare_attention", "bsmr_plan_attention_prepared",
+    "bsmr_plan_attention_stats", "bsmr_attention_limits",
 ]
 
 _lib = None
@@ -290,6 +302,15 @@ def lib():
     L.bsmr_softmax_items.restype = C.c_int
     L.bsmr_softmax_limits.argtypes = [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     L.bsmr_softmax_limits.restype = None
+    L.bsmr_attention.argtypes = [vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_int, C.c_float, vp, vp, vp]
+    L.bsmr_attention.restype = C.c_int
+    for f in ("bsmr_plan_prepare_attention", "bsmr_plan_attention_prepared"):
+        getattr(L, f).argtypes = [vp, C.c_uint32, C.c_uint32]
+        getattr(L, f).restype = C.c_int
+    L.bsmr_plan_attention_stats.argtypes = [vp, C.POINTER(AttentionStats)]
+    L.bsmr_plan_attention_stats.restype = C.c_int
+    L.bsmr_attention_limits.argtypes = [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    L.bsmr_attention_limits.restype = None
     L.bsmr_plan_check.argtypes = [vp, C.c_uint32, C.c_int, C.c_int]
     L.bsmr_plan_check.restype = C.c_int
     L.bsmr_check_rphm_arrays.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32] + [_u32p] * 2 + \
@@ -599,6 +620,27 @@ class Plan:
         _check(lib().bsmr_plan_softmax_stats(self.h, C.byref(s)), "bsmr_plan_softmax_stats")
         return s.as_dict()
 
+    def attention(self, dQ, dK, dV, D, Dv, dO, dLse=0, scale=1.0, stream=0, dtype=F32):
+        """bsmr_attention: O (M x Dv fp32) = softmax(scale * S .* (Q K^T)) V per row of S in one
+        launch (two with split rows), without the nnz-sized scores and weights; dLse (M fp32, 0 =
+        none) receives max * scale + ln(sum). dQ (M x D), dK (N x D), dV (N x Dv) of one dtype;
+        every element of O and LSE is written."""
+        _check(lib().bsmr_attention(self.h, dQ, dK, dV, D, Dv, dtype, scale, dO, dLse or None,
+                                    stream or None), "bsmr_attention")
+
+    def prepare_attention(self, D, Dv):
+        """bsmr_plan_prepare_attention: build the attention lists and the scratch of the split rows
+        for Dv now, so that the first attention launch can be captured."""
+        _check(lib().bsmr_plan_prepare_attention(self.h, D, Dv), "bsmr_plan_prepare_attention")
+
+    def attention_prepared(self, D, Dv):
+        return bool(lib().bsmr_plan_attention_prepared(self.h, D, Dv))
+
+    def attention_stats(self):
+        s = AttentionStats()
+        _check(lib().bsmr_plan_attention_stats(self.h, C.byref(s)), "bsmr_plan_attention_stats")
+        return s.as_dict()
+
     def sddmm_backward(self, dG, dA, dB, K, dGA, dGB, stream=0, dtype=F32):
         """The gradients of P = sddmm(A, B) from dG = dL/dP (fp32, nnz): dGA (M x K fp32) =
         S(G) B and dGB (N x K fp32) = S(G)^T A. Either output may be 0: that side is skipped."""
@@ -708,6 +750,14 @@ def softmax_limits():
     w, b = C.c_uint32(), C.c_uint32()
     lib().bsmr_softmax_limits(C.byref(w), C.byref(b))
     return dict(wave_max=w.value, block_pass=b.value)
+
+
+def attention_limits():
+    """bsmr_attention_limits (host only): dict(chunk, max_row_bytes), the constants of
+    Plan.attention without a plan."""
+    c, b = C.c_uint32(), C.c_uint32()
+    lib().bsmr_attention_limits(C.byref(c), C.byref(b))
+    return dict(chunk=c.value, max_row_bytes=b.value)
 
 
 def sddmm_cpu(M, N, rowptr, colidx, K, A, B, threads=0):

@@ -9,13 +9,15 @@ and, over the same plan, the row softmax, the SpMM and their composition into sp
     spmm(plan, V, X)             Y = S(V) X                        Plan.spmm; dV = Plan.sddmm(dY, X),
                                                                    dX = Plan.spmm_t(V, dY)
     attention(plan, Q, K, V)     spmm(softmax(sddmm(Q, K), scale), V)
+    attention_fused(plan, Q, K, V)   the same O from one fused forward launch (Plan.attention) that
+                                     keeps no nnz-sized tensor; the backward recomputes P and W
 
 Every direction is the library's HIP kernels on torch.cuda.current_stream(); torch only owns the
 tensors. Importing this module imports torch (`import bsmr` alone does not).
 """
 import torch
 
-from . import BF16, F16, F32
+from . import BF16, F16, F32, attention_limits
 
 _DTYPES = {torch.float32: F32, torch.float16: F16, torch.bfloat16: BF16}
 
@@ -230,3 +232,93 @@ def attention(plan, Q, K, V, scale=None):
     if V.device != Q.device:
         raise ValueError(f"spmm: V ({V.device}) and Q ({Q.device}) must share one device")
     return spmm(plan, softmax(plan, sddmm(plan, Q, K), scale), V)
+
+
+def _validate_fused(plan, Q, K, V):
+    """attention's checks, one dtype for all three operands and rows within the fused kernel's byte
+    cap. Returns (D, Dv, dtype)."""
+    D, dtype = _validate(plan, Q, K)
+    Dv, vdtype = _validate_dense(plan, V)
+    if V.device != Q.device:
+        raise ValueError(f"spmm: V ({V.device}) and Q ({Q.device}) must share one device")
+    if vdtype != dtype:
+        raise ValueError(f"attention_fused: V ({V.dtype}) must share the dtype of Q and K ({Q.dtype})")
+    cap = attention_limits()["max_row_bytes"]
+    if max(D, Dv) * Q.element_size() > cap:
+        raise ValueError(f"attention_fused: rows of D = {D} / Dv = {Dv} {Q.dtype} exceed {cap} bytes")
+    return D, Dv, dtype
+
+
+class _AttentionFused(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, Q, K, V, plan, scale, want_lse):
+        D, Dv, dtype = _validate_fused(plan, Q, K, V)
+        O = torch.empty((plan.M, Dv), dtype=torch.float32, device=Q.device)
+        lse = torch.empty(plan.M, dtype=torch.float32, device=Q.device) if want_lse else None
+        plan.attention(Q.data_ptr(), K.data_ptr(), V.data_ptr(), D, Dv, O.data_ptr(),
+                       lse.data_ptr() if want_lse else 0, scale, stream=_stream(), dtype=dtype)
+        ctx.plan, ctx.scale, ctx.dims = plan, scale, (D, Dv, dtype)
+        ctx.save_for_backward(Q, K, V)
+        if not want_lse:
+            return O
+        ctx.mark_non_differentiable(lse)
+        return O, lse
+
+    @staticmethod
+    def backward(ctx, grad, *_):
+        Q, K, V = ctx.saved_tensors
+        plan, scale = ctx.plan, ctx.scale
+        D, Dv, dtype = ctx.dims
+        s = _stream()
+        vec = lambda: torch.empty(max(plan.nnz, 1), dtype=torch.float32, device=Q.device)  # noqa: E731
+        dO = grad.contiguous().float()
+        # P and W again, by the launches of the composed forward
+        P, W = vec(), vec()
+        plan.sddmm(Q.data_ptr(), K.data_ptr(), D, P.data_ptr(), stream=s, dtype=dtype)
+        plan.softmax(P.data_ptr(), W.data_ptr(), scale, stream=s)
+        # from here on exactly the launches of attention's backward (_Spmm, _Softmax, _Sddmm)
+        need_qk = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        gQ = gK = gV = None
+        if need_qk:
+            gW = vec()
+            plan.sddmm(dO.data_ptr(), V.float().data_ptr(), Dv, gW.data_ptr(), stream=s)
+        if ctx.needs_input_grad[2]:
+            gV = torch.empty((plan.N, Dv), dtype=torch.float32, device=Q.device)
+            plan.spmm_t(W.data_ptr(), dO.data_ptr(), Dv, gV.data_ptr(), stream=s)
+            gV = gV.to(V.dtype)
+        if need_qk:
+            gP = vec()
+            plan.softmax_backward(W.data_ptr(), gW.data_ptr(), gP.data_ptr(), scale, stream=s)
+            if ctx.needs_input_grad[0]:
+                gQ = torch.empty((plan.M, D), dtype=torch.float32, device=Q.device)
+            if ctx.needs_input_grad[1]:
+                gK = torch.empty((plan.N, D), dtype=torch.float32, device=Q.device)
+            plan.sddmm_backward(gP.data_ptr(), Q.data_ptr(), K.data_ptr(), D,
+                                gQ.data_ptr() if gQ is not None else 0,
+                                gK.data_ptr() if gK is not None else 0, stream=s, dtype=dtype)
+            gQ = None if gQ is None else gQ.to(Q.dtype)
+            gK = None if gK is None else gK.to(K.dtype)
+        return gQ, gK, gV, None, None, None
+
+
+def attention_fused(plan, Q, K, V, scale=None, return_lse=False):
+    """O (M, Dv) float32 of attention(plan, Q, K, V, scale) from one fused forward launch
+    (Plan.attention: no nnz-sized scores or weights are written), and with return_lse=True also
+    LSE (M,) float32 = max * scale + ln(sum) per row (-inf for an empty row), returned
+    non-differentiable. Q, K and V share one dtype and their rows hold at most
+    attention_limits()["max_row_bytes"] bytes; otherwise attention's checks (D a positive multiple
+    of 16, of 32 for float16 / bfloat16; Dv of 16), with its ValueErrors, before any launch.
+
+    The forward saves Q, K and V only. The backward recomputes P = Plan.sddmm(Q, K) and W =
+    Plan.softmax(P, scale) and then runs exactly the launches of attention's backward; it does not
+    read O, so dQ, dK and dV are bitwise equal to those of attention. The price is one more SDDMM
+    and softmax in the backward; the gain is that no W (nnz values) is held between forward and
+    backward. O itself is summed in another order than attention's and agrees with it within the
+    two paths' error bounds, not bit for bit."""
+    if scale is None:
+        if not isinstance(Q, torch.Tensor) or Q.dim() != 2 or Q.shape[1] == 0:
+            raise ValueError("attention_fused: Q must be an (M, D) tensor with D > 0")
+        scale = Q.shape[1] ** -0.5
+    scale = _valid_scale("attention_fused", scale)
+    _validate_fused(plan, Q, K, V)
+    return _AttentionFused.apply(Q, K, V, plan, scale, bool(return_lse))

@@ -367,6 +367,21 @@ struct Plan {
     };
     mutable SoftmaxList softmax;
 
+    // fused sparse attention (attention.hip; bsmr_attention): the rows' segments of at most
+    // ATTN_CHUNK entries (spmm_lists at side 1: src is colidx and vpos the identity, so neither is
+    // kept), the split rows, and their partials: partials x scratchDv accumulator rows followed
+    // by partials (m, l) pairs. Built on first use or by bsmr_plan_prepare_attention, under
+    // layout_mu; its own lists, which bsmr_plan_prepare_spmm never touches, and which depend on S
+    // and the row order only, so build_columns keeps them
+    struct AttentionState {
+        bool built = false;
+        u32 nSegs = 0, nReds = 0, splitRows = 0, partials = 0, maxRow = 0, scratchDv = 0;
+        DevBuf<SpmmSeg> segs;
+        DevBuf<SpmmRed> reds;
+        DevBuf<float> scratch;
+    };
+    mutable AttentionState attention;
+
     int build_rows(const u32* h_rowptr, const u32* h_col);
     int build_columns();
     ~Plan() {

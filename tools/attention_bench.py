@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""Times the row softmax over the plan's pattern (forward, backward) and the whole sparse attention
-forward + backward beside the byte floors and the same softmax written with torch ops; one JSON
-line per case.
+"""Times the row softmax over the plan's pattern (forward, backward), the whole sparse attention
+forward + backward, and the attention forward alone as the composed chain and as the one fused
+launch, beside the byte floors and the same softmax written with torch ops; one JSON line per case.
 
     python3 tools/attention_bench.py [--cases C2,C3] [--steps 50] [--rounds 7] [--d 64]
 
@@ -13,6 +13,8 @@ Per case (the C2 nips-like and C3 cop20k-like stand-in patterns, fp32, D = Dv = 
       softmax, spmm; then sddmm and spmm_t for dW and dV, softmax_backward, spmm and spmm_t for dQ
       and dK): the hand composition that tests/test_gpu_attention_autograd.py shows bitwise equal
       to bsmr.autograd.attention, without the autograd allocations a capture would not time fairly;
+      composed_fwd: its first three launches (sddmm, softmax, spmm) on the same tensors;
+      fused_fwd: one Plan.attention on the same tensors (O and LSE written);
   * stream_us: the same calls issued on a stream between two events (how the torch chain is timed,
     so the two compare like for like);
   * torch_us: the softmax as a chain of torch ops on the same tensors, stream-timed: forward
@@ -20,7 +22,9 @@ Per case (the C2 nips-like and C3 cop20k-like stand-in patterns, fp32, D = Dv = 
     two products. Its result is compared with ours (max_abs_diff);
   * floor_us: 8 nnz + 4 (M + 1) bytes forward (P read, W written, rowptr) and 16 nnz + 4 (M + 1)
     backward (W and G read, dP written, and 4 nnz allowed for the second read of rows longer than
-    one pass), over 8 TB/s; floor_fraction = floor / graph.
+    one pass), over 8 TB/s; fused_fwd: Q and O, one read of every K and V row that some entry
+    references, colidx and LSE; floor_fraction = floor / graph;
+  * fused_over_composed: graph_us of fused_fwd / composed_fwd, and the largest |O_fused - O_composed|.
 """
 import argparse
 import json
@@ -101,6 +105,7 @@ def main():
         plan.prepare(D)
         plan.prepare_spmm(D, 3)
         plan.prepare_softmax()
+        plan.prepare_attention(D, D)
 
         def data(n, shape=None):
             t = torch.from_numpy(make_data(n)).to(dev) - 1.0  # uniform [-1, 1)
@@ -123,10 +128,22 @@ def main():
             plan.spmm(p(agP), p(K), D, p(agQ), stream=s)
             plan.spmm_t(p(agP), p(Q), D, p(agK), stream=s)
 
+        fO, fL = z(M, D), z(M)
+
+        def composed_fwd(s):
+            plan.sddmm(p(Q), p(K), D, p(aP), stream=s)
+            plan.softmax(p(aP), p(aW), scale, stream=s)
+            plan.spmm(p(aW), p(V), D, p(aO), stream=s)
+
+        def fused_fwd(s):
+            plan.attention(p(Q), p(K), p(V), D, D, p(fO), p(fL), scale, stream=s)
+
         ours = {
             "softmax_fwd": lambda s: plan.softmax(p(P), p(W), scale, stream=s),
             "softmax_bwd": lambda s: plan.softmax_backward(p(W), p(G), p(gP), scale, stream=s),
             "attention": attention,
+            "composed_fwd": composed_fwd,
+            "fused_fwd": fused_fwd,
         }
         graphs = {k: graph_of(f) for k, f in ours.items()}
         graph_us = alternate({k: g.replay for k, g in graphs.items()})
@@ -150,14 +167,22 @@ def main():
         check = {"softmax_fwd_max_abs_diff_vs_torch": (tW - W).abs().max().item(),
                  "softmax_bwd_max_abs_diff_vs_torch": (tgP - gP).abs().max().item()}
 
+        used = len(np.unique(ci))  # K and V rows that some entry references
         floor = {"softmax_fwd": (8 * nnz + 4 * (M + 1)) / HBM_BYTES_PER_S * 1e6,
-                 "softmax_bwd": (16 * nnz + 4 * (M + 1)) / HBM_BYTES_PER_S * 1e6}
+                 "softmax_bwd": (16 * nnz + 4 * (M + 1)) / HBM_BYTES_PER_S * 1e6,
+                 "fused_fwd": (4 * D * (2 * M + 2 * used) + 4 * nnz + 4 * M) / HBM_BYTES_PER_S * 1e6}
+        with torch.cuda.stream(gs):
+            composed_fwd(gs.cuda_stream)
+            fused_fwd(gs.cuda_stream)
+        gs.synchronize()
+        check["fused_vs_composed_max_abs_diff"] = (fO - aO).abs().max().item()
         line = {"case": case, "M": M, "N": N, "nnz": nnz, "D": D, "scale": scale, "steps": args.steps,
                 "rounds": args.rounds, "graph_us": graph_us, "stream_us": stream_us, "torch_us": torch_us,
                 "floor_us": {k: round(v, 3) for k, v in floor.items()},
                 "floor_fraction": {k: round(floor[k] / graph_us[k], 3) for k in floor},
                 "torch_over_ours_stream": {k: round(torch_us[k] / stream_us[k], 2) for k in torch_us},
-                "softmax_stats": plan.softmax_stats(), "check": check, "torch": torch.__version__}
+                "fused_over_composed": round(graph_us["fused_fwd"] / graph_us["composed_fwd"], 3),
+                "softmax_stats": plan.softmax_stats(), "attention_stats": plan.attention_stats(), "check": check, "torch": torch.__version__}
         print(json.dumps(line), flush=True)
 
 

@@ -1,12 +1,12 @@
 #!/usr/bin/env python3
 """Build gate: parse hipcc's -Rpass-analysis=kernel-resource-usage remarks and fail when an SDDMM
-kernel (k_sddmm*, k_sim_filter, k_spmm*, k_softmax*) spills VGPRs/SGPRs or uses scratch. Usage: check_kernel_resources.py <remarks>"""
+kernel (k_sddmm*, k_sim_filter, k_spmm*, k_softmax*, k_attention*) spills VGPRs/SGPRs or uses scratch. Usage: check_kernel_resources.py <remarks>"""
 import os
 import re
 import sys
 
 
-GATED = ("k_sddmm", "k_sim_filter", "k_spmm", "k_softmax")
+GATED = ("k_sddmm", "k_sim_filter", "k_spmm", "k_softmax", "k_attention")
 
 
 def gated(kern):
@@ -35,7 +35,7 @@ def main(path):
         sys.stderr.write("kernel resource check failed (spills/scratch):\n  " + "\n  ".join(bad) + "\n")
         return 1
     if seen == 0:
-        sys.stderr.write(f"kernel resource check: no k_sddmm / k_sim_filter / k_spmm / k_softmax kernels in {path}\n")
+        sys.stderr.write(f"kernel resource check: no k_sddmm / k_sim_filter / k_spmm / k_softmax / k_attention kernels in {path}\n")
         return 1
     return 0
 

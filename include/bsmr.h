@@ -172,7 +172,12 @@ typedef struct {
     int32_t col_blocks;        /* BSMR_COL_BLOCKS: column-block launch (blocks of original columns,
                                   B rows staged, A rows gathered per row run) for the whole plan: 0
                                   never, 1 always, 2 = wide patterns (N >= 2 M) with fewer than 0.9 x
-                                  the pieces of the row-block layout; -1 = 0 */
+                                  the pieces of the row-block layout; -1 = 0. The
+                                  launch gathers A rows through a 22-bit row field and a 32-bit
+                                  byte offset, so the column blocks exist only when M <= 2^22 and
+                                  M x row bytes < 2^32; on a taller A the setting is ignored, for
+                                  1 too: the row-block layout runs, stats rb_col_blocks stays
+                                  clear and no error is returned */
 } bsmr_tuning;
 
 void bsmr_tuning_default(bsmr_tuning* t);

@@ -838,6 +838,18 @@ extern "C" int bsmr_debug_launch_choice(const uint32_t* facts, int layout_rowblo
     return report(validate_launch_k("bsmr_debug_launch_choice", c.kind, K));
 }
 
+// debug: whether a plan of facts[0] = M rows and facts[1] = N columns with bsmr_tuning.col_blocks =
+// col_blocks builds the column-block candidate for rows of rowBytes (launch_select.hpp
+// col_block_candidate): 1 or 0, -1 without facts. Needs no device. Not in the header
+// (tests/test_launch_select_cpu.py)
+extern "C" int bsmr_debug_col_block_candidate(const uint32_t* facts, int col_blocks, uint32_t rowBytes) {
+    if (!facts) return -1;
+    PlanFacts f;
+    f.M = facts[0];
+    f.N = facts[1];
+    return col_block_candidate(f, col_blocks, rowBytes) ? 1 : 0;
+}
+
 // debug: the panel-range rules (launch_select.hpp check_panel_range) as entry point `who` reports
 // them for a plan of P panels whose (K, dtype) has row-block slot `slot` (-1: none): the status,
 // its text in bsmr_last_error. Needs no device. Not in the header
@@ -861,20 +873,22 @@ extern "C" int bsmr_debug_rb_form(const uint32_t* layoutFacts, const bsmr_tuning
     return BSMR_OK;
 }
 
-// debug: what bsmr_sddmm runs on this plan for (K, dtype): out[12] = the three words of
+// debug: what bsmr_sddmm runs on this plan for (K, dtype): out[13] = the three words of
 // bsmr_debug_launch_choice, then for the row-block kind the nine of bsmr_debug_rb_form for the
 // whole launch of the plan's layout (built on first use, as bsmr_debug_rb_items does; else
-// zeros). Not in the header (tests/sddmm_cases.py)
+// zeros) and whether that layout's output is packed (the CSR position in the metadata's low 22
+// bits, no `out` array). Not in the header (tests/sddmm_cases.py)
 extern "C" int bsmr_debug_plan_launch(const bsmr_plan* plan, uint32_t K, int dtype, uint32_t* out) {
     if (!plan || !out) return BSMR_ERR_INVALID;
     BSMR_CHECK(report(validate_kd("bsmr_debug_plan_launch", K, dtype)));
     const Plan& p = plan->p;
     const LaunchChoice c = choose_launch(p, K, dtype);
-    std::fill(out, out + 12, 0u);
+    std::fill(out, out + 13, 0u);
     put_choice(c, out);
     if (c.kind != Launch::RowBlock) return BSMR_OK;
     const Plan::RowBlockLayout* L = nullptr;
     BSMR_CHECK(whole_rb_layout(p, K, dtype, &L));
     put_form(rb_form(rb_layout_facts(*L), rb_launch_knobs(p), 3), out + 3);
+    out[12] = L->outPacked ? 1u : 0u;
     return BSMR_OK;
 }

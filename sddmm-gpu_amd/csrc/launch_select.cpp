@@ -21,6 +21,14 @@ int rb_slot(const PlanFacts& f, uint32_t K, int dtype) {
     return rby == 128 ? 0 : rby == 256 ? 1 : rby == 512 ? 2 : rby == 1024 ? 3 : rby == 2048 ? 4 : -1;
 }
 
+bool col_block_candidate(const PlanFacts& f, int col_blocks, uint32_t rowBytes) {
+    if (col_blocks != 1 && !(col_blocks == 2 && static_cast<uint64_t>(f.N) >= 2ull * f.M)) return false;
+    // the roles swapped, A's rows are the gathered ones: the metadata's 22-bit "column" holds an
+    // original row, and load_bcol's 32-bit byte offset runs over A. (Under rule 2 both follow from
+    // rb_slot: N >= 2 M, N <= 2^22 and N rowBytes < 2^32.)
+    return f.M <= (1u << 22) && static_cast<uint64_t>(f.M) * rowBytes < (1ull << 32);
+}
+
 bool use_dense(const PlanFacts& f, uint32_t K, int dtype) {
     // layout auto only (BSMR_LAYOUT_ROWBLOCK / _COLMAJOR force those launches); choose_launch asks
     // use_ptile first (tile-dominated fp16/bf16 plans, K in {64..512}: C5 block 7.8 -> 5.6 us)

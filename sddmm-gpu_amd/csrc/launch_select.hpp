@@ -36,6 +36,12 @@ struct PlanFacts {
 bool tile_dominated(const PlanFacts& f);
 // (K, dtype) -> row-block layout slot by row bytes (0..4: 128 B .. 2 KiB); -1: no row-block launch
 int rb_slot(const PlanFacts& f, uint32_t K, int dtype);
+// whether the whole-plan row-block launch of rows of rowBytes builds the column-block candidate
+// (Plan::col_blocks: 1 always, 2 for wide patterns N >= 2 M, else never). The candidate gathers A
+// rows the way the plain launch gathers B rows, so it exists only when M <= 2^22 and M rowBytes <
+// 2^32; otherwise it is skipped, for col_blocks = 1 too, and the launch runs the row-block layout
+// already built. bsmr_debug_col_block_candidate reports the value
+bool col_block_candidate(const PlanFacts& f, int col_blocks, uint32_t rowBytes);
 // fp16/bf16 patterns dense enough for whole MFMA tiles (sddmm_dense.hip); asked after use_ptile
 bool use_dense(const PlanFacts& f, uint32_t K, int dtype);
 // tile-dominated fp16/bf16 plans with K in {64, 128, 256, 512}: the panel-grouped tile launch

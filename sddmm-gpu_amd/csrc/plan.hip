@@ -1542,9 +1542,11 @@ std::shared_ptr<const Plan::RowBlockLayout> Plan::rowblock_layout(u32 rowBytes, 
             }
             // column blocks, B rows staged and A rows gathered (the roles swapped): always (1),
             // or (2) for wide patterns (N >= 2 M) when their pieces are below 0.9 x the chosen
-            // layout's (C2 nips-like 1,500 x 12,419: 93.5 K -> 75.8 K pieces, the same time)
+            // layout's (C2 nips-like 1,500 x 12,419: 93.5 K -> 75.8 K pieces, the same time); only
+            // while A stays inside the gather's 22-bit row field and 32-bit byte offset
+            // (launch_select.cpp col_block_candidate: else the layout above runs, no error)
             rb_use_cols[slot] = false;
-            if (col_blocks == 1 || (col_blocks == 2 && static_cast<u64>(N) >= 2ull * M)) {
+            if (col_block_candidate(launch_facts(*this), col_blocks, rowBytes)) {
                 RowBlockLayout& Lc = rblc[slot];
                 *err = build_rowblock_layout(Lc, rowBytes, 0, P, tmin, false, true);
                 if (*err != BSMR_OK) return nullptr;

@@ -140,20 +140,22 @@ def plan_launch(plan, K, dtype):
     """What bsmr_sddmm runs on `plan` for (K, dtype), as the library decides it (the debug export
     bsmr_debug_plan_launch, not in the header): dict(kind=a sddmm_cases kind, slot=the row-block
     slot or -1, row_bytes) and, for the row-block kind, the kernel form of the whole launch: lite,
-    pairs, dyn (booleans), NT, grid, ... (RB_FORM). Builds the row-block layout if no launch has."""
+    pairs, dyn (booleans), NT, grid, ... (RB_FORM) and packed (the layout keeps the CSR position in
+    its metadata words and no `out` array). Builds the row-block layout if no launch has."""
     import ctypes as C
 
     import bsmr
     f = bsmr.lib().bsmr_debug_plan_launch
     f.argtypes = [C.c_void_p, C.c_uint32, C.c_int, np.ctypeslib.ndpointer(np.uint32, flags="C_CONTIGUOUS")]
-    out = np.zeros(12, np.uint32)
+    out = np.zeros(13, np.uint32)
     assert f(plan.h, K, dtype, out) == 0, bsmr.lib().bsmr_last_error()
     w = [int(x) for x in out]
     d = dict(kind=LAUNCH_KINDS[w[0]], slot=w[1] - 1, row_bytes=w[2])
     if d["kind"] == "rowblock":
-        d.update(zip(RB_FORM, w[3:]))
+        d.update(zip(RB_FORM, w[3:12]))
         for k in RB_FORM[:5]:
             d[k] = bool(d[k])
+        d["packed"] = bool(w[12])
     return d
 
 

@@ -1,5 +1,6 @@
 """CPU: the host-only launch decision (csrc/launch_select.cpp) through its device-free debug
-exports bsmr_debug_launch_choice, bsmr_debug_rb_form and bsmr_debug_panel_range.
+exports bsmr_debug_launch_choice, bsmr_debug_rb_form, bsmr_debug_panel_range and
+bsmr_debug_col_block_candidate.
 
 The expected values come from the restatement below of the documented rules (DESIGN.md "Launch
 selection"), never from the library:
@@ -14,6 +15,7 @@ selection"), never from the library:
   launch           panel-tile, else dense-sampled, else row-block (a slot), else column-major (half
                    for fp16 / bf16, which needs K % 32 == 0); every launch needs K % 16 == 0, K > 0
   row-block form   rb_form_rule below
+  column blocks    col_block_rule below
 """
 import ctypes as C
 import itertools
@@ -325,3 +327,44 @@ def test_panel_range_codes_and_texts(who):
         assert panel_range(who, 3, 9, P, -1, dtype, False) == UNSUPPORTED
         assert last_error() == who + ": fp16/bf16 panel ranges need the row-block layout (half K in 128..1024)"
     assert panel_range(who, 3, 9, P, -1, F32, False) == OK  # fp32: the panel-major lists
+
+
+# ---- the column-block candidate ---------------------------------------------------------------------
+
+def col_block_candidate(M, N, col_blocks, row_bytes):
+    f = bsmr.lib().bsmr_debug_col_block_candidate
+    f.argtypes = [_u32p, C.c_int, C.c_uint32]
+    f.restype = C.c_int
+    return f(np.array([M, N, 0, 0, 0], np.uint32), col_blocks, row_bytes)
+
+
+def col_block_rule(M, N, col_blocks, row_bytes):
+    """The column-block launch swaps the operands: it gathers A rows through the metadata's 22-bit
+    column field and load_bcol's 32-bit byte offset, so the candidate (col_blocks = 1, or 2 on a
+    wide pattern) exists only when M <= 2^22 and M rowBytes < 2^32."""
+    asked = col_blocks == 1 or (col_blocks == 2 and N >= 2 * M)
+    return int(asked and M <= 1 << 22 and M * row_bytes < 1 << 32)
+
+
+def test_col_block_candidate_follows_the_rule():
+    for M, N, cb, rby in itertools.product(
+            (1, 1500, (1 << 21) - 1, 1 << 21, (1 << 21) + 64, (1 << 22) - 1, 1 << 22, (1 << 22) + 1),
+            (192, 2999, 3000, 1 << 22), (-1, 0, 1, 2, 3), (128, 256, 512, 1024, 2048)):
+        assert col_block_candidate(M, N, cb, rby) == col_block_rule(M, N, cb, rby), (M, N, cb, rby)
+
+
+def test_col_block_candidate_boundaries():
+    """Spelled out: A of 2^21 - 1, 2^21 and 2^21 + 64 rows of 2 KiB (one row under 4 GiB, exactly
+    4 GiB, past it) and of 2^22 and 2^22 + 1 rows of 128 B (the 22-bit row field), under
+    col_blocks = 1; a taller A never gets column blocks, whatever is asked."""
+    assert col_block_candidate((1 << 21) - 1, 192, 1, 2048) == 1
+    assert col_block_candidate(1 << 21, 192, 1, 2048) == 0
+    assert col_block_candidate((1 << 21) + 64, 192, 1, 2048) == 0
+    assert col_block_candidate((1 << 21) + 64, 192, 1, 1024) == 1  # 1 KiB rows: 2 GiB + 64 KiB
+    assert col_block_candidate(1 << 22, 192, 1, 128) == 1
+    assert col_block_candidate((1 << 22) + 1, 192, 1, 128) == 0
+    assert col_block_candidate(1 << 22, 192, 1, 1024) == 0  # 2^22 x 1 KiB = 2^32
+    # rule 2 asks for N >= 2 M first; what rb_slot admits then always fits
+    assert col_block_candidate(1500, 3000, 2, 128) == 1
+    assert col_block_candidate(1500, 2999, 2, 128) == 0
+    assert col_block_candidate(1500, 3000, 0, 128) == 0 and col_block_candidate(1500, 3000, -1, 128) == 0

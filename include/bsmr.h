@@ -126,7 +126,7 @@ typedef struct {
     int32_t l2_range_kb;       /* BSMR_L2_RANGE_KB: B bytes per XCD column range (>= 64);
                                   -1 = auto */
     int32_t stage_nt;          /* BSMR_STAGE_NT: row-block A staging with the nt cache policy, 0
-                                  never, 1 always, -1 auto */
+                                  never, 1 always, -1 auto (no layout takes it on auto: never) */
     int32_t rb_rows;           /* BSMR_RB_ROWS: rows per row block of the row-block launch (a
                                   multiple of 16 within 160 KiB of LDS); -1 = by the LDS budget */
     int32_t late_b;            /* BSMR_LATE_B: 1 = row-block phase-0 B columns loaded after the

@@ -1,7 +1,6 @@
 // capi.cpp — plan lifecycle, parity dumps, reorder statistics and sharding of the C ABI.
 #include <algorithm>
 #include <cmath>
-#include <cstdlib>
 #include <cstring>
 #include <unordered_map>
 #include <vector>
@@ -11,126 +10,7 @@
 
 using namespace bsmr;
 
-extern "C" void bsmr_plan_options_default(bsmr_plan_options* o) {
-    o->alpha = 0.3f;   // Options.hpp:40
-    o->delta = 0.3f;   // Options.hpp:41
-    o->free_mem_bytes = 0;
-    o->device = 0;
-    o->cluster_batch = 0;
-    o->exact_similarity = 0;
-    o->layout = BSMR_LAYOUT_AUTO;
-    o->lds_budget_kb = 0;
-    o->tuning = nullptr;
-}
-
-extern "C" void bsmr_tuning_default(bsmr_tuning* t) {
-    t->diag = 0;
-    t->tile_min_f32 = t->tile_min_half = t->piece_max = -1;
-    t->piece_weight = t->shard_piece_weight = t->dense_min = -1.0f;
-    t->orig_rows = t->orig_contig = t->dense_ks = t->dense_ns = t->out_staged = -1;
-    t->l2_range_kb = -1;
-    t->stage_nt = -1;
-    t->rb_rows = -1;
-    t->late_b = -1;
-    t->item_cap = -1.0f;
-    t->item_sched = -1;
-    t->out_packed = -1;
-    t->cluster_filter = -1;
-    t->pair_min_items = -1;
-    t->batches = -1;
-    t->ptile = t->ptile_tpi = -1;
-    t->piece_balance = -1;
-    t->col_blocks = -1;
-}
-
-extern "C" int bsmr_tuning_from_env(bsmr_tuning* t) {
-    int n = 0;
-    auto geti = [&](const char* name, int32_t& f) {
-        if (const char* v = std::getenv(name)) {
-            f = std::atoi(v);
-            ++n;
-        }
-    };
-    auto getf = [&](const char* name, float& f) {
-        if (const char* v = std::getenv(name)) {
-            f = static_cast<float>(std::atof(v));
-            ++n;
-        }
-    };
-    // tri-state switches: "0" never, "1" always, anything else auto
-    auto get3 = [&](const char* name, int32_t& f) {
-        if (const char* v = std::getenv(name)) {
-            f = v[0] == '0' ? 0 : v[0] == '1' ? 1 : -1;
-            ++n;
-        }
-    };
-    if (const char* v = std::getenv("BSMR_DIAG")) {
-        t->diag = static_cast<uint32_t>(std::atoi(v));
-        ++n;
-    }
-    geti("BSMR_TILE_MIN_F32", t->tile_min_f32);
-    geti("BSMR_TILE_MIN_HALF", t->tile_min_half);
-    geti("BSMR_PIECE_MAX", t->piece_max);
-    getf("BSMR_PIECE_WEIGHT", t->piece_weight);
-    getf("BSMR_SHARD_PIECE_WEIGHT", t->shard_piece_weight);
-    getf("BSMR_DENSE_MIN", t->dense_min);
-    get3("BSMR_ORIG_ROWS", t->orig_rows);
-    geti("BSMR_ORIG_CONTIG", t->orig_contig);
-    geti("BSMR_DENSE_KS", t->dense_ks);
-    geti("BSMR_DENSE_NS", t->dense_ns);
-    get3("BSMR_OUT_STAGED", t->out_staged);
-    geti("BSMR_L2_RANGE_KB", t->l2_range_kb);
-    get3("BSMR_STAGE_NT", t->stage_nt);
-    geti("BSMR_RB_ROWS", t->rb_rows);
-    geti("BSMR_LATE_B", t->late_b);
-    getf("BSMR_ITEM_CAP", t->item_cap);
-    get3("BSMR_ITEM_SCHED", t->item_sched);
-    get3("BSMR_OUT_PACKED", t->out_packed);
-    get3("BSMR_CLUSTER_FILTER", t->cluster_filter);
-    geti("BSMR_PAIR_MIN_ITEMS", t->pair_min_items);
-    get3("BSMR_BATCHES", t->batches);
-    get3("BSMR_PTILE", t->ptile);
-    geti("BSMR_PTILE_TPI", t->ptile_tpi);
-    get3("BSMR_PIECE_BALANCE", t->piece_balance);
-    geti("BSMR_COL_BLOCKS", t->col_blocks);
-    return n;
-}
-
 namespace {
-
-// launch-layout knobs onto a plan's fields; "auto" keeps the defaults. No device involved.
-void apply_tuning(Plan& p, const bsmr_tuning& t) {
-    p.diag = t.diag;
-    if (t.tile_min_f32 >= 0) p.tile_min_f32 = static_cast<u32>(t.tile_min_f32);
-    if (t.tile_min_half >= 0) p.tile_min_half = static_cast<u32>(t.tile_min_half);
-    if (t.piece_max >= 0) p.piece_max = std::min<u32>(RB_PIECE_MAX, std::max(1, t.piece_max));
-    if (t.piece_weight >= 0) p.piece_weight = t.piece_weight;
-    if (t.shard_piece_weight >= 0) p.shard_piece_weight = t.shard_piece_weight;
-    if (t.dense_min >= 0) p.dense_min = t.dense_min;
-    if (t.orig_rows >= 0) p.orig_rows = t.orig_rows ? 1 : 0;
-    if (t.orig_contig >= 0) p.orig_contig = t.orig_contig;
-    if (t.dense_ks >= 0) p.dense_ks = t.dense_ks;
-    if (t.dense_ns >= 0) p.dense_ns = t.dense_ns;
-    if (t.out_staged >= 0) p.out_staged = t.out_staged ? 1 : 0;
-    if (t.out_packed >= 0) p.out_packed = t.out_packed ? 1 : 0;
-    if (t.stage_nt >= 0) p.stage_nt = t.stage_nt ? 1 : 0;
-    if (t.rb_rows > 0) p.rb_rows_force = t.rb_rows;
-    if (t.late_b >= 0) p.late_b = t.late_b;
-    if (t.item_cap >= 0) p.item_cap = t.item_cap;
-    if (t.item_sched >= 0)
-        p.item_cost_cuts = p.item_lpt = p.small_sparse_rb = t.item_sched != 0;
-    if (t.cluster_filter >= 0) p.cluster_filter = t.cluster_filter ? 1 : 0;
-    if (t.pair_min_items >= 0) p.pair_min_items = static_cast<u32>(t.pair_min_items);
-    if (t.batches >= 0) p.batches = t.batches ? 1 : 0;
-    if (t.ptile >= 0) p.ptile_mode = t.ptile ? 1 : 0;
-    if (t.ptile_tpi >= 0) p.ptile_tpi = static_cast<u32>(std::min(64, t.ptile_tpi));
-    if (t.piece_balance >= 0) p.piece_balance = t.piece_balance ? 1 : 0;
-    if (t.col_blocks >= 0) p.col_blocks = std::min(2, t.col_blocks);
-    if (t.l2_range_kb >= 0) {
-        p.l2_range_kb = static_cast<u32>(std::max(64, t.l2_range_kb));
-        p.l2_range_user = true;
-    }
-}
 
 // device, stream and the launch / tuning options shared by bsmr_plan_create and
 // bsmr_plan_import_rows
@@ -147,20 +27,7 @@ int init_plan(Plan& p, const bsmr_plan_options& o) {
     p.alpha = o.alpha;
     p.delta = o.delta;
     p.exact_all = o.exact_similarity;
-    if (o.cluster_batch) p.cluster_batch = o.cluster_batch;
-    if (o.layout < BSMR_LAYOUT_AUTO || o.layout > BSMR_LAYOUT_COLMAJOR ||
-        (o.lds_budget_kb && (o.lds_budget_kb < 16 || o.lds_budget_kb > 160))) {
-        set_error("bsmr_plan: bad layout or lds_budget_kb");
-        return BSMR_ERR_INVALID;
-    }
-    p.use_rowblock = o.layout != BSMR_LAYOUT_COLMAJOR;
-    p.force_rowblock = o.layout == BSMR_LAYOUT_ROWBLOCK;
-    if (o.lds_budget_kb) {
-        p.rb_lds_kb = o.lds_budget_kb;
-        p.rb_lds_user = true;
-    }
-    if (o.tuning) apply_tuning(p, *o.tuning);
-    return BSMR_OK;
+    return report(apply_options(p.k, o));
 }
 
 // The CSR contract of bsmr_plan_create / bsmr_plan_import_rows (include/bsmr.h), checked on the
@@ -401,7 +268,7 @@ extern "C" int bsmr_plan_get_stats(const bsmr_plan* plan, bsmr_plan_stats* s) {
         s->rb_work_items[i] = L.rowBytes ? L.nWorkItems : 0;
         if (L.rowBytes && L.orig) s->rb_orig_rows |= 1u << i;
         if (L.rowBytes && L.cols) s->rb_col_blocks |= 1u << i;
-        if (L.rowBytes && rb_form(rb_layout_facts(L), rb_launch_knobs(p), 3).pairs) s->rb_pairs |= 1u << i;
+        if (L.rowBytes && rb_form(rb_layout_facts(L), p.k, 3).pairs) s->rb_pairs |= 1u << i;
         if (L.rowBytes && L.dynBatches) s->rb_batches |= 1u << i;
     }
     s->dense_sampled_tiles = p.dense.built ? p.dense.nonempty : 0;
@@ -724,10 +591,11 @@ extern "C" int bsmr_plan_shard_dtype(const bsmr_plan* plan, uint32_t K, int dtyp
 namespace {
 constexpr uint32_t RB_GEOM_WORDS = 13;
 
-RbKnobs debug_knobs(const bsmr_tuning* t) {
-    Plan p;  // defaults; no device, no stream
-    if (t) apply_tuning(p, *t);
-    return rb_knobs(p);
+// the knobs of tuning t (null: defaults)
+Knobs debug_knobs(const bsmr_tuning* t) {
+    Knobs k;
+    if (t) apply_tuning(k, *t);
+    return k;
 }
 }  // namespace
 
@@ -782,7 +650,8 @@ extern "C" int bsmr_debug_rb_schedule(const uint32_t* sorted_cols, uint64_t n, c
     in.rbEnd = rbEnd;
     in.keptBegin = keptBegin;
     in.NS = NS;
-    in.knobs = debug_knobs(t);
+    const Knobs k = debug_knobs(t);
+    in.knobs = &k;
     in.threads = static_cast<unsigned>(threads);
     RbScheduleOut o;
     rb_schedule(in, o);
@@ -823,16 +692,10 @@ void put_form(const RbForm& f, uint32_t* out) {
 extern "C" int bsmr_debug_launch_choice(const uint32_t* facts, int layout_rowblock, int force_rowblock,
                                         const bsmr_tuning* t, uint32_t K, int dtype, uint32_t* out) {
     if (!facts || !out) return BSMR_ERR_INVALID;
-    Plan p;  // defaults; no device, no stream
-    if (t) apply_tuning(p, *t);
-    p.M = facts[0];
-    p.N = facts[1];
-    p.nnz = facts[2];
-    p.nres = facts[3];
-    p.numDenseTiles = facts[4];
-    p.use_rowblock = layout_rowblock != 0;
-    p.force_rowblock = force_rowblock != 0;
-    const LaunchChoice c = choose_launch(p, K, dtype);
+    Knobs k = debug_knobs(t);
+    k.use_rowblock = layout_rowblock != 0;
+    k.force_rowblock = force_rowblock != 0;
+    const LaunchChoice c = choose_launch({facts[0], facts[1], facts[2], facts[3], facts[4]}, k, K, dtype);
     put_choice(c, out);
     BSMR_CHECK(report(validate_kd("bsmr_debug_launch_choice", K, dtype)));
     return report(validate_launch_k("bsmr_debug_launch_choice", c.kind, K));
@@ -847,7 +710,9 @@ extern "C" int bsmr_debug_col_block_candidate(const uint32_t* facts, int col_blo
     PlanFacts f;
     f.M = facts[0];
     f.N = facts[1];
-    return col_block_candidate(f, col_blocks, rowBytes) ? 1 : 0;
+    Knobs k;
+    k.col_blocks = col_blocks;  // (as given: not through apply_tuning's clamp)
+    return col_block_candidate(f, k, rowBytes) ? 1 : 0;
 }
 
 // debug: the panel-range rules (launch_select.hpp check_panel_range) as entry point `who` reports
@@ -866,10 +731,8 @@ extern "C" int bsmr_debug_panel_range(const char* who, uint32_t p0, uint32_t p1,
 extern "C" int bsmr_debug_rb_form(const uint32_t* layoutFacts, const bsmr_tuning* t, uint32_t mode,
                                   uint32_t* out) {
     if (!layoutFacts || !out) return BSMR_ERR_INVALID;
-    Plan p;
-    if (t) apply_tuning(p, *t);
     const uint32_t* w = layoutFacts;
-    put_form(rb_form({w[0], w[1], w[2], w[3], w[4], w[5] != 0, w[6] != 0}, rb_launch_knobs(p), mode), out);
+    put_form(rb_form({w[0], w[1], w[2], w[3], w[4], w[5] != 0, w[6] != 0}, debug_knobs(t), mode), out);
     return BSMR_OK;
 }
 
@@ -888,7 +751,7 @@ extern "C" int bsmr_debug_plan_launch(const bsmr_plan* plan, uint32_t K, int dty
     if (c.kind != Launch::RowBlock) return BSMR_OK;
     const Plan::RowBlockLayout* L = nullptr;
     BSMR_CHECK(whole_rb_layout(p, K, dtype, &L));
-    put_form(rb_form(rb_layout_facts(*L), rb_launch_knobs(p), 3), out + 3);
+    put_form(rb_form(rb_layout_facts(*L), p.k, 3), out + 3);
     out[12] = L->outPacked ? 1u : 0u;
     return BSMR_OK;
 }

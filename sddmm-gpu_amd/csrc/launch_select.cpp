@@ -3,33 +3,35 @@
 
 #include <cstring>
 
+#include "knobs.hpp"
+
 namespace bsmr {
 
 bool tile_dominated(const PlanFacts& f) {
     return static_cast<uint64_t>(f.nres) * 4 < static_cast<uint64_t>(f.numDenseTiles) * 16;
 }
 
-int rb_slot(const PlanFacts& f, uint32_t K, int dtype) {
-    if (f.N > (1u << 22) || !f.use_rowblock) return -1;
+int rb_slot(const PlanFacts& f, const Knobs& k, uint32_t K, int dtype) {
+    if (f.N > (1u << 22) || !k.use_rowblock) return -1;
     // tile-dominated plans (e.g. 16x16 block masks): one tile per wave with A from L2 beats
     // staging row blocks (C5 block mask: 8.9 vs 11.1 us); row blocks pay off once the residual
     // carries a quarter of the work (a tile ~ 16 entries)
-    if (!f.force_rowblock && tile_dominated(f)) return -1;
+    if (!k.force_rowblock && tile_dominated(f)) return -1;
     const uint32_t rby = K * (dtype == LS_F32 ? 4u : 2u);
     // the row-block kernel addresses B with 32-bit byte offsets (load_bcol): B < 4 GiB
     if (static_cast<uint64_t>(f.N) * rby >= (1ull << 32)) return -1;
     return rby == 128 ? 0 : rby == 256 ? 1 : rby == 512 ? 2 : rby == 1024 ? 3 : rby == 2048 ? 4 : -1;
 }
 
-bool col_block_candidate(const PlanFacts& f, int col_blocks, uint32_t rowBytes) {
-    if (col_blocks != 1 && !(col_blocks == 2 && static_cast<uint64_t>(f.N) >= 2ull * f.M)) return false;
+bool col_block_candidate(const PlanFacts& f, const Knobs& k, uint32_t rowBytes) {
+    if (k.col_blocks != 1 && !(k.col_blocks == 2 && static_cast<uint64_t>(f.N) >= 2ull * f.M)) return false;
     // the roles swapped, A's rows are the gathered ones: the metadata's 22-bit "column" holds an
     // original row, and load_bcol's 32-bit byte offset runs over A. (Under rule 2 both follow from
     // rb_slot: N >= 2 M, N <= 2^22 and N rowBytes < 2^32.)
     return f.M <= (1u << 22) && static_cast<uint64_t>(f.M) * rowBytes < (1ull << 32);
 }
 
-bool use_dense(const PlanFacts& f, uint32_t K, int dtype) {
+bool use_dense(const PlanFacts& f, const Knobs& k, uint32_t K, int dtype) {
     // layout auto only (BSMR_LAYOUT_ROWBLOCK / _COLMAJOR force those launches); choose_launch asks
     // use_ptile first (tile-dominated fp16/bf16 plans, K in {64..512}: C5 block 7.8 -> 5.6 us)
     // tile-dominated plans (16 x 16 block masks) keep the column-major tile launch below K = 512:
@@ -37,34 +39,34 @@ bool use_dense(const PlanFacts& f, uint32_t K, int dtype) {
     // bf16: dense 8.2 vs 8.9 us at K = 512, 5.95 vs 5.35 at 256, 4.7 vs 3.8 at 128;
     // profiles/r02c/dense_blockmask_ab.txt)
     if (K < 512 && tile_dominated(f)) return false;
-    return f.use_rowblock && !f.force_rowblock && dtype != LS_F32 && K % 64 == 0 &&
-           static_cast<double>(f.nnz) >= static_cast<double>(f.dense_min) * f.M * static_cast<double>(f.N);
+    return k.use_rowblock && !k.force_rowblock && dtype != LS_F32 && K % 64 == 0 &&
+           static_cast<double>(f.nnz) >= static_cast<double>(k.dense_min) * f.M * static_cast<double>(f.N);
 }
 
 // every BSMR tile on MFMA with the panel's A rows staged once per item (sddmm_half.hip
 // k_sddmm_ptile; BSMR_PTILE = 1: whenever the dtype and K allow, also beside a large residual; 0:
 // never)
-bool use_ptile(const PlanFacts& f, uint32_t K, int dtype) {
-    if (dtype == LS_F32 || f.ptile_mode == 0 || !f.use_rowblock || f.force_rowblock) return false;
+bool use_ptile(const PlanFacts& f, const Knobs& k, uint32_t K, int dtype) {
+    if (dtype == LS_F32 || k.ptile_mode == 0 || !k.use_rowblock || k.force_rowblock) return false;
     if ((K != 64 && K != 128 && K != 256 && K != 512) || f.numDenseTiles == 0) return false;
-    return f.ptile_mode == 1 || tile_dominated(f);
+    return k.ptile_mode == 1 || tile_dominated(f);
 }
 
-LaunchChoice choose_launch(const PlanFacts& f, uint32_t K, int dtype) {
+LaunchChoice choose_launch(const PlanFacts& f, const Knobs& k, uint32_t K, int dtype) {
     LaunchChoice c;
     c.rowBytes = K * (dtype == LS_F32 ? 4u : 2u);
-    c.slot = rb_slot(f, K, dtype);
-    c.kind = use_ptile(f, K, dtype)   ? Launch::Ptile
-             : use_dense(f, K, dtype) ? Launch::Dense
+    c.slot = rb_slot(f, k, K, dtype);
+    c.kind = use_ptile(f, k, K, dtype)   ? Launch::Ptile
+             : use_dense(f, k, K, dtype) ? Launch::Dense
              : c.slot >= 0            ? Launch::RowBlock
              : dtype != LS_F32        ? Launch::Half
                                       : Launch::ColMajor;
     return c;
 }
 
-RbForm rb_form(const RbLayoutFacts& L, const RbLaunchKnobs& k, uint32_t mode) {
+RbForm rb_form(const RbLayoutFacts& L, const Knobs& k, uint32_t mode) {
     RbForm f;
-    f.stageNt = k.stage_nt == 1 || (k.stage_nt == -1 && L.outLds != 0 && k.stage_nt_auto);
+    f.stageNt = k.stage_nt == 1;
     f.lateB = k.late_b != 0;
     // pairs (BSMR_DIAG & 16384 off): the whole launch, staged output by runs, rows of >= 512
     // bytes, at least pair_min_items (4096: 16 rounds of the chip's workgroup slots) items, an even

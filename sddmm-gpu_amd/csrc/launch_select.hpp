@@ -1,51 +1,46 @@
 // launch_select.hpp — which launch bsmr_sddmm runs for (K, dtype), which form of the row-block
 // kernel a layout takes, and the argument rules of the launch entry points: every such decision,
 // once. Standard library only: no HIP, no device, so it builds, runs and is tested on a machine
-// without a GPU. The rules read a few plain numbers (PlanFacts, RbLayoutFacts, RbLaunchKnobs) that
-// plan.hpp fills from a Plan; sddmm.hip, plan_check.cpp, spmm.hip and capi.cpp ask here and never
-// restate a rule. A success costs a few compares: messages are built on the error path only.
+// without a GPU. The rules read a few plain numbers (PlanFacts, RbLayoutFacts) that plan.hpp fills
+// from a Plan, and the plan's tuning (knobs.hpp Knobs) beside them; sddmm.hip, plan_check.cpp,
+// spmm.hip and capi.cpp ask here and never restate a rule. A success costs a few compares:
+// messages are built on the error path only.
 #pragma once
 
 #include <cstdint>
 #include <string>
 
+#include "verdict.hpp"
+
 namespace bsmr {
+
+struct Knobs;  // knobs.hpp
 
 // the values of bsmr.h that the rules use (plan.hpp asserts that they agree)
 constexpr int LS_F32 = 0, LS_F16 = 1, LS_BF16 = 2;
 constexpr int LS_OK = 0, LS_ERR_INVALID = 1, LS_ERR_UNSUPPORTED = 6;
 constexpr uint32_t LS_XCDS = 8;  // XCD_BUCKETS (plan.hpp)
 
-// an argument rule's verdict: code 0, or a bsmr_status and the bsmr_last_error text (the caller
-// calls set_error: plan.hpp report)
-struct Verdict {
-    int code = LS_OK;
-    std::string msg;
-};
-
-// what the launch decision reads from a Plan (plan.hpp launch_facts); the fields are documented at
-// Plan's members of the same name
+// what the launch decision reads from a Plan (plan.hpp launch_facts) beside its Knobs; the fields
+// are documented at Plan's members of the same name
 struct PlanFacts {
     uint32_t M = 0, N = 0, nnz = 0, nres = 0, numDenseTiles = 0;
-    bool use_rowblock = true, force_rowblock = false;
-    int ptile_mode = -1;
-    float dense_min = 0.05f;
 };
 
 // the residual carries under a quarter of the work (a tile ~ 16 entries): 16 x 16 block masks
 bool tile_dominated(const PlanFacts& f);
 // (K, dtype) -> row-block layout slot by row bytes (0..4: 128 B .. 2 KiB); -1: no row-block launch
-int rb_slot(const PlanFacts& f, uint32_t K, int dtype);
+int rb_slot(const PlanFacts& f, const Knobs& k, uint32_t K, int dtype);
 // whether the whole-plan row-block launch of rows of rowBytes builds the column-block candidate
-// (Plan::col_blocks: 1 always, 2 for wide patterns N >= 2 M, else never). The candidate gathers A
+// (Knobs::col_blocks: 1 always, 2 for wide patterns N >= 2 M, else never). The candidate gathers A
 // rows the way the plain launch gathers B rows, so it exists only when M <= 2^22 and M rowBytes <
 // 2^32; otherwise it is skipped, for col_blocks = 1 too, and the launch runs the row-block layout
 // already built. bsmr_debug_col_block_candidate reports the value
-bool col_block_candidate(const PlanFacts& f, int col_blocks, uint32_t rowBytes);
+bool col_block_candidate(const PlanFacts& f, const Knobs& k, uint32_t rowBytes);
 // fp16/bf16 patterns dense enough for whole MFMA tiles (sddmm_dense.hip); asked after use_ptile
-bool use_dense(const PlanFacts& f, uint32_t K, int dtype);
+bool use_dense(const PlanFacts& f, const Knobs& k, uint32_t K, int dtype);
 // tile-dominated fp16/bf16 plans with K in {64, 128, 256, 512}: the panel-grouped tile launch
-bool use_ptile(const PlanFacts& f, uint32_t K, int dtype);
+bool use_ptile(const PlanFacts& f, const Knobs& k, uint32_t K, int dtype);
 
 // the launch bsmr_sddmm / bsmr_sddmm_batch runs for (K, dtype); bsmr_debug_launch_choice reports
 // the values
@@ -57,19 +52,13 @@ struct LaunchChoice {
     int slot = -1;
     uint32_t rowBytes = 0;  // K * the operands' element size
 };
-LaunchChoice choose_launch(const PlanFacts& f, uint32_t K, int dtype);
+LaunchChoice choose_launch(const PlanFacts& f, const Knobs& k, uint32_t K, int dtype);
 
 // what the form of a row-block launch reads from its layout (Plan::RowBlockLayout's members of the
-// same name; plan.hpp rb_layout_facts) and from the plan's tuning (plan.hpp rb_launch_knobs)
+// same name; plan.hpp rb_layout_facts)
 struct RbLayoutFacts {
     uint32_t rowBytes = 0, NT = 1024, nItems = 0, nTilesKept = 0, outLds = 0;
     bool outRuns = false, dynBatches = false;
-};
-struct RbLaunchKnobs {
-    int stage_nt = -1;
-    bool stage_nt_auto = false;
-    int late_b = -1;
-    uint32_t pair_min_items = 4096, diag = 0;
 };
 // the kernel form and launch configuration of a row-block launch (sddmm.hip launch_rb, pick_rb)
 struct RbForm {
@@ -84,7 +73,7 @@ struct RbForm {
     uint32_t stageBlocks = 0;
 };
 // mode: 1 = dense tiles only, 2 = residual only, 3 = both (the whole launch)
-RbForm rb_form(const RbLayoutFacts& L, const RbLaunchKnobs& k, uint32_t mode);
+RbForm rb_form(const RbLayoutFacts& L, const Knobs& k, uint32_t mode);
 
 // K / dtype rules of every launch and prepare call, reported under the caller's name
 Verdict validate_kd(const char* who, uint32_t K, int dtype);

@@ -1508,7 +1508,7 @@ std::shared_ptr<const Plan::RowBlockLayout> Plan::rowblock_layout(u32 rowBytes, 
                                                                   u32 pa, u32 pb, int* err,
                                                                   bool keep) const {
     *err = BSMR_OK;
-    const u32 tmin = half ? tile_min_half : tile_min_f32;
+    const u32 tmin = half ? k.tile_min_half : k.tile_min_f32;
     if (pa == 0 && pb == P) {
         const int slot = rb_layout_slot(rowBytes, half);
         RowBlockLayout& L = rbl[slot];
@@ -1529,7 +1529,7 @@ std::shared_ptr<const Plan::RowBlockLayout> Plan::rowblock_layout(u32 rowBytes, 
             // original-order row blocks and keep the cheaper layout by the shard cost model
             const bool sparse = R && static_cast<u64>(nres) + static_cast<u64>(numDenseTiles) * 16 <
                                          64ull * R;
-            if (orig_rows == 1 || (orig_rows != 0 && sparse)) {
+            if (k.orig_rows == 1 || (k.orig_rows != 0 && sparse)) {
                 RowBlockLayout& Lo = rblo[slot];
                 *err = build_rowblock_layout(Lo, rowBytes, 0, P, tmin, true);
                 if (*err != BSMR_OK) return nullptr;
@@ -1537,7 +1537,7 @@ std::shared_ptr<const Plan::RowBlockLayout> Plan::rowblock_layout(u32 rowBytes, 
                 // are the same, and their LDS dot products cost far less than a gathered row
                 // (C3 cop20k-like: 1.03 M -> 0.80 M pieces, 109 -> 78 us)
                 const double c = L.nPieces + 16.0 * L.nTilesKept, co = Lo.nPieces;
-                rb_use_orig[slot] = orig_rows == 1 || co < 0.9 * c;
+                rb_use_orig[slot] = k.orig_rows == 1 || co < 0.9 * c;
                 if (!rb_use_orig[slot]) release_layout(Lo);  // keep the decision, free the candidate
             }
             // column blocks, B rows staged and A rows gathered (the roles swapped): always (1),
@@ -1546,13 +1546,13 @@ std::shared_ptr<const Plan::RowBlockLayout> Plan::rowblock_layout(u32 rowBytes, 
             // while A stays inside the gather's 22-bit row field and 32-bit byte offset
             // (launch_select.cpp col_block_candidate: else the layout above runs, no error)
             rb_use_cols[slot] = false;
-            if (col_block_candidate(launch_facts(*this), col_blocks, rowBytes)) {
+            if (col_block_candidate(launch_facts(*this), k, rowBytes)) {
                 RowBlockLayout& Lc = rblc[slot];
                 *err = build_rowblock_layout(Lc, rowBytes, 0, P, tmin, false, true);
                 if (*err != BSMR_OK) return nullptr;
                 const RowBlockLayout& Lw = rb_use_orig[slot] ? rblo[slot] : L;
                 const double cw = Lw.nPieces + 16.0 * Lw.nTilesKept;
-                rb_use_cols[slot] = col_blocks == 1 || Lc.nPieces < 0.9 * cw;
+                rb_use_cols[slot] = k.col_blocks == 1 || Lc.nPieces < 0.9 * cw;
                 if (!rb_use_cols[slot]) release_layout(Lc);
             }
         }
@@ -1582,7 +1582,7 @@ std::shared_ptr<const Plan::RowBlockLayout> Plan::rowblock_layout(u32 rowBytes, 
 
 std::shared_ptr<const Plan::RowBlockLayout> Plan::rowblock_ready(u32 rowBytes, bool half, u32 pa,
                                                                  u32 pb) const {
-    const u32 tmin = half ? tile_min_half : tile_min_f32;
+    const u32 tmin = half ? k.tile_min_half : k.tile_min_f32;
     if (pa == 0 && pb == P) {
         const int slot = rb_layout_slot(rowBytes, half);
         if (rbl[slot].rowBytes != rowBytes || rbl[slot].tileMin != tmin) return nullptr;
@@ -1622,33 +1622,6 @@ static_assert(sizeof(RbPiece) == sizeof(uint2) && alignof(RbPiece) == alignof(ui
                   offsetof(RbPiece, y) == offsetof(uint2, y),
               "RbPiece is uploaded as uint2");
 static_assert(RB_XCDS == XCD_BUCKETS && RB_COL_MASK == (1u << 22) - 1, "rb_schedule.hpp constants");
-
-RbKnobs rb_knobs(const Plan& p) {
-    RbKnobs k;
-    k.diag = p.diag;
-    k.rb_lds_kb = p.rb_lds_kb;
-    k.rb_lds_kb_staged = p.rb_lds_kb_staged;
-    k.l2_range_kb = p.l2_range_kb;
-    k.l2_range_kb_staged = p.l2_range_kb_staged;
-    k.rb_lds_user = p.rb_lds_user;
-    k.l2_range_user = p.l2_range_user;
-    k.out_staged = p.out_staged;
-    k.out_staged_min = p.out_staged_min;
-    k.rb_rows_force = p.rb_rows_force;
-    k.small_sparse_rb = p.small_sparse_rb;
-    k.batches = p.batches;
-    k.item_cost_cuts = p.item_cost_cuts;
-    k.item_lpt = p.item_lpt;
-    k.piece_max = p.piece_max;
-    k.piece_weight = p.piece_weight;
-    k.shard_piece_weight = p.shard_piece_weight;
-    k.item_cap = p.item_cap;
-    k.item_fixed = p.item_fixed;
-    k.orig_contig = p.orig_contig;
-    k.batch_min_phases = p.batch_min_phases;
-    k.piece_balance = p.piece_balance;
-    return k;
-}
 
 namespace {
 // what the device sort leaves on the host for the scheduler
@@ -1767,7 +1740,7 @@ static int sort_rb_entries(const Plan& p, Plan::RowBlockLayout& L, const RbGeome
 static int build_output_tables(const Plan& p, Plan::RowBlockLayout& L, const RbGeometry& g, u32 n,
                                const std::vector<uint2>& ient) {
     hipStream_t s = p.stream;
-    const u32 nnz = p.nnz, diag = p.diag, NT = g.NT, outCap = g.outCap;
+    const u32 nnz = p.nnz, diag = p.k.diag, NT = g.NT, outCap = g.outCap;
     DevBuf<uint8_t>& tmp = p.tmp;
     L.outLds = 0;
     L.outCap = 0;
@@ -1869,7 +1842,7 @@ static int build_output_tables(const Plan& p, Plan::RowBlockLayout& L, const RbG
                 L.outRuns = true;
             }
         }
-    } else if (n && p.out_packed != 0 && nnz <= (1u << 22)) {
+    } else if (n && p.k.out_packed != 0 && nnz <= (1u << 22)) {
         hipLaunchKernelGGL(k_pack_out, dim3((n + 255) / 256), dim3(256), 0, s, L.meta.data(),
                            L.out.data(), n);
         BSMR_HIP(hipGetLastError());
@@ -1904,7 +1877,7 @@ int Plan::build_rowblock_layout(RowBlockLayout& L, u32 rowBytes, u32 pa, u32 pb,
     // BSMR_DIAG & 524288: section times of this build to stderr (host-side layout cost)
     auto lap_t = std::chrono::steady_clock::now();
     auto lap = [&](const char* what) {
-        if (!(diag & 524288)) return;
+        if (!(k.diag & 524288)) return;
         const auto t = std::chrono::steady_clock::now();
         std::fprintf(stderr, "[rb layout %u B] %-12s %8.1f ms\n", rowBytes, what,
                      std::chrono::duration<double, std::milli>(t - lap_t).count());
@@ -1917,8 +1890,7 @@ int Plan::build_rowblock_layout(RowBlockLayout& L, u32 rowBytes, u32 pa, u32 pb,
         cus = 256;
     // residual entries of the range (original order: every stored entry)
     const u32 n0 = whole ? nnz : h_sparseValueOffsets[pb] - h_sparseValueOffsets[pa];
-    const RbKnobs knobs = rb_knobs(*this);
-    const RbGeometry g = rb_geometry(rowBytes, Rs, n0, NS, nnz, cus, orig, cols, knobs);
+    const RbGeometry g = rb_geometry(rowBytes, Rs, n0, NS, nnz, cus, orig, cols, k);
 
     SortedEntries se;
     BSMR_CHECK(sort_rb_entries(*this, L, g, pa, pb, tileMin, n0, se));
@@ -1931,7 +1903,7 @@ int Plan::build_rowblock_layout(RowBlockLayout& L, u32 rowBytes, u32 pa, u32 pb,
     in.keptBegin = se.keptBegin.empty() ? nullptr : se.keptBegin.data();
     in.NS = NS;
     in.geom = g;
-    in.knobs = knobs;
+    in.knobs = &k;
     in.lap = lap;  // cuts, segments, chunks, items, pieces
     RbScheduleOut sch;
     rb_schedule(in, sch);
@@ -2036,8 +2008,8 @@ int Plan::build_rows(const u32* h_rowptr, const u32* h_col) {
     u32 fW = 0;
     filter_used = false;
     filter_ms = 0.f;
-    const bool filter_ok = cluster_filter != 0 && !exact_all && alpha >= 0.01f && M - z >= 2 &&
-                           (cluster_filter == 1 || M >= filter_min_rows);
+    const bool filter_ok = k.cluster_filter != 0 && !exact_all && alpha >= 0.01f && M - z >= 2 &&
+                           (k.cluster_filter == 1 || M >= k.filter_min_rows);
     auto build_filter = [&]() -> int {
         size_t fr = 0, tot = 0;
         BSMR_HIP(hipMemGetInfo(&fr, &tot));
@@ -2057,8 +2029,8 @@ int Plan::build_rows(const u32* h_rowptr, const u32* h_col) {
         filter_used = true;
         return BSMR_OK;
     };
-    if (filter_ok && cluster_filter == 1) BSMR_CHECK(build_filter());
-    bool probe = filter_ok && cluster_filter != 1;
+    if (filter_ok && k.cluster_filter == 1) BSMR_CHECK(build_filter());
+    bool probe = filter_ok && k.cluster_filter != 1;
     ClusterArgs ca{};
     ca.fbits = filter_used ? fbits.data() : nullptr;
     ca.fW = fW;
@@ -2079,7 +2051,7 @@ int Plan::build_rows(const u32* h_rowptr, const u32* h_col) {
     // even number (block b of cluster c at reps[b * T + c]: 8- or 16-byte LDS reads of all T)
     const u32 NP = (nbpr + 3) & ~3u;
     u32 T = std::max<u32>(2, std::min<u32>(CL_TMAX, CL_LDS_BUDGET / (NP * 4)) & ~1u);
-    if (diag & 65536) T = std::min<u32>(T, 4);  // (experiment: 4 clusters per tile)
+    if (k.diag & 65536) T = std::min<u32>(T, 4);  // (experiment: 4 clusters per tile)
     ca.NP = NP;
     ca.T = T;
     const size_t lds_cl = static_cast<size_t>(T) * NP * 4 + sizeof(ClusterCtl);
@@ -2088,14 +2060,14 @@ int Plan::build_rows(const u32* h_rowptr, const u32* h_col) {
     // so more tiles than fit on the chip at once cannot deadlock (later ones start as earlier
     // ones finish); capped by the exact path's scratch (<= 256 MiB)
     const u32 Rcap = static_cast<u32>(std::max<u64>(
-        T, std::min<u64>(cluster_batch, (64ull << 20) / std::max<u32>(nbpr, 1)) / T * T));
+        T, std::min<u64>(k.cluster_batch, (64ull << 20) / std::max<u32>(nbpr, 1)) / T * T));
     const u32 tilesMax = Rcap / T;
     DevBuf<u32> cmpScratch;
     BSMR_CHECK(cmpScratch.alloc(static_cast<size_t>(tilesMax) * nbpr));
     BSMR_HIP(hipMemsetAsync(cmpScratch.data(), 0, static_cast<size_t>(tilesMax) * nbpr * sizeof(u32), s));
     ca.cmpScratch = cmpScratch.data();
     ca.ctrace = nullptr;
-    if (diag & 2048) {  // clustering timeline (tools/cluster_trace.py): 16 u64 per tile
+    if (k.diag & 2048) {  // clustering timeline (tools/cluster_trace.py): 16 u64 per tile
         BSMR_CHECK(prepare_trace((static_cast<size_t>(M) / T + 2) * 4, s));
         ca.ctrace = trace.data();
     }

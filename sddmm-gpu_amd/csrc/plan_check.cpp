@@ -293,7 +293,7 @@ public:
             case Launch::Ptile: {
                 {
                     std::lock_guard<std::mutex> g(p_.layout_mu);
-                    if (!p_.ptile_ready()) BSMR_CHECK(p_.build_ptile_layout(p_.ptile_tpi));
+                    if (!p_.ptile_ready()) BSMR_CHECK(p_.build_ptile_layout(p_.k.ptile_tpi));
                 }
                 BSMR_CHECK(ptile_layout(&r));
                 break;

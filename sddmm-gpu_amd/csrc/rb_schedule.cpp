@@ -27,7 +27,7 @@ u32 rowblock_rows(u32 rowBytes, u32 lds_kb, u32 R) {
 }
 
 RbGeometry rb_geometry(u32 rowBytes, u32 Rs, u32 n0, u32 NS, u32 nnz, int cus, bool orig, bool cols,
-                       const RbKnobs& k) {
+                       const Knobs& k) {
     RbGeometry g;
     g.rowBytes = rowBytes;
     g.orig = orig;
@@ -259,7 +259,7 @@ void balance_pieces(std::vector<RbPiece>& pcs, u32 NT, u32 G, double w) {
 // of columns and finds its part of every row block's column-sorted entries by binary search:
 // N + 1 counters in all, not one vector per row-block chunk.
 std::vector<u32> column_cuts(const RbScheduleIn& in, u32 NCR) {
-    const u32 NS = in.NS, nRB = in.geom.nRB, piece_max = in.knobs.piece_max;
+    const u32 NS = in.NS, nRB = in.geom.nRB, piece_max = in.knobs->piece_max;
     const u32* ent = in.entries;
     const u32* rbEnd = in.rbEnd;
     std::vector<u32> cuts(NCR + 1, NS);
@@ -288,7 +288,7 @@ std::vector<u32> column_cuts(const RbScheduleIn& in, u32 NCR) {
     std::vector<double> cnt(NS + 1, 0.0);
     for (u32 c = 0; c < NS; ++c)
         cnt[c] = static_cast<double>(ecount[c]) +
-                 (in.knobs.item_cost_cuts ? in.knobs.piece_weight * scount[c] : 0.0);
+                 (in.knobs->item_cost_cuts ? in.knobs->piece_weight * scount[c] : 0.0);
     double tot = 0;
     for (u32 c = 0; c < NS; ++c) tot += cnt[c];
     double run = 0;
@@ -312,8 +312,8 @@ struct Segments {
 };
 
 Segments build_segments(const RbScheduleIn& in, const std::vector<u32>& cuts, u32 NCR) {
-    const u32 nRB = in.geom.nRB, piece_max = in.knobs.piece_max;
-    const double piece_weight = in.knobs.piece_weight;
+    const u32 nRB = in.geom.nRB, piece_max = in.knobs->piece_max;
+    const double piece_weight = in.knobs->piece_weight;
     const u32* ent = in.entries;
     const size_t nseg = static_cast<size_t>(nRB) * NCR;
     Segments s;
@@ -396,7 +396,7 @@ private:
 
     const RbScheduleIn& in_;
     const RbGeometry& g_;
-    const RbKnobs& k_;
+    const Knobs& k_;
     const Segments& seg_;
     const u32 nRB_, NCR_;
     double total_ = 0, target_ = 0, cap_ = 0, splitTotal_ = 0;
@@ -411,7 +411,7 @@ private:
 };
 
 ChunkPlanner::ChunkPlanner(const RbScheduleIn& in, const Segments& seg)
-    : in_(in), g_(in.geom), k_(in.knobs), seg_(seg), nRB_(in.geom.nRB), NCR_(seg.NCR) {
+    : in_(in), g_(in.geom), k_(*in.knobs), seg_(seg), nRB_(in.geom.nRB), NCR_(seg.NCR) {
     const u32 m = g_.m;
     for (double c : seg_.cost) total_ += c;
     Q1_ = g_.perBucket * RB_XCDS;
@@ -652,7 +652,7 @@ void interleave(const Lists& lists, bool staged, std::vector<RbItem>& items, std
 // return its pieces. Also the dynamic-batch decision and the per-item / per-block statistics.
 void build_pieces(const RbScheduleIn& in, RbScheduleOut& out) {
     const RbGeometry& g = in.geom;
-    const RbKnobs& kn = in.knobs;
+    const Knobs& kn = *in.knobs;
     std::vector<RbItem>& items = out.items;
     std::vector<u32>& ends = out.ends;
     const u32 NT = g.NT, rowBytes = g.rowBytes;

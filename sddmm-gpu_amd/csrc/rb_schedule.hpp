@@ -1,7 +1,8 @@
 // rb_schedule.hpp — the host-only part of the row-block launch layout: block geometry
-// (rb_geometry) and item scheduling (rb_schedule). Standard library only: no HIP, no device, so it
-// builds, runs and is tested on a machine without a GPU. plan.hip (Plan::build_rowblock_layout)
-// sorts the entries on the device, calls these two, and uploads what they return.
+// (rb_geometry) and item scheduling (rb_schedule). Standard library and knobs.hpp only: no HIP, no
+// device, so it builds, runs and is tested on a machine without a GPU. plan.hip
+// (Plan::build_rowblock_layout) sorts the entries on the device, calls these two, and uploads
+// what they return.
 #pragma once
 
 #include <algorithm>
@@ -10,6 +11,8 @@
 #include <functional>
 #include <thread>
 #include <vector>
+
+#include "knobs.hpp"
 
 namespace bsmr {
 
@@ -24,27 +27,6 @@ struct alignas(16) RbItem {
 // layout-compatible with uint2
 struct alignas(8) RbPiece {
     uint32_t x, y;
-};
-
-// the tuning a layout depends on: the only place this unit learns about Plan's knobs
-// (plan.hip rb_knobs(const Plan&)); the fields are documented at Plan's members of the same name
-struct RbKnobs {
-    uint32_t diag = 0;
-    // geometry
-    uint32_t rb_lds_kb = 144, rb_lds_kb_staged = 120, l2_range_kb = 2048, l2_range_kb_staged = 4096;
-    bool rb_lds_user = false, l2_range_user = false;
-    int out_staged = -1;
-    uint64_t out_staged_min = 8ull << 20;
-    int rb_rows_force = -1;
-    bool small_sparse_rb = true;
-    int batches = -1;
-    // scheduling
-    bool item_cost_cuts = true, item_lpt = true;
-    uint32_t piece_max = 16;
-    double piece_weight = 4.0, shard_piece_weight = 4.0, item_cap = -1.0, item_fixed = 1024.0;
-    int orig_contig = 1;
-    double batch_min_phases = 2.0;
-    int piece_balance = 0;
 };
 
 struct RbGeometry {
@@ -65,7 +47,7 @@ uint32_t rowblock_rows(uint32_t rowBytes, uint32_t lds_kb, uint32_t R);
 // Block geometry of a layout over Rs staged rows holding n0 entries (before tile demotion), the
 // gathered index space of NS columns, on a device of cus compute units; nnz = the plan's.
 RbGeometry rb_geometry(uint32_t rowBytes, uint32_t Rs, uint32_t n0, uint32_t NS, uint32_t nnz, int cus,
-                       bool orig, bool cols, const RbKnobs& k);
+                       bool orig, bool cols, const Knobs& k);
 
 struct RbScheduleIn {
     // the entries sorted by (row block, column): words whose low 22 bits are the column (read in
@@ -78,7 +60,7 @@ struct RbScheduleIn {
     const uint32_t* keptBegin = nullptr;
     uint32_t NS = 0;
     RbGeometry geom;
-    RbKnobs knobs;
+    const Knobs* knobs = nullptr;  // the plan's tuning (Plan::k); read in place
     unsigned threads = 0;  // host threads (0: up to 16); the result does not depend on it
     std::function<void(const char*)> lap;  // called after each phase with its name (may be empty)
 };

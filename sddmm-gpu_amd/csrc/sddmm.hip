@@ -417,7 +417,7 @@ struct RbArgs {
     // to P[sortedPos[itemEnt.x + t]] at the end
     u32 outLds;
     u32 outPacked;  // 1: no out array, the metadata's low 22 bits are the CSR position
-    u32 stageNt;  // 1: stage the A rows with the nt policy (Plan::stage_nt)
+    u32 stageNt;  // 1: stage the A rows with the nt policy (Knobs::stage_nt)
     u32 lateB;    // 1: phase-0 B columns / metadata loaded after the staging barrier (late_b)
     u32 stageBlocks;  // 1 KiB LDS-DMA blocks that hold the image (RB * RBY / 1024); the rest of
                       // the workgroup's LDS is not staged
@@ -1480,7 +1480,7 @@ SddmmArgs make_args(const Plan& p, const void* dA, const void* dB, u32 K, float*
     a.sparseValues = p.sparseValues.data();
     a.sparseRel = p.sparseRel.data();
     a.sparseCol = p.sparseColIdx.data();
-    a.diag = p.diag;
+    a.diag = p.k.diag;
     return a;
 }
 
@@ -1522,7 +1522,7 @@ int get_iota(const Plan& p, const LaunchSite* at = nullptr) {
 int launch_rb(const Plan& p, const Plan::RowBlockLayout& L, const void* dA, const void* dB,
               float* dP, int dtype, u32 mode, hipStream_t s, u32 nb = 1, bool local = false) {
     if (L.nItems == 0) return BSMR_OK;
-    const RbForm f = rb_form(rb_layout_facts(L), rb_launch_knobs(p), mode);
+    const RbForm f = rb_form(rb_layout_facts(L), p.k, mode);
     RbArgs a{};
     a.A = static_cast<const char*>(dA);
     if (local)
@@ -1559,8 +1559,8 @@ int launch_rb(const Plan& p, const Plan::RowBlockLayout& L, const void* dA, cons
     a.denseCols = p.denseCols.data();
     a.blockValues = p.blockValues.data();
     a.mode = mode;
-    a.diag = p.diag;
-    if (p.diag & 32) {
+    a.diag = p.k.diag;
+    if (p.k.diag & 32) {
         BSMR_CHECK(p.prepare_trace(static_cast<size_t>(L.nItems) * (L.NT / 64), s));
         a.trace = p.trace.data();
     }
@@ -1593,7 +1593,7 @@ int launch_full(const Plan& p, SddmmArgs a, hipStream_t s, u32 nb = 1) {
     a.bA = static_cast<unsigned long long>(p.M) * a.K;
     a.bB = static_cast<unsigned long long>(p.N) * a.K;
     a.bP = p.nnz;
-    if (p.diag & 32) {
+    if (p.k.diag & 32) {
         BSMR_CHECK(p.prepare_trace((items + 3) / 4 * 4, s));
         a.trace = p.trace.data();
     }
@@ -1809,7 +1809,7 @@ extern "C" int bsmr_plan_prepare(const bsmr_plan* plan, uint32_t K, int dtype) {
     switch (c.kind) {
         case Launch::Ptile: {
             std::lock_guard<std::mutex> g(p.layout_mu);
-            if (!p.ptile_ready()) BSMR_CHECK(p.build_ptile_layout(p.ptile_tpi));
+            if (!p.ptile_ready()) BSMR_CHECK(p.build_ptile_layout(p.k.ptile_tpi));
             return BSMR_OK;
         }
         case Launch::Dense: {

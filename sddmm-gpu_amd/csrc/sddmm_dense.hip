@@ -306,7 +306,7 @@ int launch_dense(const Plan& p, const void* dA, const void* dB, u32 K, int dtype
     const u32 grid = per * XCD_BUCKETS;
     const dim3 g(grid, nb);
     a.trace = nullptr;
-    if (p.diag & 32) {
+    if (p.k.diag & 32) {
         BSMR_CHECK(p.prepare_trace(static_cast<size_t>(grid) * nb, s));
         a.trace = p.trace.data();
     }
@@ -315,10 +315,10 @@ int launch_dense(const Plan& p, const void* dA, const void* dB, u32 K, int dtype
     // all slower (C5 uniform 10.6-12.1 us vs 8.8-9.8)
     // eight waves (64 x 32 blocks, two per SIMD) when the tiles fill at most one workgroup per CU
     // (C5: 256 tiles)
-    const bool ks2 = p.dense_ks == 2 || (p.dense_ks != 1 && D.nonempty < 512);
+    const bool ks2 = p.k.dense_ks == 2 || (p.k.dense_ks != 1 && D.nonempty < 512);
     if (ks2) {
         const bool f16 = dtype == BSMR_F16;
-        switch (p.dense_ns) {
+        switch (p.k.dense_ns) {
             case 3:
                 if (f16) hipLaunchKernelGGL((k_sddmm_dense<1, 64, 3, 8>), g, dim3(512), 0, s, a);
                 else hipLaunchKernelGGL((k_sddmm_dense<2, 64, 3, 8>), g, dim3(512), 0, s, a);

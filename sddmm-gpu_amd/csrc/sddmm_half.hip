@@ -406,7 +406,7 @@ int launch_ptile(const Plan& p, const void* dA, const void* dB, u32 K, int dtype
         std::lock_guard<std::mutex> g(p.layout_mu);
         if (!p.ptile_ready()) {
             if (at) BSMR_CHECK(lazy_build_guard(*at));
-            BSMR_CHECK(p.build_ptile_layout(p.ptile_tpi));
+            BSMR_CHECK(p.build_ptile_layout(p.k.ptile_tpi));
         }
     }
     PtileArgs a{};
@@ -434,7 +434,7 @@ int launch_ptile(const Plan& p, const void* dA, const void* dB, u32 K, int dtype
         if (mode == 3) return BSMR_OK;
         grid = 1;  // a profiling split with nothing to run (no residual) still dispatches once
     }
-    if (p.diag & 32) {
+    if (p.k.diag & 32) {
         BSMR_CHECK(p.prepare_trace(static_cast<size_t>(grid) * nb, s));
         a.trace = p.trace.data();
     }

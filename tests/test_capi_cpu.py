@@ -147,6 +147,23 @@ def test_tuning_env_parser_matches_python_mapping(monkeypatch):
                        "piece_weight": 2.5, "l2_range_kb": 64, "diag": 8}
     # orig_rows "auto" equals the default (-1), so the C parser reports no change for it
     assert from_c == {k: v for k, v in from_py.items() if k != "orig_rows"}
+    # all 26 fields at once, by their kinds as include/bsmr.h documents them: the tri-state
+    # switches at "0" and at "1", the floats at "2.5", the integers at "3", BSMR_DIAG=8
+    fields = [f for f, _ in bsmr.Tuning._fields_]
+    tri = {"orig_rows", "out_staged", "stage_nt", "item_sched", "out_packed", "cluster_filter", "batches", "ptile",
+           "piece_balance"}
+    flt = {"piece_weight", "shard_piece_weight", "dense_min", "item_cap"}
+    assert len(fields) == 26 and tri | flt < set(fields)
+    for switch in ("0", "1"):
+        env = {bsmr.TUNING_ENV[f]: switch if f in tri else "2.5" if f in flt else "3" for f in fields}
+        env["BSMR_DIAG"] = "8"
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        want = {f: int(switch) if f in tri else 2.5 if f in flt else 3 for f in fields}
+        want["diag"] = 8
+        from_c, from_py = bsmr.tuning_from_env(), bsmr.tuning_from_env(env)
+        assert from_c == want and from_py == want, (switch, from_c, from_py)
+        assert all(type(from_c[f]) is type(from_py[f]) for f in fields)
     with pytest.raises(bsmr.BsmrError):
         bsmr._tuning_struct({"no_such_knob": 1})
 

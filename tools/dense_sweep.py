@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Dense-sampled vs gathered launch for fp16/bf16 uniform masks over a density sweep (the
-crossover that sets Plan::dense_min): per density, TFLOP/s (2 nnz K / time) of the layout-auto
+crossover that sets Knobs::dense_min): per density, TFLOP/s (2 nnz K / time) of the layout-auto
 launch with BSMR_DENSE_MIN = 0 (dense-sampled) and = 2 (row-block / column-major).
 
     python3 tools/dense_sweep.py --n 2048 --K 512 --densities 0.005,0.01,0.02,0.05,0.1

@@ -670,6 +670,35 @@ extern "C" int bsmr_debug_rb_schedule(const uint32_t* sorted_cols, uint64_t n, c
     return BSMR_OK;
 }
 
+// debug: the host-only run cutting of staged output (rb_schedule.hpp rb_cut_runs) on nItems items
+// given as ient = {first entry, entries} (2 u32 each) over sortedPos (every item's positions in
+// ascending order), for a workgroup of NT threads; threads as above. Needs no device. host_out =
+// {fits, n items, r runs, itemRuns (2 u32 each: first run, runs), runs (2 u32 each: position, slot |
+// length << 16)} with r = 0 when the table does not fit: *len = 3 + 2 n + 2 r; call with host_out =
+// null for the length. Not in the header (tests/test_store_ref_cpu.py)
+extern "C" int bsmr_debug_rb_runs(const uint32_t* sortedPos, uint64_t nPos, const uint32_t* ient,
+                                  uint64_t nItems, uint32_t NT, int threads, uint32_t* host_out,
+                                  uint64_t* len) {
+    if ((nPos && !sortedPos) || (nItems && !ient) || !len || NT == 0 || threads < 0 || nPos > 0xffffffffull)
+        return BSMR_ERR_INVALID;
+    for (uint64_t i = 0; i < nItems; ++i)
+        if (static_cast<uint64_t>(ient[2 * i]) + ient[2 * i + 1] > nPos || ient[2 * i + 1] > 65535u)
+            return BSMR_ERR_INVALID;
+    std::vector<RbPiece> ie(nItems);
+    for (uint64_t i = 0; i < nItems; ++i) ie[i] = RbPiece{ient[2 * i], ient[2 * i + 1]};
+    RbRuns rr;
+    rb_cut_runs(sortedPos, ie.data(), nItems, NT, rr, static_cast<unsigned>(threads));
+    *len = 3 + 2 * nItems + 2 * rr.runs.size();
+    if (!host_out) return BSMR_OK;
+    uint32_t* w = host_out;
+    *w++ = rr.fits;
+    *w++ = static_cast<uint32_t>(nItems);
+    *w++ = static_cast<uint32_t>(rr.runs.size());
+    for (const RbPiece& r : rr.itemRuns) { *w++ = r.x; *w++ = r.y; }
+    for (const RbPiece& r : rr.runs) { *w++ = r.x; *w++ = r.y; }
+    return BSMR_OK;
+}
+
 namespace {
 void put_choice(const LaunchChoice& c, uint32_t* out) {
     out[0] = static_cast<uint32_t>(c.kind);

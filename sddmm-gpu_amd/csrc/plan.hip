@@ -1801,42 +1801,15 @@ static int build_output_tables(const Plan& p, Plan::RowBlockLayout& L, const RbG
             BSMR_HIP(hipMemcpyAsync(hpos.data(), L.sortedPos.data(), n * sizeof(u32),
                                     hipMemcpyDeviceToHost, s));
             BSMR_HIP(hipStreamSynchronize(s));
-            // two passes on the host threads: count each item's runs, then (offsets by a scan)
-            // write them in item order into one flat table (no per-item vectors: C4 x1 holds
-            // ~60 M runs)
-            // a run is one wave store: at most 64 consecutive positions (an unsplit original-order
-            // item is one long run, which would leave all but one wave idle in the store pass)
-            auto runs_of = [&](size_t i, uint2* dst) {
-                const u32 e0 = ient[i].x, len = ient[i].y;
-                u32 nrun = 0;
-                for (u32 t = 0; t < len;) {
-                    u32 u = t + 1;
-                    while (u < len && u - t < 64 && hpos[e0 + u] == hpos[e0 + u - 1] + 1) ++u;
-                    if (dst) dst[nrun] = make_uint2(hpos[e0 + t], t | ((u - t) << 16));
-                    ++nrun;
-                    t = u;
-                }
-                return nrun;
-            };
-            std::vector<uint2> hir(ient.size(), make_uint2(0, 0));
-            par_for(ient.size(), [&](unsigned, size_t i0, size_t i1) {
-                for (size_t i = i0; i < i1; ++i) hir[i].y = runs_of(i, nullptr);
-            });
-            bool fits = true;
-            size_t nr = 0;
-            for (size_t i = 0; i < ient.size(); ++i) {
-                fits = fits && hir[i].y <= NT;
-                hir[i].x = static_cast<u32>(nr);
-                nr += hir[i].y;
-            }
-            std::vector<uint2> hr(fits ? nr : 0);
-            if (fits)
-                par_for(ient.size(), [&](unsigned, size_t i0, size_t i1) {
-                    for (size_t i = i0; i < i1; ++i) runs_of(i, hr.data() + hir[i].x);
-                });
+            // the host-only run cutting (rb_schedule.hpp rb_cut_runs)
+            RbRuns rr;
+            rb_cut_runs(hpos.data(), reinterpret_cast<const RbPiece*>(ient.data()), ient.size(), NT, rr);
+            const bool fits = rr.fits;
+            const uint2* hr = reinterpret_cast<const uint2*>(rr.runs.data());
+            const uint2* hir = reinterpret_cast<const uint2*>(rr.itemRuns.data());
             if (fits) {
-                BSMR_CHECK(L.runs.upload(hr.data(), std::max<size_t>(hr.size(), 1), s));
-                BSMR_CHECK(L.itemRuns.upload(hir.data(), std::max<size_t>(hir.size(), 1), s));
+                BSMR_CHECK(L.runs.upload(hr, std::max<size_t>(rr.runs.size(), 1), s));
+                BSMR_CHECK(L.itemRuns.upload(hir, std::max<size_t>(rr.itemRuns.size(), 1), s));
                 BSMR_HIP(hipStreamSynchronize(s));
                 L.sortedPos.release();
                 L.outRuns = true;

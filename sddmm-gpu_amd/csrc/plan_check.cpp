@@ -856,7 +856,9 @@ int run_checks(Checker& c, u32 K, int dtype, int verbose) {
 // plan array (which = a bsmr_array value 0..10) or of the launch layout bsmr_sddmm runs for
 // (K, dtype) (100: row-block entry metadata, 101: row-block piece words {first entry, column |
 // (length - 1) << 22} as 2 u32 per piece, 102: column-major residual output positions, 103: the
-// panel-tile launch's item descriptors), so a
+// panel-tile launch's item descriptors, 104: the staged-output positions sortedPos of a row-block
+// layout without a run table, 105: its run words {position, slot | length << 16} as 2 u32 per run),
+// so a
 // test can show that bsmr_plan_check catches the corruption. *old receives the previous value.
 extern "C" int bsmr_debug_plan_poke(bsmr_plan* plan, int which, uint64_t index, uint32_t value,
                                     uint32_t K, int dtype, uint32_t* old) {
@@ -878,7 +880,9 @@ extern "C" int bsmr_debug_plan_poke(bsmr_plan* plan, int which, uint64_t index, 
         case BSMR_ARR_SPARSE_RELATIVE_ROWS: base = p.sparseRel.data(); n = p.nres; break;
         case BSMR_ARR_SPARSE_COL_INDICES: base = p.sparseColIdx.data(); n = p.nres; break;
         case 100:
-        case 101: {
+        case 101:
+        case 104:
+        case 105: {
             const Plan::RowBlockLayout* L = nullptr;
             BSMR_CHECK(whole_rb_layout(p, K, dtype, &L));
             if (!L) {
@@ -888,9 +892,15 @@ extern "C" int bsmr_debug_plan_poke(bsmr_plan* plan, int which, uint64_t index, 
             if (which == 100) {
                 base = L->meta.data();
                 n = L->nEntries;
-            } else {
+            } else if (which == 101) {
                 base = reinterpret_cast<u32*>(L->pieces.data());
                 n = 2ull * L->nPieces;
+            } else if (which == 104) {  // (null with a run table: the positions are released)
+                base = L->outLds && !L->outRuns ? L->sortedPos.data() : nullptr;
+                n = base ? L->nEntries : 0;
+            } else {
+                base = L->outRuns ? reinterpret_cast<u32*>(L->runs.data()) : nullptr;
+                n = base ? 2ull * L->runs.size() : 0;
             }
             break;
         }

@@ -754,4 +754,41 @@ void rb_schedule(const RbScheduleIn& in, RbScheduleOut& out) {
     lap("pieces");
 }
 
+namespace {
+// the runs of one item's sorted positions pos[0, len): written to dst unless null; their number
+u32 runs_of(const u32* pos, u32 len, RbPiece* dst) {
+    u32 nrun = 0;
+    for (u32 t = 0; t < len;) {
+        u32 u = t + 1;
+        while (u < len && u - t < RB_RUN_MAX && pos[u] == pos[u - 1] + 1) ++u;
+        if (dst) dst[nrun] = RbPiece{pos[t], t | ((u - t) << 16)};
+        ++nrun;
+        t = u;
+    }
+    return nrun;
+}
+}  // namespace
+
+void rb_cut_runs(const u32* sortedPos, const RbPiece* ient, size_t nItems, u32 NT, RbRuns& out, unsigned threads) {
+    // two passes on the host threads: count each item's runs, then (offsets by a scan) write them
+    // in item order into one flat table (no per-item vectors: C4 x1 holds ~60 M runs)
+    out.itemRuns.assign(nItems, RbPiece{0, 0});
+    par_for(nItems, [&](unsigned, size_t i0, size_t i1) {
+        for (size_t i = i0; i < i1; ++i) out.itemRuns[i].y = runs_of(sortedPos + ient[i].x, ient[i].y, nullptr);
+    }, 2048, threads);
+    out.fits = true;
+    size_t nr = 0;
+    for (size_t i = 0; i < nItems; ++i) {
+        out.fits = out.fits && out.itemRuns[i].y <= NT;
+        out.itemRuns[i].x = static_cast<u32>(nr);
+        nr += out.itemRuns[i].y;
+    }
+    out.runs.assign(out.fits ? nr : 0, RbPiece{0, 0});
+    if (out.fits)
+        par_for(nItems, [&](unsigned, size_t i0, size_t i1) {
+            for (size_t i = i0; i < i1; ++i)
+                runs_of(sortedPos + ient[i].x, ient[i].y, out.runs.data() + out.itemRuns[i].x);
+        }, 2048, threads);
+}
+
 }  // namespace bsmr

@@ -1,8 +1,8 @@
 // rb_schedule.hpp — the host-only part of the row-block launch layout: block geometry
-// (rb_geometry) and item scheduling (rb_schedule). Standard library and knobs.hpp only: no HIP, no
-// device, so it builds, runs and is tested on a machine without a GPU. plan.hip
-// (Plan::build_rowblock_layout) sorts the entries on the device, calls these two, and uploads
-// what they return.
+// (rb_geometry), item scheduling (rb_schedule) and the run table of staged output (rb_cut_runs).
+// Standard library and knobs.hpp only: no HIP, no device, so it builds, runs and is tested on a
+// machine without a GPU. plan.hip (Plan::build_rowblock_layout) sorts the entries on the device,
+// calls these, and uploads what they return.
 #pragma once
 
 #include <algorithm>
@@ -78,6 +78,26 @@ struct RbScheduleOut {
 
 // Items, pieces and statistics of a layout from its sorted entries. Never touches a device.
 void rb_schedule(const RbScheduleIn& in, RbScheduleOut& out);
+
+// Run table of staged output (plan.hpp RowBlockLayout::outRuns): an item's slots are its entries
+// sorted by CSR position; up to RB_RUN_MAX consecutive positions form one run {first position,
+// first slot | length << 16}: one wave store (an unsplit original-order item is one long run,
+// which would leave all but one wave idle in the store pass, hence the cut). The table is used
+// when no item has more runs than the workgroup has lanes (one descriptor per lane); else the
+// layout keeps the per-result positions.
+constexpr uint32_t RB_RUN_MAX = 64;
+
+struct RbRuns {
+    bool fits = false;              // every item has at most NT runs
+    std::vector<RbPiece> itemRuns;  // per item {first run, runs} (the counts also when !fits)
+    std::vector<RbPiece> runs;      // the flat table in item order; empty when !fits
+};
+
+// sortedPos: every item's positions in ascending order at [ient[i].x, + ient[i].y) (slots below
+// 65536 per item: the caller's outCap). Never touches a device; the result does not depend on
+// `threads` (0: up to 16).
+void rb_cut_runs(const uint32_t* sortedPos, const RbPiece* ient, size_t nItems, uint32_t NT, RbRuns& out,
+                 unsigned threads = 0);
 
 // f(thread, begin, end) over [0, n) on up to `threads` host threads (0: up to 16): contiguous
 // ranges, each index visited once (results written per index are independent of the split)

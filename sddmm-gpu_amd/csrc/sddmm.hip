@@ -1977,6 +1977,128 @@ extern "C" int bsmr_debug_rb_pieces(const bsmr_plan* plan, uint32_t K, int dtype
     return BSMR_OK;
 }
 
+namespace {
+// the store export of layout L (bsmr_debug_rb_store; ext: the panel-range form of
+// bsmr_debug_rb_store_panels, whose header also holds the launch's form and whose item words
+// also hold the row block and whether the item is real)
+int store_export(const Plan& p, const Plan::RowBlockLayout& L, bool ext, uint32_t* host_out, uint64_t* len) {
+    const u64 cap = host_out ? *len : 0;
+    const u64 n = L.nItems;
+    const bool staged = L.outLds != 0;
+    std::vector<uint2> ient, irun, runs;
+    std::vector<u32> spos, iend;
+    std::vector<uint4> items;
+    if (staged) {
+        BSMR_CHECK(L.itemEnt.download(ient, p.stream));
+        if (L.outRuns) {
+            BSMR_CHECK(L.itemRuns.download(irun, p.stream));
+            BSMR_CHECK(L.runs.download(runs, p.stream));
+            u64 nr = 0;
+            for (u64 i = 0; i < n; ++i) nr += irun[i].y;
+            runs.resize(nr);  // (an empty table is uploaded as one word)
+        } else {
+            BSMR_CHECK(L.sortedPos.download(spos, p.stream));
+            spos.resize(L.nEntries);
+        }
+        ient.resize(n);
+    }
+    if (ext) {
+        BSMR_CHECK(L.items.download(items, p.stream));
+        BSMR_CHECK(L.itemEnd.download(iend, p.stream));
+        items.resize(n);
+        iend.resize(n);
+    }
+    const u64 nh = ext ? 12 : 8, per = ext ? 6 : 4;
+    const u64 head = nh + per * n;
+    const u64 full = head + (staged ? 2 * n + (L.outRuns ? 2 * n + 2 * runs.size() : spos.size()) : 0);
+    *len = full;
+    if (!host_out || cap < head) return BSMR_OK;
+    const RbForm f = rb_form(rb_layout_facts(L), p.k, 3);
+    const u32 hdr[12] = {L.outLds, L.outCap, L.outRuns, L.outPacked, L.NT, static_cast<u32>(n),
+                         PAIR_RUNS_PER_WAVE, XCD_BUCKETS, f.pairs, f.dyn, f.lite, f.grid};
+    std::copy(hdr, hdr + nh, host_out);
+    for (u64 i = 0; i < n; ++i) {
+        u32* w = host_out + nh + per * i;
+        w[0] = staged ? ient[i].y : (i < L.itemStat.size() ? L.itemStat[i].z : 0u);
+        w[1] = w[2] = w[3] = 0;
+        if (staged && L.outRuns) {
+            w[1] = irun[i].y;
+            for (u32 r = irun[i].x; r < irun[i].x + irun[i].y; ++r) {
+                const u32 l = runs[r].y >> 16;
+                w[2] = std::max(w[2], l);
+                w[3] = r == irun[i].x ? l : std::min(w[3], l);
+            }
+        }
+        if (ext) {
+            w[4] = items[i].x;
+            w[5] = !(items[i].y == items[i].z && items[i].w == iend[i]);  // (k_sddmm_rb's padding test)
+        }
+    }
+    if (!staged || cap < full) return BSMR_OK;
+    u32* w = host_out + head;
+    for (u64 i = 0; i < n; ++i) { *w++ = ient[i].x; *w++ = ient[i].y; }
+    if (L.outRuns) {
+        for (u64 i = 0; i < n; ++i) { *w++ = irun[i].x; *w++ = irun[i].y; }
+        for (const uint2& r : runs) { *w++ = r.x; *w++ = r.y; }
+    } else {
+        std::copy(spos.begin(), spos.end(), w);
+    }
+    return BSMR_OK;
+}
+}  // namespace
+
+// debug: how the whole-plan row-block layout of (K, dtype) writes P. host_out = the header {outLds,
+// outCap, outRuns, outPacked, NT, n item slots, PAIR_RUNS_PER_WAVE, XCD_BUCKETS}, then 4 u32 per
+// item slot in launch order {entries (itemEnt.y; unstaged: the item's entry count), runs
+// (itemRuns.y; 0 without a run table), longest run, shortest run (0 without runs)}, then the raw
+// tables of a staged layout: itemEnt (2 u32 per item: first entry, entries) and, with a run table,
+// itemRuns (2 u32 per item) and the r run words (2 u32 each), else sortedPos (one u32 per entry).
+// *len on entry = the u32 the buffer holds, on return = those of the whole export; the raw tables
+// are written only into a buffer that holds all of it (the header and the item words into one of
+// 8 + 4 n). *len = 0 without a row-block layout. Not in the header (tests/gpu_util.py rb_store)
+extern "C" int bsmr_debug_rb_store(const bsmr_plan* plan, uint32_t K, int dtype, uint32_t* host_out,
+                                   uint64_t* len) {
+    if (!plan || !len) return BSMR_ERR_INVALID;
+    const Plan& p = plan->p;
+    const Plan::RowBlockLayout* L = nullptr;
+    BSMR_CHECK(whole_rb_layout(p, K, dtype, &L));
+    if (!L) {
+        *len = 0;
+        return BSMR_OK;
+    }
+    return store_export(p, *L, false, host_out, len);
+}
+
+// debug: the same for the layout bsmr_sddmm_panels runs over panels [p0, p1) (the range's own
+// layout, built on first use as the launch builds it), with the launch's form: the header has 12
+// words, the eight above and {pairs, dynamic batches, lite, grid} of rb_form on that layout, and
+// an item slot has 6, the four above and {row block, 1 if the item is real (0: padding)}. *len = 0
+// when (K, dtype) has no row-block slot or the range is empty. Not in the header
+extern "C" int bsmr_debug_rb_store_panels(const bsmr_plan* plan, uint32_t K, int dtype, uint32_t p0,
+                                          uint32_t p1, uint32_t* host_out, uint64_t* len) {
+    if (!plan || !len) return BSMR_ERR_INVALID;
+    const Plan& p = plan->p;
+    LaunchChoice c;
+    BSMR_CHECK(panel_choice("bsmr_debug_rb_store_panels", p, K, dtype, p0, p1, false, &c));
+    if (c.slot < 0 || p0 == p1) {
+        *len = 0;
+        return BSMR_OK;
+    }
+    std::shared_ptr<const Plan::RowBlockLayout> L;
+    BSMR_CHECK(get_rb_layout(p, c.slot, dtype, p0, p1, &L));
+    return store_export(p, *L, true, host_out, len);
+}
+
+// debug: the store pass's constants {PAIR_RUNS_PER_WAVE, XCD_BUCKETS, RB_RUN_MAX}, for a host
+// model of a layout. Needs no device. Not in the header (tests/test_store_ref_cpu.py)
+extern "C" int bsmr_debug_rb_store_constants(uint32_t* out) {
+    if (!out) return BSMR_ERR_INVALID;
+    out[0] = PAIR_RUNS_PER_WAVE;
+    out[1] = XCD_BUCKETS;
+    out[2] = RB_RUN_MAX;
+    return BSMR_OK;
+}
+
 // debug timeline of the last traced launch (BSMR_DIAG & 32): 4 u64 per wave (not in the header)
 extern "C" int bsmr_debug_trace(const bsmr_plan* plan, uint64_t* host_out, uint64_t* len) {
     if (!plan) return BSMR_ERR_INVALID;

@@ -132,6 +132,84 @@ def rb_geometry(plan, K, dtype):
     return dict(rb=int(buf[0]), nt=int(buf[1]), items=int(buf[2]), row_bytes=int(buf[3]))
 
 
+STORE_HEAD = ("outLds", "outCap", "outRuns", "outPacked", "NT", "nItems", "prpw", "xcds")
+
+
+def rb_store(plan, K, dtype, raw=True, panels=None):
+    """How the whole-plan row-block layout of (K, dtype) writes P, through the library's debug
+    exports bsmr_debug_rb_store and bsmr_debug_rb_pieces (not in the header); None when that
+    (K, dtype) does not run the row-block launch. The dict store_cases.classify reads: the header
+    (STORE_HEAD; prpw = PAIR_RUNS_PER_WAVE, xcds = XCD_BUCKETS, the library's constants), per item
+    slot in launch order ent (entries), nruns, longest, shortest (0 without a run table), rb (row
+    block), real (not padding), and with raw the tables of a staged layout: itemEnt (n x 2) and
+    itemRuns (n x 2) + runs (r x 2), or sortedPos. Builds the layout if no launch has.
+    panels = (p0, p1): the same of the layout bsmr_sddmm_panels runs over that range
+    (bsmr_debug_rb_store_panels), with the form of its launch: pairs, dyn, lite (booleans), grid."""
+    import ctypes as C
+
+    import bsmr
+    L = bsmr.lib()
+    args = [C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.POINTER(C.c_uint64)]
+    L.bsmr_debug_rb_store.argtypes = args
+    L.bsmr_debug_rb_pieces.argtypes = args
+    L.bsmr_debug_rb_store_panels.argtypes = args[:3] + [C.c_uint32, C.c_uint32] + args[3:]
+    if panels is None:
+        export = lambda out, n: L.bsmr_debug_rb_store(plan.h, K, dtype, out, n)  # noqa: E731
+        nh, per = 8, 4
+    else:
+        export = lambda out, n: L.bsmr_debug_rb_store_panels(plan.h, K, dtype, panels[0], panels[1], out, n)  # noqa: E731
+        nh, per = 12, 6
+    n = C.c_uint64(0)
+    assert export(None, C.byref(n)) == 0, L.bsmr_last_error()
+    if n.value == 0:
+        return None
+    buf = np.zeros(n.value, np.uint32)  # (the whole export: a buffer of the item words alone gets no raw tables)
+    want = C.c_uint64(n.value)
+    assert export(buf.ctypes.data, C.byref(want)) == 0
+    assert want.value == n.value
+    d = dict(zip(STORE_HEAD, (int(x) for x in buf[:8])))
+    d["outRuns"], d["outPacked"] = bool(d["outRuns"]), bool(d["outPacked"])
+    ni = d["nItems"]
+    item = buf[nh:nh + per * ni].reshape(-1, per)
+    d.update(ent=item[:, 0].copy(), nruns=item[:, 1].copy(), longest=item[:, 2].copy(), shortest=item[:, 3].copy(),
+             itemEnt=None, itemRuns=None, runs=None, sortedPos=None)
+    if d["outLds"] and raw:
+        o = nh + per * ni
+        d["itemEnt"] = buf[o:o + 2 * ni].reshape(-1, 2).copy()
+        o += 2 * ni
+        if d["outRuns"]:
+            d["itemRuns"] = buf[o:o + 2 * ni].reshape(-1, 2).copy()
+            d["runs"] = buf[o + 2 * ni:].reshape(-1, 2).copy()
+            assert len(d["runs"]) == int(d["nruns"].sum())
+        else:
+            d["sortedPos"] = buf[o:].copy()
+            assert len(d["sortedPos"]) == int(d["ent"].sum())
+    if panels is not None:
+        d.update(pairs=bool(buf[8]), dyn=bool(buf[9]), lite=bool(buf[10]), grid=int(buf[11]),
+                 rb=item[:, 4].copy(), real=item[:, 5].astype(bool))
+        return d
+    assert L.bsmr_debug_rb_pieces(plan.h, K, dtype, None, C.byref(n)) == 0
+    pb = np.zeros(n.value, np.uint32)
+    assert L.bsmr_debug_rb_pieces(plan.h, K, dtype, pb.ctypes.data, C.byref(n)) == 0
+    assert int(pb[0]) == ni
+    items = pb[2:2 + 4 * ni].reshape(-1, 4)
+    ends = pb[2 + 4 * ni:2 + 5 * ni]
+    d["rb"] = items[:, 0].copy()
+    d["real"] = ~((items[:, 1] == items[:, 2]) & (items[:, 3] == ends))  # (k_sddmm_rb's padding test)
+    return d
+
+
+def store_constants():
+    """{prpw, xcds, run_max}: PAIR_RUNS_PER_WAVE, XCD_BUCKETS and RB_RUN_MAX from the library
+    (bsmr_debug_rb_store_constants; needs no device)."""
+    import bsmr
+    f = bsmr.lib().bsmr_debug_rb_store_constants
+    f.argtypes = [np.ctypeslib.ndpointer(np.uint32, flags="C_CONTIGUOUS")]
+    out = np.zeros(3, np.uint32)
+    assert f(out) == 0
+    return dict(prpw=int(out[0]), xcds=int(out[1]), run_max=int(out[2]))
+
+
 LAUNCH_KINDS = ("ptile", "dense", "rowblock", "half", "colmajor")  # csrc/launch_select.hpp Launch
 RB_FORM = ("stageNt", "lateB", "pairs", "lite", "dyn", "NT", "grid", "ldsBytes", "stageBlocks")
 
@@ -166,12 +244,13 @@ def path_evidence(case, plan):
     plan's tile offsets and the device's CU count."""
     from sddmm_cases import check_stats
     launch = plan_launch(plan, case.K, case.dtype)
-    geom = None
+    geom = store = None
     if case.kind == "rowblock":
         geom = rb_geometry(plan, case.K, case.dtype)
+        store = rb_store(plan, case.K, case.dtype, raw=False)
     elif case.kind == "ptile":
         cus = torch_cuda().cuda.get_device_properties(0).multi_processor_count
         geom = dict(block_offsets=plan.array("blockOffsets"), cus=int(cus))
-    bad = check_stats(case, plan.stats(), launch, geom)
+    bad = check_stats(case, plan.stats(), launch, geom, store)
     shown = dict(geom, block_offsets="...") if geom and "block_offsets" in geom else geom
     return [f"{b} (launch {launch}, geometry {shown}, stats {plan.stats()})" for b in bad]

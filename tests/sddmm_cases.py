@@ -14,6 +14,15 @@ Data:
     P == ref bit for bit: a dropped, doubled or misplaced term, a wrong row, a narrowed accumulator
     or store all fail with no tolerance.
   * signed_data: uniform [-1, 1) in fp32 (full mantissa), held to sddmm_bound.
+  * identity_data (patterns with M, N <= 4096, any K >= 16): operands that make stored entry
+    (i, j) equal 4096 i + j. Six columns pos[t] = t K // 6 carry everything, the rest is zero:
+    A[i, pos[k]] = digit_k(i) 16^k against B[j, pos[k]] = 4096, and A[i, pos[3 + k]] = 16^k against
+    B[j, pos[3 + k]] = digit_k(j) (base-16 digits, k = 0, 1, 2). Every operand has at most four
+    significant bits and magnitude <= 4096 (exact in fp16 and bf16), every product and every
+    partial sum in any order is an integer below 2^24 (exact in fp32). Every entry of a pattern
+    has its own value, so under assert_exact a misplaced, swapped, missing or doubled store fails
+    with certainty and names the entry; grid data catches a misplaced value only when the two
+    entries' values differ (tests/test_store_ref_cpu.py measures how often they do not).
 
 Bound: |P - ref| <= min(2 K, 8 sqrt K) 2^-24 S + 1e-6 scale.
   * 2 K 2^-24 S is the deterministic bound of a K-term fp32 sum of once-rounded products
@@ -80,7 +89,7 @@ import numpy as np
 
 from bsmr import BF16, F16, F32, synth
 from gpu_util import half_values
-from spmm_cases import entry_rows
+from spmm_cases import entry_rows, shuffled
 from spmm_cases import pattern as _spmm_pattern
 
 FREE = 288 * 1024 ** 3
@@ -90,8 +99,12 @@ DTYPE_NAME = {F32: "f32", F16: "f16", BF16: "bf16"}
 @functools.lru_cache(maxsize=None)
 def pattern(name):
     """(M, N, rowptr, colidx), built once per process; callers do not modify the arrays."""
-    if name in ("zipf", "empty", "hub"):
+    if name in ("zipf", "empty", "hub", "zipf_shuffled"):
         return _spmm_pattern(name)
+    if name == "band":  # 4096 x 4096, 215,552 entries: store_cases' large items (band_scatter)
+        return band_scatter(4096, 4096, 64, 1100, 36, seed=1)
+    if name == "band_shuffled":  # the same with every row's columns in random order
+        return shuffled(pattern("band"))
     if name == "blocky":  # test_gpu_parity.small_cases()["blocky"]: 147 full tiles, no residual
         return synth.block_mask(512, 16, 0.15, seed=4)
     if name == "blockmask":  # test_gpu_ptile's mask: 164 full tiles, 16 empty rows
@@ -103,6 +116,17 @@ def pattern(name):
     if name == "uniform300":  # 19 % dense, 3 x 3 tiles of 128 with ragged last tiles
         return synth.uniform_mask(300, 0.2, 7)
     raise KeyError(name)
+
+
+def band_scatter(M, N, band_rows, band_cols, per_row, seed):
+    """Rows [0, band_rows) hold the columns [0, band_cols) and nothing else (a dense band: column
+    runs of 16 in every row block, long runs of consecutive CSR positions); every other row holds
+    per_row columns drawn at random (single-entry column runs). Rows are column-sorted."""
+    rng = np.random.default_rng(seed)
+    cols = [np.arange(band_cols) if r < band_rows else np.sort(rng.choice(N, per_row, replace=False))
+            for r in range(M)]
+    rp = np.concatenate([[0], np.cumsum([len(c) for c in cols])]).astype(np.uint32)
+    return M, N, rp, np.concatenate(cols).astype(np.uint32)
 
 
 def as_seen(X, dtype):
@@ -147,6 +171,28 @@ def signed_data(n, seed):
     return np.random.default_rng(seed).random(int(n), dtype=np.float32) * np.float32(2) - np.float32(1)
 
 
+def identity_data(M, N, K):
+    """(A, B), fp32 M x K and N x K, with sum_k A[i, k] B[j, k] = 4096 i + j exactly in fp32, fp16
+    and bf16 in any summation order (module docstring). M, N <= 4096, K >= 16."""
+    assert M <= 4096 and N <= 4096 and K >= 16
+    pos = [t * K // 6 for t in range(6)]
+    A = np.zeros((M, K), np.float32)
+    B = np.zeros((N, K), np.float32)
+    i, j = np.arange(M), np.arange(N)
+    for k in range(3):
+        A[:, pos[k]] = ((i >> (4 * k)) & 15) * 16 ** k
+        B[:, pos[k]] = 4096
+        A[:, pos[3 + k]] = 16 ** k
+        B[:, pos[3 + k]] = (j >> (4 * k)) & 15
+    return A, B
+
+
+def identity_values(pat):
+    """What identity data makes of every stored entry: 4096 row + column (float64, CSR order)."""
+    M, _, rp, ci = pat
+    return 4096.0 * entry_rows(M, rp) + np.asarray(ci, np.float64)
+
+
 def sddmm_bound(S, K, scale=1.0):
     """Per entry: min(2 K, 8 sqrt K) 2^-24 S + 1e-6 scale (module docstring)."""
     return min(2.0 * K, 8.0 * np.sqrt(K)) * 2.0 ** -24 * np.asarray(S, np.float64) + 1e-6 * scale
@@ -178,12 +224,16 @@ def assert_bound(P, ref, S, K, what, kind, scale=1.0):
 @functools.lru_cache(maxsize=12)
 def reference(name, K, dtype, data, seed=0):
     """(A, B, P, S) of pattern `name`: operands as the kernel sees them (read-only, shared by the
-    cases of one (pattern, K, dtype)) and their float64 reference. data: "grid" or "signed"."""
+    cases of one (pattern, K, dtype)) and their float64 reference. data: "grid", "signed" or
+    "identity" (the same for every seed)."""
     pat = pattern(name)
     M, N, _, _ = pat
-    gen = {"grid": grid_data, "signed": signed_data}[data]
-    A = as_seen(gen(M * K, 101 + 2 * seed), dtype).reshape(M, K)
-    B = as_seen(gen(N * K, 202 + 2 * seed), dtype).reshape(N, K)
+    if data == "identity":
+        A, B = (as_seen(X, dtype) for X in identity_data(M, N, K))
+    else:
+        gen = {"grid": grid_data, "signed": signed_data}[data]
+        A = as_seen(gen(M * K, 101 + 2 * seed), dtype).reshape(M, K)
+        B = as_seen(gen(N * K, 202 + 2 * seed), dtype).reshape(N, K)
     P, S = sddmm_ref(pat, A, B)
     for x in (A, B, P, S):
         x.setflags(write=False)
@@ -194,7 +244,8 @@ def reference(name, K, dtype, data, seed=0):
 # rowblock, dense, ptile. proof: {evidence: value} checked by check_stats on top of the kind's own
 # evidence: rb_pairs / rb_batches / rb_orig_rows / rb_col_blocks (the stats bit of the row size set
 # or clear), rb_tiles (kept tiles > 0), rb_rows (rows per block), nt (threads per workgroup, from
-# the layout's geometry). need: a property of the plan the case relies on ("tiles": dense tiles
+# the layout's geometry), store (how P is written: "direct", "runs" or "positions"; default: runs
+# for out_staged = 1, else direct). need: a property of the plan the case relies on ("tiles": dense tiles
 # and a residual, "no_tiles", "no_residual").
 Case = collections.namedtuple("Case", "name kind pattern K dtype layout tuning proof need")
 
@@ -376,12 +427,13 @@ def plan_kwargs(case):
     return dict(alpha=0.3, delta=0.3, free_mem_bytes=FREE, layout=case.layout, tuning=case.tuning)
 
 
-def check_stats(case, st, launch, geom=None):
+def check_stats(case, st, launch, geom=None, store=None):
     """Failures (strings) of the evidence that `case` ran the path it names. st: Plan.stats() after
     the launch; launch: gpu_util.plan_launch, the library's account of the launch and of the
     row-block kernel's form; geom: gpu_util.rb_geometry of the launched layout (needed by an `nt`
     proof), or for the panel-tile launch dict(block_offsets=the plan's blockOffsets, cus=the
-    device's CU count)."""
+    device's CU count); store: gpu_util.rb_store of the launched row-block layout (how it
+    writes P: the staged cases are held to the store form they in fact run, a `store` proof)."""
     bad = []
 
     def want(cond, what):
@@ -460,4 +512,24 @@ def check_stats(case, st, launch, geom=None):
         want(lite == named, f"the case's knobs give lite = {lite}, its name {named}")
     want(launch["lite"] == lite, f"launch lite = {launch['lite']}, the case names {lite}")
     want(not (launch["lite"] and launch["pairs"]), "a launch both lite and paired")
+    # how P is written: direct stores, or staged through LDS slots and then by the
+    # run table ("runs") or by per-result positions ("positions"). The suite's patterns are
+    # column-sorted unless a case says otherwise, so no item has more runs than threads and every
+    # staged case (`rb_staged_*`, `rb_pairs_*`, `rb_batches_staged_*`, `rbx_full_*`, `rbx_pair_*`)
+    # runs the run table; pairs exist only with it (csrc/launch_select.cpp rb_form)
+    if store is not None:
+        staged = case.tuning.get("out_staged") == 1
+        form = "direct" if not store["outLds"] else "runs" if store["outRuns"] else "positions"
+        named = proof.get("store", "runs" if staged else "direct")
+        want(form == named, f"P is written by {form}, the case names {named} "
+                            f"(outLds {store['outLds']}, outCap {store['outCap']}, outRuns {store['outRuns']})")
+        want(store["NT"] == launch["NT"], f"store export NT {store['NT']} against the launch's {launch['NT']}")
+        want(not launch["pairs"] or form == "runs", "a paired launch without a run table")
+        if form == "direct":
+            want(store["outPacked"] == launch["packed"], "packed output against the launch's account")
+        if form == "runs":
+            real = store["real"]
+            want(int(store["nruns"][real].max(initial=0)) <= store["NT"], "an item with more runs than threads")
+            want(int(store["longest"][real].max(initial=0)) <= 64, "a run longer than a wave")
+            want(((store["nruns"][real] > 0) == (store["ent"][real] > 0)).all(), "an item with entries and no run")
     return bad

@@ -8,6 +8,10 @@ launch layouts it extends the check to.
 * the paired row-block kernel (k_sddmm_rb_pair) runs in this suite: pair_min_items lowers its
   4,096-item threshold, the plan stats show the pair launch, and XCD lists of odd length (a pair
   whose second item is padding) are among the cases;
+* a staged layout without a run table (an unsorted pattern with an item of more runs than
+  threads keeps the per-result positions sortedPos) passes, and one corrupted word of either store
+  table fails: a position moved to its neighbour's, a run's length + 1, a run's slot base shifted
+  (checked only: a corrupted plan is never launched);
 * a corrupted plan or layout (one array element overwritten through the library's test hook)
   fails with the reference's messages on stderr; the CLI's BSMR_VALIDATE path prints them.
 """
@@ -21,7 +25,7 @@ import pytest
 import oracle_lib as O
 import bsmr
 from bsmr import BF16, F16, F32, Plan, make_data, synth
-from gpu_util import half_values, run_sddmm
+from gpu_util import half_values, rb_store, run_sddmm
 
 pytestmark = pytest.mark.gpu
 
@@ -31,14 +35,18 @@ BIN = os.path.join(ROOT, "sddmm-gpu_amd", "bin", "BSMR-sddmm")
 BIN_FI = os.path.join(ROOT, "sddmm-gpu_amd", "bin", "BSMR-sddmm-faultinject")
 
 
-def _poke(plan, which, index, value, K=0, dtype=F32):
+def _poke_status(plan, which, index, value, K=0, dtype=F32):
     L = bsmr.lib()
     L.bsmr_debug_plan_poke.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_uint32, C.c_uint32,
                                        C.c_int, C.POINTER(C.c_uint32)]
     old = C.c_uint32()
-    st = L.bsmr_debug_plan_poke(plan.h, which, index, value, K, dtype, C.byref(old))
-    assert st == 0, L.bsmr_last_error()
-    return old.value
+    return L.bsmr_debug_plan_poke(plan.h, which, index, value, K, dtype, C.byref(old)), old.value
+
+
+def _poke(plan, which, index, value, K=0, dtype=F32):
+    st, old = _poke_status(plan, which, index, value, K, dtype)
+    assert st == 0, bsmr.lib().bsmr_last_error()
+    return old
 
 
 def _rb_items(plan, K, dtype):
@@ -215,6 +223,66 @@ def test_corrupted_plan_fails_with_reference_text(kind, capfd):
     assert not ok and line in msg and line in err, (msg, err)
     if summary:
         assert summary in err
+
+
+def _store_table_plan(table):
+    """(plan, K, rb_store dump) of a staged layout that stores by `table`: "positions" = an unsorted
+    pattern whose large items have more runs than threads (store_cases' pos_band_rb64), "runs" =
+    its sorted twin."""
+    from sddmm_cases import pattern
+    from store_cases import BAND
+    pat = pattern("band_shuffled" if table == "positions" else "band")
+    M, N, rp, ci = pat
+    plan = Plan(M, N, rp, ci, alpha=0.3, delta=0.3, free_mem_bytes=FREE, tuning=dict(BAND, rb_rows=64))
+    dump = rb_store(plan, 128, F32)
+    assert dump["outLds"] and dump["outRuns"] == (table == "runs"), dump
+    return plan, pat, dump
+
+
+def test_staged_layout_without_a_run_table_passes(capfd):
+    plan, (M, N, rp, ci), dump = _store_table_plan("positions")
+    assert dump["sortedPos"] is not None and dump["runs"] is None
+    assert _values_ok(plan, M, N, rp, ci, 128, F32) == 0
+    ok, msg = plan.check(128, F32)
+    err = capfd.readouterr().err
+    assert ok, (msg, err)
+    assert "Error!" not in err
+
+
+@pytest.mark.parametrize("kind", ["position_moved", "run_length_plus_one", "run_slot_shifted"])
+def test_corrupted_store_table_fails(kind, capfd):
+    """One word of sortedPos (poke 104) or of the run table (105: word 2 r = run r's position, 2 r +
+    1 = its slot | length << 16) overwritten: the check, which rebuilds slot -> position from the
+    table the kernel would read, fails. The corrupted plan is not launched."""
+    K = 128
+    plan, _, dump = _store_table_plan("positions" if kind == "position_moved" else "runs")
+    ok, msg = plan.check(K, F32)
+    assert ok, msg
+    capfd.readouterr()
+    if kind == "position_moved":
+        i = int(np.nonzero(dump["real"] & (dump["ent"] >= 2))[0][0])
+        e0 = int(dump["itemEnt"][i, 0])
+        assert _poke(plan, 104, e0, int(dump["sortedPos"][e0 + 1]), K, F32) == int(dump["sortedPos"][e0])
+    else:
+        i = int(np.nonzero(dump["real"] & (dump["nruns"] >= 3))[0][0])
+        r = int(dump["itemRuns"][i, 0]) + 1  # a middle run of the item: a following run's slots exist
+        word = int(dump["runs"][r, 1])
+        new = word + (1 << 16) if kind == "run_length_plus_one" else word + 1
+        assert _poke(plan, 105, 2 * r + 1, new, K, F32) == word
+    ok, msg = plan.check(K, F32)
+    err = capfd.readouterr().err
+    line = "Error! The launch layout is incorrect!"
+    assert not ok and line in msg and line in err, (msg, err)
+
+
+def test_store_table_pokes_name_the_table_that_exists():
+    """104 addresses sortedPos, which a run-table layout has released, and 105 the run words, which
+    a layout without the table never had: out of range, nothing written."""
+    for table, which in (("runs", 104), ("positions", 105)):
+        plan, _, _ = _store_table_plan(table)
+        assert _poke_status(plan, which, 0, 0, 128, F32)[0] != 0
+        ok, msg = plan.check(128, F32, verbose=False)
+        assert ok, msg
 
 
 def test_cli_validate_runs_plan_check(tmp_path):

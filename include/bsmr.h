@@ -46,7 +46,11 @@ extern "C" {
                               softmax over the plan's pattern: the step between bsmr_sddmm and
                               bsmr_spmm); bsmr_attention, bsmr_plan_prepare_attention,
                               bsmr_plan_attention_prepared, bsmr_plan_attention_stats,
-                              bsmr_attention_limits (fused sparse attention forward) */
+                              bsmr_attention_limits (fused sparse attention forward);
+                              bsmr_attention_backward, bsmr_plan_prepare_attention_backward,
+                              bsmr_plan_attention_backward_prepared,
+                              bsmr_plan_attention_backward_stats, bsmr_attention_backward_limits
+                              (fused sparse attention backward) */
 
 typedef enum {
     BSMR_OK = 0,
@@ -604,6 +608,61 @@ int bsmr_plan_attention_stats(const bsmr_plan* plan, bsmr_attention_stats* out);
 /* The constants of the attention path without a plan (either pointer may be NULL): entries per
  * segment and the largest K / V row in bytes. */
 void bsmr_attention_limits(uint32_t* chunk, uint32_t* max_row_bytes);
+
+/* ------------------------------------------------ fused sparse attention backward ---- */
+/* The gradients of bsmr_attention without an nnz-sized tensor (the chain's backward holds four: P,
+ * W, dW and dP). A function of its six inputs: Q, K, V as in bsmr_attention (one dtype, the same
+ * D / Dv rules and byte cap), O (M x Dv) and LSE (M) as a forward produced them, GO = dL/dO
+ * (M x Dv), all three fp32. Per stored entry e = (i, j):
+ *   p_e  = dot(Q[i,:], K[j,:])                        the forward's order, fp32
+ *   w_e  = LSE[i] == -inf ? 0 : 2^((p_e scale - LSE[i]) log2e)    every step rounded on its own
+ *   g_e  = dot(GO[i,:], V[j,:]),   delta_i = dot(GO[i,:], O[i,:])  (once per row, plan-owned scratch)
+ *   dp_e = (w_e (g_e - delta_i)) scale
+ *   GQ[i,:] = sum_e dp_e K[j_e,:]   GK[j,:] = sum_{e in column j} dp_e Q[i_e,:]   GV[j,:] = sum w_e GO[i_e,:]
+ * dGQ (M x D), dGK (N x D) and dGV (N x Dv) are fp32 and row-major; every element of a requested
+ * output is written (rows and columns without entries get 0). Any of the three may be NULL: without
+ * dGQ the row side is skipped, without dGK and dGV the column side; all three NULL is
+ * BSMR_ERR_INVALID. Every pointer but dLse is 16-byte aligned. Scale, dtype, dimension and pointer
+ * rules and their status codes are bsmr_attention's, and on every error the outputs are untouched.
+ * No output may alias an input or another output.
+ * Conventions:
+ *   a row with LSE = -inf (empty or fully masked) has w = 0: its GQ row is 0 and it adds nothing;
+ *   a NaN / inf in row i of Q, GO, O or LSE reaches at most GQ[i] and the GK / GV rows of the
+ *   columns row i references; one in K[j] or V[j] at most GK[j], GV[j] and the GQ rows that
+ *   reference j; no other destination changes by a bit.
+ * At most five launches: delta; one wave per segment of a row (the forward's lists, `row_chunk`
+ * entries at most) and the sum of split rows; one wave per segment of a column (`col_chunk`) and
+ * the sum of split columns. A lane group accumulates in entry order, the groups are added in group
+ * order and the partials in segment order, without atomics: the order is a function of the
+ * destination's list length, D, Dv and dtype alone, so results are bitwise
+ * reproducible and equal between a lazily built and a prepared plan. Launches of one plan share
+ * delta and the scratch: order them on one stream (or with events). The forward's scratch is
+ * another: forward and backward launches may interleave.
+ * Asynchronous on `stream` once the plan's backward state exists and covers (D, Dv): the first
+ * launch builds it unless bsmr_plan_prepare_attention_backward did, and on a capturing stream an
+ * unprepared plan gives BSMR_ERR_NOT_PREPARED and leaves the capture intact. */
+int bsmr_attention_backward(const bsmr_plan* plan, const void* dQ, const void* dK, const void* dV,
+                            const float* dO, const float* dGO, const float* dLse, uint32_t D,
+                            uint32_t Dv, int dtype, float scale, float* dGQ, float* dGK, float* dGV,
+                            void* stream);
+/* Build now what the first bsmr_attention_backward at (D, Dv) would build inside the call: the
+ * column lists (and the row lists, unless the forward's exist and are shared), delta, and the
+ * scratch of split rows (row_partials x D floats) and split columns (col_partials x (D + Dv)).
+ * Synchronous and idempotent; a larger D or Dv grows the scratch. bsmr_plan_prepare_spmm (whatever
+ * its chunk) and bsmr_plan_recolumn keep this state, and it never changes the forward's. */
+int bsmr_plan_prepare_attention_backward(const bsmr_plan* plan, uint32_t D, uint32_t Dv);
+/* 1 when a launch at (D, Dv) would make no allocation, copy or synchronisation, else 0 (also 0 on
+ * bad arguments, with bsmr_last_error set). No device call. */
+int bsmr_plan_attention_backward_prepared(const bsmr_plan* plan, uint32_t D, uint32_t Dv);
+typedef struct {
+    uint32_t row_segments, row_split, row_partials, row_max, row_chunk; /* as bsmr_attention_stats */
+    uint32_t col_segments, col_split, col_partials, col_max, col_chunk; /* the same per column */
+    uint64_t row_scratch_bytes, col_scratch_bytes, delta_bytes;          /* plan-owned device memory */
+} bsmr_attention_backward_stats;
+/* Counts and sizes are zeros while the state is not built; the chunks are always filled. */
+int bsmr_plan_attention_backward_stats(const bsmr_plan* plan, bsmr_attention_backward_stats* out);
+/* The constants of the backward without a plan (any pointer may be NULL). */
+void bsmr_attention_backward_limits(uint32_t* row_chunk, uint32_t* col_chunk, uint32_t* max_row_bytes);
 
 /* Timing: run `iters` back-to-back SDDMMs on `stream`, timing each kernel with HIP events on
  * that stream (BSMR_ERR_UNSUPPORTED on a capturing stream). Outputs average ms per launch of the dense-tile kernel, the residual kernel and

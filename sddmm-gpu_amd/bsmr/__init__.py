@@ -8,7 +8,7 @@ Reference interface mirrored (paths relative to the reference root):
   * evaluationReordering                               -> Plan.evaluate   (src/BSMR.cpp:826-994)
 Beyond the reference: the gradients of the SDDMM as SpMM over the same plan (Plan.spmm,
 Plan.spmm_t, Plan.sddmm_backward), the row softmax over the plan's pattern (Plan.softmax,
-Plan.softmax_backward), the fused sparse attention forward (Plan.attention), and bsmr.autograd,
+Plan.softmax_backward), the fused sparse attention forward and backward (Plan.attention, Plan.attention_backward), and bsmr.autograd,
 which wraps SDDMM, softmax and SpMM for torch.autograd and composes them into sparse attention.
 
 Every call goes through the HIP library; there is no CPU fallback. If the shared library is
@@ -167,6 +167,17 @@ class AttentionStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class AttentionBackwardStats(C.Structure):
+    """bsmr_attention_backward_stats: the fused attention backward's row and column segment lists
+    and plan-owned scratch (zeros when not built) and the library's constant chunks."""
+    _fields_ = [(f"{side}_{k}", C.c_uint32) for side in ("row", "col")
+                for k in ("segments", "split", "partials", "max", "chunk")] + \
+               [("row_scratch_bytes", C.c_uint64), ("col_scratch_bytes", C.c_uint64), ("delta_bytes", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 # bsmr_softmax_item.kind beside a packed run's lane-group width 1 .. 64
 SOFTMAX_WAVE = 0x100
 SOFTMAX_BLOCK = 0x200
@@ -196,6 +207,9 @@ EXPORTS = [
     "bsmr_softmax_limits",
     "bsmr_attention", "bsmr_plan_prepare_attention", "bsmr_plan_attention_prepared",
     "bsmr_plan_attention_stats", "bsmr_attention_limits",
+    "bsmr_attention_backward", "bsmr_plan_prepare_attention_backward",
+    "bsmr_plan_attention_backward_prepared", "bsmr_plan_attention_backward_stats",
+    "bsmr_attention_backward_limits",
 ]
 
 _lib = None
@@ -311,6 +325,15 @@ def lib():
     L.bsmr_plan_attention_stats.restype = C.c_int
     L.bsmr_attention_limits.argtypes = [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     L.bsmr_attention_limits.restype = None
+    L.bsmr_attention_backward.argtypes = [vp] * 7 + [C.c_uint32, C.c_uint32, C.c_int, C.c_float] + [vp] * 4
+    L.bsmr_attention_backward.restype = C.c_int
+    for f in ("bsmr_plan_prepare_attention_backward", "bsmr_plan_attention_backward_prepared"):
+        getattr(L, f).argtypes = [vp, C.c_uint32, C.c_uint32]
+        getattr(L, f).restype = C.c_int
+    L.bsmr_plan_attention_backward_stats.argtypes = [vp, C.POINTER(AttentionBackwardStats)]
+    L.bsmr_plan_attention_backward_stats.restype = C.c_int
+    L.bsmr_attention_backward_limits.argtypes = [C.POINTER(C.c_uint32)] * 3
+    L.bsmr_attention_backward_limits.restype = None
     L.bsmr_plan_check.argtypes = [vp, C.c_uint32, C.c_int, C.c_int]
     L.bsmr_plan_check.restype = C.c_int
     L.bsmr_check_rphm_arrays.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32] + [_u32p] * 2 + \
@@ -641,6 +664,28 @@ class Plan:
         _check(lib().bsmr_plan_attention_stats(self.h, C.byref(s)), "bsmr_plan_attention_stats")
         return s.as_dict()
 
+    def attention_backward(self, dQ, dK, dV, dO, dGO, dLse, D, Dv, dGQ=0, dGK=0, dGV=0, scale=1.0, stream=0,
+                           dtype=F32):
+        """bsmr_attention_backward: GQ (M x D), GK (N x D), GV (N x Dv) fp32, the gradients of
+        Plan.attention from Q, K, V, the forward's O and LSE and GO = dL/dO (fp32), without an
+        nnz-sized tensor. Any output may be 0 (skipped); not all three."""
+        _check(lib().bsmr_attention_backward(self.h, dQ, dK, dV, dO, dGO, dLse, D, Dv, dtype, scale,
+                                             dGQ or None, dGK or None, dGV or None, stream or None),
+               "bsmr_attention_backward")
+
+    def prepare_attention_backward(self, D, Dv):
+        """bsmr_plan_prepare_attention_backward: build the backward's lists, delta and scratch for
+        (D, Dv) now, so that the first attention_backward launch can be captured."""
+        _check(lib().bsmr_plan_prepare_attention_backward(self.h, D, Dv), "bsmr_plan_prepare_attention_backward")
+
+    def attention_backward_prepared(self, D, Dv):
+        return bool(lib().bsmr_plan_attention_backward_prepared(self.h, D, Dv))
+
+    def attention_backward_stats(self):
+        s = AttentionBackwardStats()
+        _check(lib().bsmr_plan_attention_backward_stats(self.h, C.byref(s)), "bsmr_plan_attention_backward_stats")
+        return s.as_dict()
+
     def sddmm_backward(self, dG, dA, dB, K, dGA, dGB, stream=0, dtype=F32):
         """The gradients of P = sddmm(A, B) from dG = dL/dP (fp32, nnz): dGA (M x K fp32) =
         S(G) B and dGB (N x K fp32) = S(G)^T A. Either output may be 0: that side is skipped."""
@@ -758,6 +803,14 @@ def attention_limits():
     c, b = C.c_uint32(), C.c_uint32()
     lib().bsmr_attention_limits(C.byref(c), C.byref(b))
     return dict(chunk=c.value, max_row_bytes=b.value)
+
+
+def attention_backward_limits():
+    """bsmr_attention_backward_limits (host only): dict(row_chunk, col_chunk, max_row_bytes), the
+    constants of Plan.attention_backward without a plan."""
+    r, c, b = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    lib().bsmr_attention_backward_limits(C.byref(r), C.byref(c), C.byref(b))
+    return dict(row_chunk=r.value, col_chunk=c.value, max_row_bytes=b.value)
 
 
 def sddmm_cpu(M, N, rowptr, colidx, K, A, B, threads=0):

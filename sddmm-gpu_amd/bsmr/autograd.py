@@ -10,7 +10,9 @@ and, over the same plan, the row softmax, the SpMM and their composition into sp
                                                                    dX = Plan.spmm_t(V, dY)
     attention(plan, Q, K, V)     spmm(softmax(sddmm(Q, K), scale), V)
     attention_fused(plan, Q, K, V)   the same O from one fused forward launch (Plan.attention) that
-                                     keeps no nnz-sized tensor; the backward recomputes P and W
+                                     keeps no nnz-sized tensor; the backward recomputes P and W, or
+                                     (backward="fused") is one Plan.attention_backward call that
+                                     holds no nnz-sized tensor either
 
 Every direction is the library's HIP kernels on torch.cuda.current_stream(); torch only owns the
 tensors. Importing this module imports torch (`import bsmr` alone does not).
@@ -301,7 +303,44 @@ class _AttentionFused(torch.autograd.Function):
         return gQ, gK, gV, None, None, None
 
 
-def attention_fused(plan, Q, K, V, scale=None, return_lse=False):
+class _AttentionFusedBwd(torch.autograd.Function):
+    """attention_fused with backward="fused": the forward always takes LSE and saves Q, K, V, O and
+    LSE; the backward is one Plan.attention_backward call."""
+
+    @staticmethod
+    def forward(ctx, Q, K, V, plan, scale, want_lse):
+        D, Dv, dtype = _validate_fused(plan, Q, K, V)
+        O = torch.empty((plan.M, Dv), dtype=torch.float32, device=Q.device)
+        lse = torch.empty(max(plan.M, 1), dtype=torch.float32, device=Q.device)
+        plan.attention(Q.data_ptr(), K.data_ptr(), V.data_ptr(), D, Dv, O.data_ptr(), lse.data_ptr(), scale,
+                       stream=_stream(), dtype=dtype)
+        lse = lse[:plan.M]
+        ctx.plan, ctx.scale, ctx.dims = plan, scale, (D, Dv, dtype)
+        ctx.save_for_backward(Q, K, V, O, lse)
+        if not want_lse:
+            return O
+        ctx.mark_non_differentiable(lse)
+        return O, lse
+
+    @staticmethod
+    def backward(ctx, grad, *_):
+        Q, K, V, O, lse = ctx.saved_tensors
+        plan = ctx.plan
+        D, Dv, dtype = ctx.dims
+        if not any(ctx.needs_input_grad[:3]):
+            return None, None, None, None, None, None
+        dO = grad.contiguous().float()
+        out = [torch.empty(shape, dtype=torch.float32, device=Q.device) if need else None
+               for need, shape in zip(ctx.needs_input_grad[:3], ((plan.M, D), (plan.N, D), (plan.N, Dv)))]
+        ptr = [0 if t is None else t.data_ptr() for t in out]
+        plan.attention_backward(Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), dO.data_ptr(),
+                                _launchable(lse).data_ptr(), D, Dv, ptr[0], ptr[1], ptr[2], ctx.scale,
+                                stream=_stream(), dtype=dtype)
+        gQ, gK, gV = (None if t is None else t.to(X.dtype) for t, X in zip(out, (Q, K, V)))
+        return gQ, gK, gV, None, None, None
+
+
+def attention_fused(plan, Q, K, V, scale=None, return_lse=False, backward="recompute"):
     """O (M, Dv) float32 of attention(plan, Q, K, V, scale) from one fused forward launch
     (Plan.attention: no nnz-sized scores or weights are written), and with return_lse=True also
     LSE (M,) float32 = max * scale + ln(sum) per row (-inf for an empty row), returned
@@ -314,11 +353,20 @@ def attention_fused(plan, Q, K, V, scale=None, return_lse=False):
     read O, so dQ, dK and dV are bitwise equal to those of attention. The price is one more SDDMM
     and softmax in the backward; the gain is that no W (nnz values) is held between forward and
     backward. O itself is summed in another order than attention's and agrees with it within the
-    two paths' error bounds, not bit for bit."""
+    two paths' error bounds, not bit for bit.
+
+    backward="fused": the forward always asks for LSE and saves Q, K, V, O and LSE; the backward is
+    one Plan.attention_backward call (at most five launches) that computes dQ, dK and dV per entry
+    in registers and allocates no nnz-sized tensor, skipping the side no input needs. Its gradients
+    agree with the default path's within the two paths' error bounds, not bit for bit. Any other
+    value of `backward` raises ValueError before any launch."""
+    if backward not in ("recompute", "fused"):
+        raise ValueError(f"attention_fused: backward = {backward!r} must be \"recompute\" or \"fused\"")
     if scale is None:
         if not isinstance(Q, torch.Tensor) or Q.dim() != 2 or Q.shape[1] == 0:
             raise ValueError("attention_fused: Q must be an (M, D) tensor with D > 0")
         scale = Q.shape[1] ** -0.5
     scale = _valid_scale("attention_fused", scale)
     _validate_fused(plan, Q, K, V)
-    return _AttentionFused.apply(Q, K, V, plan, scale, bool(return_lse))
+    fn = _AttentionFusedBwd if backward == "fused" else _AttentionFused
+    return fn.apply(Q, K, V, plan, scale, bool(return_lse))

@@ -26,6 +26,7 @@
 #include <string>
 #include <vector>
 
+#include "attention_common.hpp"
 #include "plan.hpp"
 #include "row_elems.hpp"
 #include "spmm_schedule.hpp"
@@ -40,7 +41,6 @@ namespace {
 #define ATTN_CHUNK 256
 #endif
 constexpr u32 ATTN_WAVES = 16;     // waves (segments) per workgroup, as k_spmm
-constexpr u32 ATTN_MAX_ROW_BYTES = 1024;
 static_assert(ATTN_CHUNK % 64 == 0 && ATTN_CHUNK >= 64 && ATTN_CHUNK <= 1024, "batches of 64; scores in LDS");
 
 struct AttnArgs {
@@ -275,9 +275,12 @@ AttnFn pick_attention(u32 rowBytes) {
     }
 }
 
+}  // namespace
+
+// (attention_common.hpp: shared with attention_bwd.hip)
 // the rules of the chain it replaces: D a positive multiple of 16 (fp32) or 32 (fp16 / bf16: what
 // bsmr_sddmm takes), Dv a positive multiple of 16 (bsmr_spmm's K); and rows of at most 1024 bytes
-int validate_dims(const char* who, u32 D, u32 Dv, int dtype) {
+int attn_validate_dims(const char* who, u32 D, u32 Dv, int dtype) {
     if (dtype != BSMR_F32 && dtype != BSMR_F16 && dtype != BSMR_BF16) {
         set_error(std::string(who) + ": dtype must be BSMR_F32, BSMR_F16 or BSMR_BF16");
         return BSMR_ERR_UNSUPPORTED;
@@ -292,10 +295,54 @@ int validate_dims(const char* who, u32 D, u32 Dv, int dtype) {
 }
 
 // the prepare calls carry no dtype: what some dtype accepts
-int validate_prepare_dims(const char* who, u32 D, u32 Dv) {
-    if (validate_dims(who, D, Dv, BSMR_F32) == BSMR_OK) return BSMR_OK;
-    return validate_dims(who, D, Dv, BSMR_F16);
+int attn_validate_prepare_dims(const char* who, u32 D, u32 Dv) {
+    if (attn_validate_dims(who, D, Dv, BSMR_F32) == BSMR_OK) return BSMR_OK;
+    return attn_validate_dims(who, D, Dv, BSMR_F16);
 }
+
+// bsmr_softmax's rule: the exponent factor is rounded once from double
+int attn_validate_scale(const char* who, float scale, float* c) {
+    *c = static_cast<float>(static_cast<double>(scale) * 1.4426950408889634);
+    if (!(scale > 0.f) || !std::isfinite(scale) || !std::isfinite(*c)) {
+        set_error(std::string(who) + ": scale must be finite and > 0 (and scale * log2(e) finite)");
+        return BSMR_ERR_INVALID;
+    }
+    return BSMR_OK;
+}
+
+u32 attn_forward_chunk() { return ATTN_CHUNK; }
+
+int attn_row_lists(const Plan& p, u32 chunk, const char* who, SpmmLists& L) {
+    const hipStream_t s = p.stream;
+    std::vector<u32> hrp, hci, hrows;
+    BSMR_CHECK(p.rowptr.download(hrp, s));
+    BSMR_CHECK(p.colidx.download(hci, s));
+    // rows in the plan's reordered order: a workgroup's waves share a panel's columns
+    BSMR_CHECK(p.rows.download(hrows, s));
+    hrows.resize(std::min<size_t>(hrows.size(), p.R));
+    SpmmIn in;
+    in.M = p.M;
+    in.N = p.N;
+    in.nnz = p.nnz;
+    in.rowptr = hrp.data();
+    in.colidx = hci.data();
+    in.side = 1;
+    in.chunk = chunk;
+    in.order = hrows.data();
+    in.norder = static_cast<u32>(hrows.size());
+    std::string err;
+    if (spmm_lists(in, L, err)) {
+        set_error(std::string(who) + ": " + err);
+        return BSMR_ERR_INVALID;
+    }
+    if (L.nSegs > (1ull << 31)) {
+        set_error(std::string(who) + ": more than 2^31 segments");
+        return BSMR_ERR_UNSUPPORTED;
+    }
+    return BSMR_OK;
+}
+
+namespace {
 
 bool attention_ready(const Plan::AttentionState& S, u32 Dv) {
     return S.built && (S.partials == 0 || S.scratchDv >= Dv);
@@ -307,32 +354,8 @@ int build_attention(const Plan& p, u32 Dv) {
     Plan::AttentionState& S = p.attention;
     const hipStream_t s = p.stream;
     if (!S.built) {
-        std::vector<u32> hrp, hci, hrows;
-        BSMR_CHECK(p.rowptr.download(hrp, s));
-        BSMR_CHECK(p.colidx.download(hci, s));
-        // rows in the plan's reordered order: a workgroup's waves share a panel's columns
-        BSMR_CHECK(p.rows.download(hrows, s));
-        hrows.resize(std::min<size_t>(hrows.size(), p.R));
-        SpmmIn in;
-        in.M = p.M;
-        in.N = p.N;
-        in.nnz = p.nnz;
-        in.rowptr = hrp.data();
-        in.colidx = hci.data();
-        in.side = 1;
-        in.chunk = ATTN_CHUNK;
-        in.order = hrows.data();
-        in.norder = static_cast<u32>(hrows.size());
         SpmmLists L;
-        std::string err;
-        if (spmm_lists(in, L, err)) {
-            set_error(std::string("bsmr_plan_prepare_attention: ") + err);
-            return BSMR_ERR_INVALID;
-        }
-        if (L.nSegs > (1ull << 31)) {
-            set_error("bsmr_plan_prepare_attention: more than 2^31 segments");
-            return BSMR_ERR_UNSUPPORTED;
-        }
+        BSMR_CHECK(attn_row_lists(p, ATTN_CHUNK, "bsmr_plan_prepare_attention", L));
         // (on side 1 L.src is colidx and L.vpos the identity: the plan's own colidx serves)
         BSMR_CHECK(S.segs.upload(L.segs.data(), L.segs.size(), s));
         BSMR_CHECK(S.reds.upload(L.reds.data(), L.reds.size(), s));
@@ -353,8 +376,6 @@ int build_attention(const Plan& p, u32 Dv) {
     return BSMR_OK;
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 }  // namespace
 }  // namespace bsmr
 
@@ -371,18 +392,14 @@ extern "C" int bsmr_attention(const bsmr_plan* plan, const void* dQ, const void*
         set_error("bsmr_attention: null device pointer");
         return BSMR_ERR_INVALID;
     }
-    if (!aligned16(dQ) || !aligned16(dK) || !aligned16(dV) || !aligned16(dO) ||
+    if (!attn_aligned16(dQ) || !attn_aligned16(dK) || !attn_aligned16(dV) || !attn_aligned16(dO) ||
         (reinterpret_cast<uintptr_t>(dLse) & 3u)) {
         set_error("bsmr_attention: dQ, dK, dV and dO must be 16-byte aligned");
         return BSMR_ERR_INVALID;
     }
-    // bsmr_softmax's rule: the exponent factor is rounded once from double
-    const float c = static_cast<float>(static_cast<double>(scale) * 1.4426950408889634);
-    if (!(scale > 0.f) || !std::isfinite(scale) || !std::isfinite(c)) {
-        set_error("bsmr_attention: scale must be finite and > 0 (and scale * log2(e) finite)");
-        return BSMR_ERR_INVALID;
-    }
-    BSMR_CHECK(validate_dims(who, D, Dv, dtype));
+    float c;
+    BSMR_CHECK(attn_validate_scale(who, scale, &c));
+    BSMR_CHECK(attn_validate_dims(who, D, Dv, dtype));
     const Plan& p = plan->p;
     const hipStream_t s = static_cast<hipStream_t>(stream);
     const Plan::AttentionState& S = p.attention;
@@ -445,7 +462,7 @@ extern "C" int bsmr_plan_prepare_attention(const bsmr_plan* plan, uint32_t D, ui
         set_error("bsmr_plan_prepare_attention: null plan");
         return BSMR_ERR_INVALID;
     }
-    BSMR_CHECK(validate_prepare_dims("bsmr_plan_prepare_attention", D, Dv));
+    BSMR_CHECK(attn_validate_prepare_dims("bsmr_plan_prepare_attention", D, Dv));
     std::lock_guard<std::mutex> g(plan->p.layout_mu);
     return build_attention(plan->p, Dv);
 }
@@ -455,7 +472,7 @@ extern "C" int bsmr_plan_attention_prepared(const bsmr_plan* plan, uint32_t D, u
         set_error("bsmr_plan_attention_prepared: null plan");
         return 0;
     }
-    if (validate_prepare_dims("bsmr_plan_attention_prepared", D, Dv) != BSMR_OK) return 0;
+    if (attn_validate_prepare_dims("bsmr_plan_attention_prepared", D, Dv) != BSMR_OK) return 0;
     std::lock_guard<std::mutex> g(plan->p.layout_mu);
     return attention_ready(plan->p.attention, Dv) ? 1 : 0;
 }

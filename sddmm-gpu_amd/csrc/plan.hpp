@@ -285,6 +285,27 @@ struct Plan {
     };
     mutable AttentionState attention;
 
+    // fused sparse attention backward (attention_bwd.hip; bsmr_attention_backward): the rows'
+    // segments (the forward's lists: AttentionState's buffers when they were built before this
+    // state and the two chunks agree, rowShared, else lists of its own built the same way), the
+    // columns' segments with the row of every entry (spmm_lists at side 2; no vpos: there are no
+    // nnz values), the M floats of delta = dot(GO, O), and the partial rows of the split
+    // destinations: rowPartials x D floats, and colPartials x D followed by colPartials x Dv. Built
+    // on first use or by bsmr_plan_prepare_attention_backward, under layout_mu; neither
+    // bsmr_plan_prepare_spmm nor build_columns touches it, and it never writes AttentionState
+    struct AttentionBwdState {
+        bool built = false, rowShared = false;
+        u32 rowSegs = 0, rowReds = 0, rowSplit = 0, rowPartials = 0, rowMax = 0;
+        u32 colSegs = 0, colReds = 0, colSplit = 0, colPartials = 0, colMax = 0;
+        DevBuf<SpmmSeg> rsegs, csegs;
+        DevBuf<SpmmRed> rreds, creds;
+        DevBuf<u32> csrc;
+        DevBuf<float> delta, rowScratch, colScratch;  // the scratches hold what the largest (D, Dv) so far needs
+        const SpmmSeg* row_segs(const AttentionState& f) const { return rowShared ? f.segs.data() : rsegs.data(); }
+        const SpmmRed* row_reds(const AttentionState& f) const { return rowShared ? f.reds.data() : rreds.data(); }
+    };
+    mutable AttentionBwdState attention_bwd;
+
     int build_rows(const u32* h_rowptr, const u32* h_col);
     int build_columns();
     ~Plan() {

@@ -24,7 +24,21 @@ Per case (the C2 nips-like and C3 cop20k-like stand-in patterns, fp32, D = Dv = 
     backward (W and G read, dP written, and 4 nnz allowed for the second read of rows longer than
     one pass), over 8 TB/s; fused_fwd: Q and O, one read of every K and V row that some entry
     references, colidx and LSE; floor_fraction = floor / graph;
-  * fused_over_composed: graph_us of fused_fwd / composed_fwd, and the largest |O_fused - O_composed|.
+  * fused_over_composed: graph_us of fused_fwd / composed_fwd, and the largest |O_fused - O_composed|;
+  * the backward alone, three ways on the same tensors (graph_us, stream_us, floor_us; launches: the
+    library calls of each and the kernels of the fused call):
+      composed_bwd: the five launches of attention's backward after a forward that kept P and W
+      (sddmm and spmm_t for dW and dV, softmax_backward, spmm and spmm_t for dQ and dK);
+      recompute_bwd: sddmm and softmax again, then those five (attention_fused's default backward);
+      fused_bwd: one Plan.attention_backward from O and LSE (delta, rows, columns and the reduces of
+      split destinations: at most five launches, no nnz-sized tensor);
+    floors: every dense operand and gradient once (Q, K, V, GO and dQ, dK, dV; the fused one also O)
+    and the nnz-sized traffic each path cannot avoid: 28 nnz bytes composed (dW written and read, W
+    read twice, dP written and read twice), 40 nnz recompute (P written and read, W written), 8 nnz
+    fused (the column index of every entry on the row side, its row on the column side);
+    backward_peak_bytes: torch's peak over forward + backward through bsmr.autograd (attention,
+    attention_fused, attention_fused(backward="fused")) above what was allocated before;
+    attention_backward_stats carries the plan-owned scratch of the fused backward.
 """
 import argparse
 import json
@@ -106,6 +120,7 @@ def main():
         plan.prepare_spmm(D, 3)
         plan.prepare_softmax()
         plan.prepare_attention(D, D)
+        plan.prepare_attention_backward(D, D)
 
         def data(n, shape=None):
             t = torch.from_numpy(make_data(n)).to(dev) - 1.0  # uniform [-1, 1)
@@ -138,12 +153,32 @@ def main():
         def fused_fwd(s):
             plan.attention(p(Q), p(K), p(V), D, D, p(fO), p(fL), scale, stream=s)
 
+        bgQ, bgK, bgV = z(M, D), z(N, D), z(N, D)
+
+        def composed_bwd(s):
+            plan.sddmm(p(dO), p(V), D, p(agW), stream=s)
+            plan.spmm_t(p(aW), p(dO), D, p(agV), stream=s)
+            plan.softmax_backward(p(aW), p(agW), p(agP), scale, stream=s)
+            plan.spmm(p(agP), p(K), D, p(agQ), stream=s)
+            plan.spmm_t(p(agP), p(Q), D, p(agK), stream=s)
+
+        def recompute_bwd(s):
+            plan.sddmm(p(Q), p(K), D, p(aP), stream=s)
+            plan.softmax(p(aP), p(aW), scale, stream=s)
+            composed_bwd(s)
+
+        def fused_bwd(s):
+            plan.attention_backward(p(Q), p(K), p(V), p(fO), p(dO), p(fL), D, D, p(bgQ), p(bgK), p(bgV), scale, stream=s)
+
         ours = {
             "softmax_fwd": lambda s: plan.softmax(p(P), p(W), scale, stream=s),
             "softmax_bwd": lambda s: plan.softmax_backward(p(W), p(G), p(gP), scale, stream=s),
             "attention": attention,
             "composed_fwd": composed_fwd,
             "fused_fwd": fused_fwd,
+            "composed_bwd": composed_bwd,
+            "recompute_bwd": recompute_bwd,
+            "fused_bwd": fused_bwd,
         }
         graphs = {k: graph_of(f) for k, f in ours.items()}
         graph_us = alternate({k: g.replay for k, g in graphs.items()})
@@ -176,13 +211,48 @@ def main():
             fused_fwd(gs.cuda_stream)
         gs.synchronize()
         check["fused_vs_composed_max_abs_diff"] = (fO - aO).abs().max().item()
+        with torch.cuda.stream(gs):
+            composed_bwd(gs.cuda_stream)
+            fused_bwd(gs.cuda_stream)
+        gs.synchronize()
+        for name, a, b in (("dQ", bgQ, agQ), ("dK", bgK, agK), ("dV", bgV, agV)):
+            check[f"fused_vs_composed_bwd_{name}_max_abs_diff"] = (a - b).abs().max().item()
+        bst = plan.attention_backward_stats()
+        dense = 4 * D * (M + 2 * used + M) + 4 * D * (M + 2 * N)  # Q, K, V, GO read; dQ, dK, dV written
+        floor["composed_bwd"] = (dense + 28 * nnz) / HBM_BYTES_PER_S * 1e6
+        floor["recompute_bwd"] = (dense + 40 * nnz) / HBM_BYTES_PER_S * 1e6
+        floor["fused_bwd"] = (dense + 4 * D * M + 8 * nnz + 12 * M) / HBM_BYTES_PER_S * 1e6
+        # library calls per backward, and the kernels of the one fused call (delta, rows, columns, two reduces)
+        launches = {"composed_bwd_calls": 5, "recompute_bwd_calls": 7, "fused_bwd_calls": 1,
+                    "fused_bwd_kernels": 3 + (bst["row_split"] > 0) + (bst["col_split"] > 0)}
+
+        from bsmr import autograd
+
+        def peak(fn):
+            ts = [t.clone().requires_grad_() for t in (Q, K, V)]
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats()
+            before = torch.cuda.memory_allocated()
+            fn(*ts).backward(dO)
+            torch.cuda.synchronize()
+            return torch.cuda.max_memory_allocated() - before
+
+        peaks = {}
+        for name, fn in (("attention", lambda q, k, v: autograd.attention(plan, q, k, v)),
+                         ("attention_fused_recompute", lambda q, k, v: autograd.attention_fused(plan, q, k, v)),
+                         ("attention_fused_fused", lambda q, k, v: autograd.attention_fused(plan, q, k, v, backward="fused"))):
+            peak(fn)  # warm the allocator
+            peaks[name] = peak(fn)
         line = {"case": case, "M": M, "N": N, "nnz": nnz, "D": D, "scale": scale, "steps": args.steps,
                 "rounds": args.rounds, "graph_us": graph_us, "stream_us": stream_us, "torch_us": torch_us,
                 "floor_us": {k: round(v, 3) for k, v in floor.items()},
                 "floor_fraction": {k: round(floor[k] / graph_us[k], 3) for k in floor},
                 "torch_over_ours_stream": {k: round(torch_us[k] / stream_us[k], 2) for k in torch_us},
                 "fused_over_composed": round(graph_us["fused_fwd"] / graph_us["composed_fwd"], 3),
-                "softmax_stats": plan.softmax_stats(), "attention_stats": plan.attention_stats(), "check": check, "torch": torch.__version__}
+                "softmax_stats": plan.softmax_stats(), "attention_stats": plan.attention_stats(),
+                "launches": launches, "backward_peak_bytes": peaks, "nnz_bytes": 4 * nnz, "attention_backward_stats": bst,
+                "fused_bwd_over_composed_bwd": round(graph_us["fused_bwd"] / graph_us["composed_bwd"], 3),
+                "fused_bwd_over_recompute_bwd": round(graph_us["fused_bwd"] / graph_us["recompute_bwd"], 3), "check": check, "torch": torch.__version__}
         print(json.dumps(line), flush=True)
 
 

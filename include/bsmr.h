@@ -50,7 +50,10 @@ extern "C" {
                               bsmr_attention_backward, bsmr_plan_prepare_attention_backward,
                               bsmr_plan_attention_backward_prepared,
                               bsmr_plan_attention_backward_stats, bsmr_attention_backward_limits
-                              (fused sparse attention backward) */
+                              (fused sparse attention backward); bsmr_attention_heads,
+                              bsmr_attention_backward_heads, their four prepare / prepared calls
+                              and bsmr_attention_layout_check (batch and heads, strided operands:
+                              new declarations only) */
 
 typedef enum {
     BSMR_OK = 0,
@@ -663,6 +666,80 @@ typedef struct {
 int bsmr_plan_attention_backward_stats(const bsmr_plan* plan, bsmr_attention_backward_stats* out);
 /* The constants of the backward without a plan (any pointer may be NULL). */
 void bsmr_attention_backward_limits(uint32_t* row_chunk, uint32_t* col_chunk, uint32_t* max_row_bytes);
+
+/* ------------------------------- fused sparse attention over batch and heads ---- */
+/* bsmr_attention and bsmr_attention_backward over Z = batches x heads slices of one pattern in one
+ * call, on strided operands: Q, K and V may be views of a (B, M, H D) projection, with no copy.
+ * One strided operand: element [b][h][r][c] lies at ptr + (b batch + h head + r row + c) elements. */
+typedef struct {
+    void*    ptr;              /* device pointer, 16-byte aligned */
+    uint64_t batch, head, row; /* strides in ELEMENTS of the operand's dtype; the last dimension is contiguous */
+} bsmr_attention_operand;
+
+#define BSMR_ATTENTION_MAX_BATCHES 65535u
+#define BSMR_ATTENTION_MAX_HEADS   65535u
+
+/* Per-slice semantics: slice (b, h) is exactly bsmr_attention / bsmr_attention_backward on that
+ * slice's rows: the same formulas, the same conventions for empty rows, -inf, NaN and inf, every
+ * element of a requested output written, and the same summation order, still a function of the
+ * destination's list length, D, Dv and dtype alone. The outputs of slice (b, h) are therefore bit
+ * for bit those of the single-slice call on a contiguous copy of that slice, and a call with
+ * batches = heads = 1 and dense strides is bit for bit the existing call (the single-slice entry
+ * points run the same launch code).
+ * Operands: Q, K and V share `dtype`; O, GO, GQ, GK and GV are fp32; dLse is dense
+ * (batches, heads, M) fp32 (it may be NULL in the forward). W below is an operand's row width in
+ * elements: D for Q, K, GQ and GK; Dv for V, O, GO and GV. The D / Dv / byte-cap / scale rules and
+ * their status codes are bsmr_attention's.
+ * Layout rules (csrc/attention_layout.cpp, host only; bsmr_attention_layout_check applies them to
+ * one operand without a device call); a violation gives BSMR_ERR_INVALID:
+ *   the operand and its ptr are non-null and ptr is 16-byte aligned;
+ *   batches is 1 .. BSMR_ATTENTION_MAX_BATCHES and heads 1 .. BSMR_ATTENTION_MAX_HEADS;
+ *   a dimension of extent 1 is never stepped over and its stride is ignored; every other stride,
+ *   multiplied by the element size, is a multiple of 16 bytes;
+ *   with more than one row, row >= W, and row times the element size is below 2^32;
+ *   every byte offset is computed in 64 bits with overflow-checked arithmetic, and a layout whose
+ *   last byte offset does not fit in 64 bits is refused;
+ *   inputs may have a batch or head stride of 0 (one K / V shared by all heads);
+ *   outputs must be provably non-overlapping: of the dimensions among (batch, head, row) whose
+ *   extent is greater than 1, sorted by stride ascending, the first stride is >= W and each
+ *   further stride >= the previous stride times the previous extent. Dense (B, H, M, W), dense
+ *   (B, M, H, W) and padded variants pass; a stride of 0 does not.
+ * On every error the outputs are untouched. The padding between the rows of an output whose
+ * row > W is never written. No output may alias an input or another output.
+ * Launches: at most two per forward call and five per backward call, whatever Z is: the grid's x
+ * is the segment, y the head and z the batch. No atomics, no nnz-sized or Z nnz-sized tensor.
+ * Plan-owned scratch is per slice: forward Z partials (Dv + 2) floats; backward Z M floats of
+ * delta, Z row_partials D and Z col_partials (D + Dv) floats. It grows, and never shrinks, when a
+ * call needs more for (D, Dv, Z); the stats structs report the bytes allocated, and nothing changes
+ * for a plan that only ever sees single-slice calls. Launches of one plan share the scratch and are
+ * ordered by the caller. On a capturing stream a plan not prepared for Z slices gives
+ * BSMR_ERR_NOT_PREPARED and leaves the capture intact. */
+int bsmr_attention_heads(const bsmr_plan* plan, uint32_t batches, uint32_t heads,
+                         const bsmr_attention_operand* Q, const bsmr_attention_operand* K,
+                         const bsmr_attention_operand* V, uint32_t D, uint32_t Dv, int dtype, float scale,
+                         const bsmr_attention_operand* O, float* dLse, void* stream);
+/* GQ, GK, GV: any may be NULL, not all. */
+int bsmr_attention_backward_heads(const bsmr_plan* plan, uint32_t batches, uint32_t heads,
+                                  const bsmr_attention_operand* Q, const bsmr_attention_operand* K,
+                                  const bsmr_attention_operand* V, const bsmr_attention_operand* O,
+                                  const bsmr_attention_operand* GO, const float* dLse, uint32_t D,
+                                  uint32_t Dv, int dtype, float scale, const bsmr_attention_operand* GQ,
+                                  const bsmr_attention_operand* GK, const bsmr_attention_operand* GV,
+                                  void* stream);
+/* Build now what the first heads launch of `slices` = batches x heads slices at (D, Dv) would build
+ * inside the call. Synchronous and idempotent; more slices or a larger D / Dv grow the scratch.
+ * The single-slice prepare calls are these at slices = 1. */
+int bsmr_plan_prepare_attention_heads(const bsmr_plan* plan, uint32_t D, uint32_t Dv, uint32_t slices);
+/* 1 exactly when a launch with that many slices would make no allocation, copy or synchronisation
+ * (so monotone: prepared for Z is prepared for every smaller count), else 0; no device call.
+ * bsmr_plan_attention_prepared and its backward twin keep their meaning: slices = 1. */
+int bsmr_plan_attention_heads_prepared(const bsmr_plan* plan, uint32_t D, uint32_t Dv, uint32_t slices);
+int bsmr_plan_prepare_attention_backward_heads(const bsmr_plan* plan, uint32_t D, uint32_t Dv, uint32_t slices);
+int bsmr_plan_attention_backward_heads_prepared(const bsmr_plan* plan, uint32_t D, uint32_t Dv, uint32_t slices);
+/* Host only, no device call: the layout rules above for one operand of `rows` rows of `width`
+ * elements of `elem_bytes` bytes; BSMR_OK or BSMR_ERR_INVALID with bsmr_last_error naming the rule. */
+int bsmr_attention_layout_check(const bsmr_attention_operand* op, uint32_t batches, uint32_t heads,
+                                uint32_t rows, uint32_t width, uint32_t elem_bytes, int is_output);
 
 /* Timing: run `iters` back-to-back SDDMMs on `stream`, timing each kernel with HIP events on
  * that stream (BSMR_ERR_UNSUPPORTED on a capturing stream). Outputs average ms per launch of the dense-tile kernel, the residual kernel and

@@ -8,7 +8,8 @@ Reference interface mirrored (paths relative to the reference root):
   * evaluationReordering                               -> Plan.evaluate   (src/BSMR.cpp:826-994)
 Beyond the reference: the gradients of the SDDMM as SpMM over the same plan (Plan.spmm,
 Plan.spmm_t, Plan.sddmm_backward), the row softmax over the plan's pattern (Plan.softmax,
-Plan.softmax_backward), the fused sparse attention forward and backward (Plan.attention, Plan.attention_backward), and bsmr.autograd,
+Plan.softmax_backward), the fused sparse attention forward and backward (Plan.attention, Plan.attention_backward; Plan.attention_heads and Plan.attention_backward_heads over batch and heads on strided
+operands), and bsmr.autograd,
 which wraps SDDMM, softmax and SpMM for torch.autograd and composes them into sparse attention.
 
 Every call goes through the HIP library; there is no CPU fallback. If the shared library is
@@ -178,6 +179,30 @@ class AttentionBackwardStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class AttentionOperand(C.Structure):
+    """bsmr_attention_operand: one strided operand of the heads calls. Element [b][h][r][c] lies at
+    ptr + (b batch + h head + r row + c) elements of the operand's dtype."""
+    _fields_ = [("ptr", C.c_void_p), ("batch", C.c_uint64), ("head", C.c_uint64), ("row", C.c_uint64)]
+
+    @classmethod
+    def of(cls, x):
+        """An AttentionOperand as it is, None (an output not asked for) as None, a (ptr, batch, head,
+        row) tuple, or a 3- or 4-dimensional tensor with a contiguous last dimension (anything with
+        data_ptr(), stride() and dim(): (H, rows, W) or (B, H, rows, W))."""
+        if x is None or isinstance(x, cls):
+            return x
+        if isinstance(x, (tuple, list)):
+            ptr, batch, head, row = x
+            return cls(ptr, batch, head, row)
+        st = tuple(x.stride())
+        if x.dim() == 3:
+            st = (0,) + st
+        if x.dim() not in (3, 4) or st[3] != 1 or min(st) < 0:
+            raise ValueError("an attention operand must be (H, rows, W) or (B, H, rows, W) with a contiguous last "
+                             f"dimension, got strides {tuple(x.stride())}")
+        return cls(x.data_ptr(), st[0], st[1], st[2])
+
+
 # bsmr_softmax_item.kind beside a packed run's lane-group width 1 .. 64
 SOFTMAX_WAVE = 0x100
 SOFTMAX_BLOCK = 0x200
@@ -210,7 +235,14 @@ EXPORTS = [
     "bsmr_attention_backward", "bsmr_plan_prepare_attention_backward",
     "bsmr_plan_attention_backward_prepared", "bsmr_plan_attention_backward_stats",
     "bsmr_attention_backward_limits",
+    "bsmr_attention_heads", "bsmr_attention_backward_heads", "bsmr_plan_prepare_attention_heads",
+    "bsmr_plan_attention_heads_prepared", "bsmr_plan_prepare_attention_backward_heads",
+    "bsmr_plan_attention_backward_heads_prepared", "bsmr_attention_layout_check",
 ]
+
+# include/bsmr.h BSMR_ATTENTION_MAX_BATCHES, BSMR_ATTENTION_MAX_HEADS
+ATTENTION_MAX_BATCHES = 65535
+ATTENTION_MAX_HEADS = 65535
 
 _lib = None
 
@@ -334,6 +366,19 @@ def lib():
     L.bsmr_plan_attention_backward_stats.restype = C.c_int
     L.bsmr_attention_backward_limits.argtypes = [C.POINTER(C.c_uint32)] * 3
     L.bsmr_attention_backward_limits.restype = None
+    op = C.POINTER(AttentionOperand)
+    L.bsmr_attention_heads.argtypes = [vp, C.c_uint32, C.c_uint32, op, op, op, C.c_uint32, C.c_uint32, C.c_int,
+                                       C.c_float, op, vp, vp]
+    L.bsmr_attention_heads.restype = C.c_int
+    L.bsmr_attention_backward_heads.argtypes = [vp, C.c_uint32, C.c_uint32, op, op, op, op, op, vp, C.c_uint32,
+                                                C.c_uint32, C.c_int, C.c_float, op, op, op, vp]
+    L.bsmr_attention_backward_heads.restype = C.c_int
+    for f in ("bsmr_plan_prepare_attention_heads", "bsmr_plan_attention_heads_prepared",
+              "bsmr_plan_prepare_attention_backward_heads", "bsmr_plan_attention_backward_heads_prepared"):
+        getattr(L, f).argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32]
+        getattr(L, f).restype = C.c_int
+    L.bsmr_attention_layout_check.argtypes = [op] + [C.c_uint32] * 5 + [C.c_int]
+    L.bsmr_attention_layout_check.restype = C.c_int
     L.bsmr_plan_check.argtypes = [vp, C.c_uint32, C.c_int, C.c_int]
     L.bsmr_plan_check.restype = C.c_int
     L.bsmr_check_rphm_arrays.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32] + [_u32p] * 2 + \
@@ -686,6 +731,43 @@ class Plan:
         _check(lib().bsmr_plan_attention_backward_stats(self.h, C.byref(s)), "bsmr_plan_attention_backward_stats")
         return s.as_dict()
 
+    def attention_heads(self, batches, heads, Q, K, V, D, Dv, O, dLse=0, scale=1.0, stream=0, dtype=F32):
+        """bsmr_attention_heads: Plan.attention over batches x heads slices of the plan's pattern in
+        one call (at most two launches). Q, K, V, O: AttentionOperand.of() of each (a tensor view, a
+        (ptr, batch, head, row) tuple or an AttentionOperand; strides in elements); O fp32; dLse a
+        dense (batches, heads, M) fp32 pointer or 0."""
+        ops = [AttentionOperand.of(x) for x in (Q, K, V, O)]
+        ref = [None if o is None else C.byref(o) for o in ops]
+        _check(lib().bsmr_attention_heads(self.h, batches, heads, ref[0], ref[1], ref[2], D, Dv, dtype, scale, ref[3],
+                                          dLse or None, stream or None), "bsmr_attention_heads")
+
+    def attention_backward_heads(self, batches, heads, Q, K, V, O, GO, dLse, D, Dv, GQ=None, GK=None, GV=None, scale=1.0,
+                                 stream=0, dtype=F32):
+        """bsmr_attention_backward_heads: Plan.attention_backward over batches x heads slices in one
+        call (at most five launches). Operands as in attention_heads; O, GO and the outputs fp32; an
+        output that is None is skipped (not all three)."""
+        ops = [AttentionOperand.of(x) for x in (Q, K, V, O, GO, GQ, GK, GV)]
+        ref = [None if o is None else C.byref(o) for o in ops]
+        _check(lib().bsmr_attention_backward_heads(self.h, batches, heads, *ref[:5], dLse or None, D, Dv, dtype, scale,
+                                                   *ref[5:], stream or None), "bsmr_attention_backward_heads")
+
+    def prepare_attention_heads(self, D, Dv, slices):
+        """bsmr_plan_prepare_attention_heads: the attention lists and the scratch of `slices` slices
+        at Dv now, so that the first attention_heads launch can be captured."""
+        _check(lib().bsmr_plan_prepare_attention_heads(self.h, D, Dv, slices), "bsmr_plan_prepare_attention_heads")
+
+    def attention_heads_prepared(self, D, Dv, slices):
+        return bool(lib().bsmr_plan_attention_heads_prepared(self.h, D, Dv, slices))
+
+    def prepare_attention_backward_heads(self, D, Dv, slices):
+        """bsmr_plan_prepare_attention_backward_heads: the backward's lists, delta and scratch of
+        `slices` slices at (D, Dv) now."""
+        _check(lib().bsmr_plan_prepare_attention_backward_heads(self.h, D, Dv, slices),
+               "bsmr_plan_prepare_attention_backward_heads")
+
+    def attention_backward_heads_prepared(self, D, Dv, slices):
+        return bool(lib().bsmr_plan_attention_backward_heads_prepared(self.h, D, Dv, slices))
+
     def sddmm_backward(self, dG, dA, dB, K, dGA, dGB, stream=0, dtype=F32):
         """The gradients of P = sddmm(A, B) from dG = dL/dP (fp32, nnz): dGA (M x K fp32) =
         S(G) B and dGB (N x K fp32) = S(G)^T A. Either output may be 0: that side is skipped."""
@@ -811,6 +893,23 @@ def attention_backward_limits():
     r, c, b = C.c_uint32(), C.c_uint32(), C.c_uint32()
     lib().bsmr_attention_backward_limits(C.byref(r), C.byref(c), C.byref(b))
     return dict(row_chunk=r.value, col_chunk=c.value, max_row_bytes=b.value)
+
+
+def attention_heads_limits():
+    """dict(max_batches, max_heads): BSMR_ATTENTION_MAX_BATCHES and BSMR_ATTENTION_MAX_HEADS of the
+    heads calls (attention_limits() and attention_backward_limits() hold the rest)."""
+    return dict(max_batches=ATTENTION_MAX_BATCHES, max_heads=ATTENTION_MAX_HEADS)
+
+
+def attention_layout_check(op, batches, heads, rows, width, elem_bytes, is_output=False):
+    """bsmr_attention_layout_check (host only, no device call): the layout rules of the heads calls
+    for one operand (AttentionOperand.of(op); None is the null operand) of `rows` rows of `width`
+    elements of `elem_bytes` bytes. Returns None when every rule holds, else the library's message
+    naming the first rule that does not."""
+    o = AttentionOperand.of(op)
+    st = lib().bsmr_attention_layout_check(None if o is None else C.byref(o), batches, heads, rows, width, elem_bytes,
+                                           1 if is_output else 0)
+    return None if st == 0 else lib().bsmr_last_error().decode(errors="replace")
 
 
 def sddmm_cpu(M, N, rowptr, colidx, K, A, B, threads=0):

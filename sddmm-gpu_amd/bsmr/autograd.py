@@ -13,13 +13,17 @@ and, over the same plan, the row softmax, the SpMM and their composition into sp
                                      keeps no nnz-sized tensor; the backward recomputes P and W, or
                                      (backward="fused") is one Plan.attention_backward call that
                                      holds no nnz-sized tensor either
+    attention_fused_heads(plan, Q, K, V)   attention_fused with backward="fused" over (H, M, D) or
+                                     (B, H, M, D) operands with any strides (views of a
+                                     (B, M, H D) projection, an expanded K / V) in one
+                                     Plan.attention_heads call and one Plan.attention_backward_heads call
 
 Every direction is the library's HIP kernels on torch.cuda.current_stream(); torch only owns the
 tensors. Importing this module imports torch (`import bsmr` alone does not).
 """
 import torch
 
-from . import BF16, F16, F32, attention_limits
+from . import BF16, F16, F32, attention_heads_limits, attention_layout_check, attention_limits
 
 _DTYPES = {torch.float32: F32, torch.float16: F16, torch.bfloat16: BF16}
 
@@ -370,3 +374,117 @@ def attention_fused(plan, Q, K, V, scale=None, return_lse=False, backward="recom
     _validate_fused(plan, Q, K, V)
     fn = _AttentionFusedBwd if backward == "fused" else _AttentionFused
     return fn.apply(Q, K, V, plan, scale, bool(return_lse))
+
+
+def _validate_heads(plan, Q, K, V):
+    """The checks of attention_fused_heads, before any launch or build. Returns (lead, D, Dv, dtype):
+    lead = (H,) or (B, H)."""
+    who = "attention_fused_heads"
+    for name, X in (("Q", Q), ("K", K), ("V", V)):
+        if not isinstance(X, torch.Tensor):
+            raise ValueError(f"{who}: {name} must be a torch tensor")
+        if not X.is_cuda:
+            raise ValueError(f"{who}: {name} must be a device tensor, got {X.device}")
+        if X.dtype not in _DTYPES:
+            raise ValueError(f"{who}: {name} must be float32, float16 or bfloat16, got {X.dtype}")
+        if X.dim() not in (3, 4):
+            raise ValueError(f"{who}: {name} must be (H, rows, W) or (B, H, rows, W), got {tuple(X.shape)}")
+    if not (Q.dtype == K.dtype == V.dtype):
+        raise ValueError(f"{who}: Q ({Q.dtype}), K ({K.dtype}) and V ({V.dtype}) must share one dtype")
+    if not (Q.device == K.device == V.device):
+        raise ValueError(f"{who}: Q ({Q.device}), K ({K.device}) and V ({V.device}) must share one device")
+    lead, D, Dv = tuple(Q.shape[:-2]), Q.shape[-1], V.shape[-1]
+    for name, X, rows, W in (("Q", Q, plan.M, D), ("K", K, plan.N, D), ("V", V, plan.N, Dv)):
+        if tuple(X.shape) != lead + (rows, W):
+            raise ValueError(f"{who}: {name} must be {lead + (rows, W)}, got {tuple(X.shape)}")
+    lim = attention_heads_limits()
+    B, H = (1,) * (2 - len(lead)) + lead
+    if not (1 <= B <= lim["max_batches"] and 1 <= H <= lim["max_heads"]):
+        raise ValueError(f"{who}: batch = {B} and heads = {H} must be 1 .. {lim['max_batches']} and 1 .. {lim['max_heads']}")
+    mult = 16 if Q.dtype == torch.float32 else 32
+    if D == 0 or D % mult or Dv == 0 or Dv % 16:
+        raise ValueError(f"{who}: D = {D} must be a positive multiple of {mult} for {Q.dtype} and Dv = {Dv} of 16")
+    cap = attention_limits()["max_row_bytes"]
+    if max(D, Dv) * Q.element_size() > cap:
+        raise ValueError(f"{who}: rows of D = {D} / Dv = {Dv} {Q.dtype} exceed {cap} bytes")
+    for name, X, rows, W in (("Q", Q, plan.M, D), ("K", K, plan.N, D), ("V", V, plan.N, Dv)):
+        if X.stride(-1) != 1 or min(X.stride()) < 0:
+            raise ValueError(f"{who}: {name} must have a contiguous last dimension, got strides {tuple(X.stride())}")
+        bad = attention_layout_check(X, B, H, rows, W, X.element_size(), False)
+        if bad is not None:
+            raise ValueError(f"{who}: {name}: {bad}")
+    return lead, D, Dv, _DTYPES[Q.dtype]
+
+
+def _dense_like(X, shape, dtype=torch.float32):
+    """An uninitialised dense tensor of `shape` whose dimensions are laid out in X's dimension order
+    (by stride, descending; an expanded or size-1 dimension keeps its standard place)."""
+    nd = len(shape)
+    if any(st == 0 and n > 1 for st, n in zip(X.stride(), X.shape)):
+        return torch.empty(shape, dtype=dtype, device=X.device)
+    order = sorted(range(nd - 1), key=lambda i: (-X.stride(i), i)) + [nd - 1]
+    inv = [order.index(i) for i in range(nd)]
+    return torch.empty([shape[i] for i in order], dtype=dtype, device=X.device).permute(inv)
+
+
+class _AttentionFusedHeads(torch.autograd.Function):
+    """attention_fused_heads: the forward always takes LSE and saves Q, K, V, O and LSE; the backward
+    is one Plan.attention_backward_heads call."""
+
+    @staticmethod
+    def forward(ctx, Q, K, V, plan, scale, want_lse, checked):
+        lead, D, Dv, dtype = checked  # (_validate_heads, run once by attention_fused_heads)
+        B, H = (1,) * (2 - len(lead)) + lead
+        O = _dense_like(Q, lead + (plan.M, Dv))
+        lse = torch.empty(lead + (plan.M,), dtype=torch.float32, device=Q.device)
+        plan.attention_heads(B, H, Q, K, V, D, Dv, O, lse.data_ptr(), scale, stream=_stream(), dtype=dtype)
+        ctx.plan, ctx.scale, ctx.dims = plan, scale, (B, H, D, Dv, dtype)
+        ctx.save_for_backward(Q, K, V, O, lse)
+        if not want_lse:
+            return O
+        ctx.mark_non_differentiable(lse)
+        return O, lse
+
+    @staticmethod
+    def backward(ctx, grad, *_):
+        Q, K, V, O, lse = ctx.saved_tensors
+        plan = ctx.plan
+        B, H, D, Dv, dtype = ctx.dims
+        if not any(ctx.needs_input_grad[:3]):
+            return None, None, None, None, None, None, None
+        dO = grad if grad.dtype == torch.float32 else grad.float()
+        if dO.stride(-1) != 1 or attention_layout_check(dO, B, H, plan.M, Dv, 4, False) is not None:
+            dO = dO.contiguous()
+        out = [_dense_like(X, X.shape) if need else None for need, X in zip(ctx.needs_input_grad[:3], (Q, K, V))]
+        plan.attention_backward_heads(B, H, Q, K, V, O, dO, lse.data_ptr(), D, Dv, out[0], out[1], out[2], ctx.scale,
+                                      stream=_stream(), dtype=dtype)
+        gQ, gK, gV = (None if t is None else t.to(X.dtype) for t, X in zip(out, (Q, K, V)))
+        return gQ, gK, gV, None, None, None, None
+
+
+def attention_fused_heads(plan, Q, K, V, scale=None, return_lse=False):
+    """attention_fused(..., backward="fused") over heads and an optional batch of one sparsity
+    pattern: Q (H, M, D) or (B, H, M, D), K and V the same with N rows (V of width Dv). Returns O
+    (..., M, Dv) float32 and, with return_lse=True, LSE (..., M) float32, non-differentiable.
+
+    Any strides with a contiguous last dimension are taken as they are, without a copy:
+    x.view(B, M, H, D).transpose(1, 2) of a (B, M, H D) projection, K.expand(B, H, N, D) of one K
+    shared by all heads. The layout rules are the library's (bsmr.attention_layout_check: 16-byte
+    aligned pointers and strides, row stride >= the row width); a violation, like a wrong shape,
+    dtype or dimension, raises ValueError before any launch or build.
+
+    O is allocated dense in Q's dimension order, so for a Q that came from (B, M, H D),
+    O.transpose(1, 2).reshape(B, M, H Dv) is a view. One Plan.attention_heads call (at most two
+    launches) forward; the forward always takes LSE and saves Q, K, V, O and LSE, and the backward
+    is one Plan.attention_backward_heads call (at most five launches) that passes NULL for the
+    outputs no input needs. Gradients are dense, in their input's dimension order, and cast to the
+    input's dtype; for an expanded input they are dense in standard order and torch's expand
+    backward sums them. Slice (b, h) of every result equals, bit for bit, attention_fused(...,
+    backward="fused") on contiguous copies of that slice."""
+    if scale is None:
+        if not isinstance(Q, torch.Tensor) or Q.dim() not in (3, 4) or Q.shape[-1] == 0:
+            raise ValueError("attention_fused_heads: Q must be an (H, M, D) or (B, H, M, D) tensor with D > 0")
+        scale = Q.shape[-1] ** -0.5
+    scale = _valid_scale("attention_fused_heads", scale)
+    checked = _validate_heads(plan, Q, K, V)
+    return _AttentionFusedHeads.apply(Q, K, V, plan, scale, bool(return_lse), checked)

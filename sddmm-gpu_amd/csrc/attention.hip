@@ -19,6 +19,14 @@
 // takes M = max m_s, scales each partial once by 2^((m_s - M) c) and adds l and acc in segment
 // order. fp32 accumulation throughout; no atomics: the order is a function of the row's length,
 // D, Dv and the dtype alone.
+//
+// Batch and heads (bsmr_attention_heads): the same kernels over Z = batches x heads slices of one
+// pattern in one grid. blockIdx.x stays the segment index, so that a slice's workgroups are
+// dispatched together; blockIdx.y is the head and blockIdx.z the batch. Every operand carries a
+// batch and a head stride (64-bit, bytes) and a row stride (32-bit, bytes); the slice's base
+// pointers are wave-uniform and computed once at kernel entry in scalar registers. LSE is dense
+// (batches, heads, M) and the scratch is per slice. bsmr_attention is the one-slice, dense-stride
+// case of the same launch code.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -27,6 +35,7 @@
 #include <vector>
 
 #include "attention_common.hpp"
+#include "attention_layout.hpp"
 #include "plan.hpp"
 #include "row_elems.hpp"
 #include "spmm_schedule.hpp"
@@ -46,13 +55,17 @@ static_assert(ATTN_CHUNK % 64 == 0 && ATTN_CHUNK >= 64 && ATTN_CHUNK <= 1024, "b
 struct AttnArgs {
     const SpmmSeg* segs;
     const u32* colidx;
-    const char* Q;      // M rows of kBytes
-    const char* K;      // N rows of kBytes
-    const char* V;      // N rows of vBytes
-    float* O;           // M x Dv
-    float* lse;         // M, or null
-    float* pacc;        // partial slots x Dv
-    float* pml;         // partial slots x (m, l)
+    const char* Q;      // per slice M rows of kBytes, qRow bytes apart
+    const char* K;      // per slice N rows of kBytes, kRow bytes apart
+    const char* V;      // per slice N rows of vBytes, vRow bytes apart
+    char* O;            // per slice M rows of Dv floats, oRow bytes apart
+    float* lse;         // slices x M, or null
+    float* pacc;        // slices x partial slots x Dv
+    float* pml;         // behind them: slices x partial slots x (m, l); both 16-byte aligned per slice
+    u64 qB, qH, kB, kH, vB, vH, oB, oH;  // batch and head strides in bytes
+    u32 partials;       // partial slots per slice
+    u32 qRow, kRow, vRow, oRow;  // row strides in bytes
+    u32 heads, M;
     u32 nSegs, Dv, kBytes, vBytes;
     u32 lanes;          // generic form: lanes per lane group (a power of two, 4 .. 64)
     float c, scale;     // scale log2(e), rounded once from double; scale
@@ -69,7 +82,9 @@ __device__ __forceinline__ float inverse_of(float s) { return s == 0.f ? 0.f : 1
 // a.lanes (every other row size: multiples of 32 bytes from 64 on). Lanes past the K row or the
 // V row idle for that operand. At most 64 VGPRs (k_softmax_rows' lesson: two resident workgroups
 // of 16 waves)
-template <int DT, int LANES>
+// SLICES: false is the one-slice instantiation that bsmr_attention keeps (no slice arithmetic, no
+// branch: the shared form measured 0.3 us slower on C2)
+template <int DT, int LANES, bool SLICES>
 __global__ __launch_bounds__(ATTN_WAVES * 64) __attribute__((amdgpu_waves_per_eu(8, 8)))
 void k_attention(const AttnArgs a) {
     using E = Elem<DT>;
@@ -84,6 +99,18 @@ void k_attention(const AttnArgs a) {
     const u32 segId = blockIdx.x * ATTN_WAVES + wave;
     if (segId >= a.nSegs) return;
     const SpmmSeg sg = a.segs[segId];
+    // the slice (head blockIdx.y of batch blockIdx.z): wave-uniform 64-bit bases, scalar registers
+    size_t slice = 0;
+    const char *Qs = a.Q, *Ks = a.K, *Vs = a.V;
+    char* Os = a.O;
+    if (SLICES) {
+        const u32 head = blockIdx.y, bat = blockIdx.z;
+        slice = static_cast<size_t>(bat) * a.heads + head;
+        Qs += bat * a.qB + head * a.qH;
+        Ks += bat * a.kB + head * a.kH;
+        Vs += bat * a.vB + head * a.vH;
+        Os += bat * a.oB + head * a.oH;
+    }
     const u32 L = LANES ? static_cast<u32>(LANES) : a.lanes;
     const u32 G = 64u / L;  // entries per instruction
     const u32 g = lane / L, l = lane % L;
@@ -94,7 +121,7 @@ void k_attention(const AttnArgs a) {
 #pragma unroll
     for (int i = 0; i < EPL; ++i) q[i] = 0.f;
     if (liveK)
-        E::unpack(*reinterpret_cast<const uint4*>(a.Q + static_cast<size_t>(sg.dst) * a.kBytes + l * 16u), q);
+        E::unpack(*reinterpret_cast<const uint4*>(Qs + static_cast<size_t>(sg.dst) * a.qRow + l * 16u), q);
     // a batch's column indices, one entry per lane. The first batch stays in a register for both
     // phases (a row of up to 64 entries reads its indices once); a later batch is loaded under
     // the gathers of the one before it, in each phase (4 bytes per entry from L2 against a
@@ -132,7 +159,7 @@ void k_attention(const AttnArgs a) {
 #pragma unroll
             for (u32 u = 0; u < ATTN_UNROLL; ++u) {
                 const u32 col = __shfl(cj, static_cast<int>((j + u) * G + g));
-                w[u] = liveK ? row_of(a.K, a.kBytes, col) : make_uint4(0, 0, 0, 0);
+                w[u] = liveK ? row_of(Ks, a.kRow, col) : make_uint4(0, 0, 0, 0);
             }
 #pragma unroll
             for (u32 u = 0; u < ATTN_UNROLL; ++u) dot(w[u], true, b0 + (j + u) * G + g);
@@ -141,7 +168,7 @@ void k_attention(const AttnArgs a) {
             const u32 idx = j * G + g;
             const u32 col = __shfl(cj, static_cast<int>(idx & 63u));
             const bool valid = idx < nb;
-            dot(liveK && valid ? row_of(a.K, a.kBytes, col) : make_uint4(0, 0, 0, 0), valid, b0 + idx);
+            dot(liveK && valid ? row_of(Ks, a.kRow, col) : make_uint4(0, 0, 0, 0), valid, b0 + idx);
         }
         cj = next;
     }
@@ -178,7 +205,7 @@ void k_attention(const AttnArgs a) {
             for (u32 u = 0; u < ATTN_UNROLL; ++u) {
                 const u32 idx = (j + u) * G + g;
                 const u32 col = __shfl(cj, static_cast<int>(idx));
-                w[u] = liveV ? row_of(a.V, a.vBytes, col) : make_uint4(0, 0, 0, 0);
+                w[u] = liveV ? row_of(Vs, a.vRow, col) : make_uint4(0, 0, 0, 0);
                 p[u] = score[b0 + idx];
             }
 #pragma unroll
@@ -187,7 +214,7 @@ void k_attention(const AttnArgs a) {
         for (; j * G < nb; ++j) {
             const u32 idx = j * G + g;
             const u32 col = __shfl(cj, static_cast<int>(idx & 63u));
-            if (idx < nb) add(liveV ? row_of(a.V, a.vBytes, col) : make_uint4(0, 0, 0, 0), score[b0 + idx]);
+            if (idx < nb) add(liveV ? row_of(Vs, a.vRow, col) : make_uint4(0, 0, 0, 0), score[b0 + idx]);
         }
         cj = next;
     }
@@ -207,33 +234,45 @@ void k_attention(const AttnArgs a) {
     if (sg.part == SPMM_DIRECT) {
         const float inv = inverse_of(ls);
         if (g == 0 && liveV) {
-            float* o = a.O + static_cast<size_t>(sg.dst) * a.Dv + static_cast<size_t>(l) * EPL;
+            float* o = reinterpret_cast<float*>(Os + static_cast<size_t>(sg.dst) * a.oRow) + static_cast<size_t>(l) * EPL;
 #pragma unroll
             for (int i = 0; i < EPL; i += 4)
                 *reinterpret_cast<float4*>(o + i) =
                     make_float4(acc[i] * inv, acc[i + 1] * inv, acc[i + 2] * inv, acc[i + 3] * inv);
         }
-        if (lane == 0 && a.lse) a.lse[sg.dst] = m * a.scale + logf(ls);
+        if (lane == 0 && a.lse) a.lse[slice * a.M + sg.dst] = m * a.scale + logf(ls);
     } else {
         if (g == 0 && liveV) {
-            float* o = a.pacc + static_cast<size_t>(sg.part) * a.Dv + static_cast<size_t>(l) * EPL;
+            float* o = a.pacc + (slice * a.partials + sg.part) * a.Dv + static_cast<size_t>(l) * EPL;
 #pragma unroll
             for (int i = 0; i < EPL; i += 4)
                 *reinterpret_cast<float4*>(o + i) = make_float4(acc[i], acc[i + 1], acc[i + 2], acc[i + 3]);
         }
         if (lane == 0) {
-            a.pml[2u * static_cast<size_t>(sg.part)] = m;
-            a.pml[2u * static_cast<size_t>(sg.part) + 1u] = ls;
+            float* ml = a.pml + 2u * (slice * a.partials + sg.part);
+            ml[0] = m;
+            ml[1] = ls;
         }
     }
 }
 
 // a split row: M = max_s m_s, then every partial scaled once by f_s = 2^((m_s - M) c) (a rounded
 // product each, never fused into the sum) and added in segment order; one thread per four columns
-__global__ __launch_bounds__(256) void k_attention_reduce(const SpmmRed* reds, u32 nReds, const float* pacc,
-                                                          const float* pml, float* O, float* lse, u32 Dv,
-                                                          float c, float scale) {
+template <bool SLICES>
+__global__ __launch_bounds__(256) void k_attention_reduce(const AttnArgs a, const SpmmRed* reds, u32 nReds) {
 #pragma clang fp contract(off)
+    const u32 Dv = a.Dv;
+    const float c = a.c, scale = a.scale;
+    size_t slice = 0;
+    char* O = a.O;
+    if (SLICES) {
+        const u32 head = blockIdx.y, bat = blockIdx.z;
+        slice = static_cast<size_t>(bat) * a.heads + head;
+        O += bat * a.oB + head * a.oH;
+    }
+    const float* pacc = a.pacc + slice * a.partials * Dv;
+    const float* pml = a.pml + 2u * slice * a.partials;
+    float* lse = a.lse ? a.lse + slice * a.M : nullptr;
     const u32 q4 = Dv / 4u;
     const size_t t = static_cast<size_t>(blockIdx.x) * 256u + threadIdx.x;
     if (t >= static_cast<size_t>(nReds) * q4) return;
@@ -257,22 +296,29 @@ __global__ __launch_bounds__(256) void k_attention_reduce(const SpmmRed* reds, u
         s.w = i ? s.w + fw : fw;
     }
     const float inv = inverse_of(ls);
-    reinterpret_cast<float4*>(O + static_cast<size_t>(r.dst) * Dv)[q] =
+    reinterpret_cast<float4*>(O + static_cast<size_t>(r.dst) * a.oRow)[q] =
         make_float4(s.x * inv, s.y * inv, s.z * inv, s.w * inv);
     if (q == 0 && lse) lse[r.dst] = m * scale + logf(ls);
 }
 
 using AttnFn = void (*)(const AttnArgs);
 
-template <int DT>
+template <int DT, bool SLICES>
 AttnFn pick_attention(u32 rowBytes) {
     switch (rowBytes) {
-        case 128: return k_attention<DT, 8>;
-        case 256: return k_attention<DT, 16>;
-        case 512: return k_attention<DT, 32>;
-        case 1024: return k_attention<DT, 64>;
-        default: return k_attention<DT, 0>;
+        case 128: return k_attention<DT, 8, SLICES>;
+        case 256: return k_attention<DT, 16, SLICES>;
+        case 512: return k_attention<DT, 32, SLICES>;
+        case 1024: return k_attention<DT, 64, SLICES>;
+        default: return k_attention<DT, 0, SLICES>;
     }
+}
+
+template <bool SLICES>
+AttnFn pick_attention(int dtype, u32 rowBytes) {
+    return dtype == BSMR_F32   ? pick_attention<BSMR_F32, SLICES>(rowBytes)
+           : dtype == BSMR_F16 ? pick_attention<BSMR_F16, SLICES>(rowBytes)
+                               : pick_attention<BSMR_BF16, SLICES>(rowBytes);
 }
 
 }  // namespace
@@ -344,18 +390,23 @@ int attn_row_lists(const Plan& p, u32 chunk, const char* who, SpmmLists& L) {
 
 namespace {
 
-bool attention_ready(const Plan::AttentionState& S, u32 Dv) {
-    return S.built && (S.partials == 0 || S.scratchDv >= Dv);
+size_t attention_scratch_floats(const Plan::AttentionState& S, u32 Dv, u32 slices) {
+    return attn_sat_mul(slices, S.partials, Dv + 2u);
 }
 
-// build the segment list (once) and size the scratch for Dv; layout_mu held. Synchronous on the
-// plan's stream.
-int build_attention(const Plan& p, u32 Dv) {
+bool attention_ready(const Plan::AttentionState& S, u32 Dv, u32 slices) {
+    // (DevBuf holds a size only with its memory: a failed grow leaves the old buffer and its size)
+    return S.built && S.scratch.size() >= attention_scratch_floats(S, Dv, slices);
+}
+
+// build the segment list (once) and size the per-slice scratch for (Dv, slices): it grows and
+// never shrinks; layout_mu held. Synchronous on the plan's stream.
+int build_attention(const Plan& p, u32 Dv, u32 slices, const char* who) {
     Plan::AttentionState& S = p.attention;
     const hipStream_t s = p.stream;
     if (!S.built) {
         SpmmLists L;
-        BSMR_CHECK(attn_row_lists(p, ATTN_CHUNK, "bsmr_plan_prepare_attention", L));
+        BSMR_CHECK(attn_row_lists(p, ATTN_CHUNK, who, L));
         // (on side 1 L.src is colidx and L.vpos the identity: the plan's own colidx serves)
         BSMR_CHECK(S.segs.upload(L.segs.data(), L.segs.size(), s));
         BSMR_CHECK(S.reds.upload(L.reds.data(), L.reds.size(), s));
@@ -365,18 +416,103 @@ int build_attention(const Plan& p, u32 Dv) {
         S.splitRows = L.splitDsts;
         S.partials = L.partials;
         S.maxRow = L.maxList;
-        S.scratchDv = 0;
         S.built = true;
     }
-    if (S.partials != 0 && S.scratchDv < Dv) {
-        S.scratchDv = 0;
-        BSMR_CHECK(S.scratch.alloc(static_cast<size_t>(S.partials) * (Dv + 2u)));
-        S.scratchDv = Dv;
+    return S.scratch.grow(attention_scratch_floats(S, Dv, slices));
+}
+
+// the launches of bsmr_attention and bsmr_attention_heads, arguments already validated: `who` and
+// `prep` name the entry point and its prepare call in errors
+int attention_launch(const char* who, const char* prep, const bsmr_plan* plan, u32 batches, u32 heads,
+                     const bsmr_attention_operand& Q, const bsmr_attention_operand& K, const bsmr_attention_operand& V,
+                     u32 D, u32 Dv, int dtype, float scale, float c, const bsmr_attention_operand& O, float* dLse,
+                     void* stream) {
+    const Plan& p = plan->p;
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    const Plan::AttentionState& S = p.attention;
+    const u32 slices = batches * heads;  // (both at most 65535)
+    AttnArgs a{};
+    const SpmmRed* reds = nullptr;
+    u32 nReds = 0, partials = 0;
+    {
+        std::lock_guard<std::mutex> g(p.layout_mu);
+        if (!attention_ready(S, Dv, slices)) {
+            const LaunchSite at{s, who, prep, D, dtype};
+            const int st = lazy_build_guard(at);
+            if (st == BSMR_ERR_NOT_PREPARED)  // (the guard's own message names a (K, dtype) layout)
+                set_error(std::string(who) + ": stream is capturing and the attention lists (or their scratch for Dv = " +
+                          std::to_string(Dv) + (slices > 1 ? ", " + std::to_string(slices) + " slices" : std::string()) +
+                          ") are not built; call " + prep + " first");
+            BSMR_CHECK(st);
+            BSMR_CHECK(build_attention(p, Dv, slices, prep));
+        }
+        a.segs = S.segs.data();
+        a.nSegs = S.nSegs;
+        a.pacc = S.scratch.data();
+        reds = S.reds.data();
+        nReds = S.nReds;
+        partials = S.partials;
+    }
+    const u32 esz = dtype == BSMR_F32 ? 4u : 2u;
+    a.pml = a.pacc ? a.pacc + static_cast<size_t>(slices) * partials * Dv : nullptr;
+    a.partials = partials;
+    a.colidx = p.colidx.data();
+    const AttnOpBytes q = attn_op_bytes(&Q, batches, heads, p.M, esz), k = attn_op_bytes(&K, batches, heads, p.N, esz),
+                      v = attn_op_bytes(&V, batches, heads, p.N, esz), o = attn_op_bytes(&O, batches, heads, p.M, 4u);
+    a.Q = q.ptr, a.qB = q.batch, a.qH = q.head, a.qRow = q.row;
+    a.K = k.ptr, a.kB = k.batch, a.kH = k.head, a.kRow = k.row;
+    a.V = v.ptr, a.vB = v.batch, a.vH = v.head, a.vRow = v.row;
+    a.O = o.ptr, a.oB = o.batch, a.oH = o.head, a.oRow = o.row;
+    a.lse = dLse;
+    a.heads = heads;
+    a.M = p.M;
+    a.Dv = Dv;
+    a.kBytes = D * esz;
+    a.vBytes = Dv * esz;
+    a.c = c;
+    a.scale = scale;
+    const u32 rowBytes = std::max(a.kBytes, a.vBytes);
+    a.lanes = attn_lanes(rowBytes);
+    const AttnFn fn = slices > 1 ? pick_attention<true>(dtype, rowBytes) : pick_attention<false>(dtype, rowBytes);
+    if (a.nSegs) {
+        const u32 grid = (a.nSegs + ATTN_WAVES - 1) / ATTN_WAVES;
+        hipLaunchKernelGGL(fn, dim3(grid, heads, batches), dim3(ATTN_WAVES * 64), 0, s, a);
+        BSMR_HIP(hipGetLastError());
+    }
+    if (nReds) {
+        const size_t threads = static_cast<size_t>(nReds) * (Dv / 4u);
+        const dim3 rgrid(static_cast<u32>((threads + 255) / 256), heads, batches);
+        if (slices > 1)
+            hipLaunchKernelGGL(k_attention_reduce<true>, rgrid, dim3(256), 0, s, a, reds, nReds);
+        else
+            hipLaunchKernelGGL(k_attention_reduce<false>, rgrid, dim3(256), 0, s, a, reds, nReds);
+        BSMR_HIP(hipGetLastError());
     }
     return BSMR_OK;
 }
 
 }  // namespace
+
+// (attention_common.hpp)
+int attn_check_slices(const char* who, u32 slices) {
+    if (slices == 0 || slices > BSMR_ATTENTION_MAX_BATCHES * static_cast<u64>(BSMR_ATTENTION_MAX_HEADS)) {
+        set_error(std::string(who) + ": slices must be 1 .. BSMR_ATTENTION_MAX_BATCHES x BSMR_ATTENTION_MAX_HEADS");
+        return BSMR_ERR_INVALID;
+    }
+    return BSMR_OK;
+}
+
+// (attention_common.hpp) one operand of a heads call against the layout rules
+int attn_check_operand(const char* who, const char* name, const bsmr_attention_operand* op, u32 batches, u32 heads,
+                       u32 rows, u32 width, u32 esz, bool is_output) {
+    std::string err;
+    if (attention_layout_check(op, batches, heads, rows, width, esz, is_output, err)) {
+        set_error(std::string(who) + ": " + name + ": " + err);
+        return BSMR_ERR_INVALID;
+    }
+    return BSMR_OK;
+}
+
 }  // namespace bsmr
 
 using namespace bsmr;
@@ -401,60 +537,41 @@ extern "C" int bsmr_attention(const bsmr_plan* plan, const void* dQ, const void*
     BSMR_CHECK(attn_validate_scale(who, scale, &c));
     BSMR_CHECK(attn_validate_dims(who, D, Dv, dtype));
     const Plan& p = plan->p;
-    const hipStream_t s = static_cast<hipStream_t>(stream);
-    const Plan::AttentionState& S = p.attention;
-    AttnArgs a{};
-    const SpmmRed* reds = nullptr;
-    u32 nReds = 0, partials = 0;
-    {
-        std::lock_guard<std::mutex> g(p.layout_mu);
-        if (!attention_ready(S, Dv)) {
-            const LaunchSite at{s, who, "bsmr_plan_prepare_attention", D, dtype};
-            const int st = lazy_build_guard(at);
-            if (st == BSMR_ERR_NOT_PREPARED)  // (the guard's own message names a (K, dtype) layout)
-                set_error("bsmr_attention: stream is capturing and the attention lists (or their scratch for Dv = " +
-                          std::to_string(Dv) + ") are not built; call bsmr_plan_prepare_attention first");
-            BSMR_CHECK(st);
-            BSMR_CHECK(build_attention(p, Dv));
-        }
-        a.segs = S.segs.data();
-        a.nSegs = S.nSegs;
-        a.pacc = S.scratch.data();
-        reds = S.reds.data();
-        nReds = S.nReds;
-        partials = S.partials;
+    return attention_launch(who, "bsmr_plan_prepare_attention", plan, 1, 1, attention_dense_operand(dQ, 1, p.M, D),
+                            attention_dense_operand(dK, 1, p.N, D), attention_dense_operand(dV, 1, p.N, Dv), D, Dv, dtype,
+                            scale, c, attention_dense_operand(dO, 1, p.M, Dv), dLse, stream);
+}
+
+extern "C" int bsmr_attention_heads(const bsmr_plan* plan, uint32_t batches, uint32_t heads,
+                                    const bsmr_attention_operand* Q, const bsmr_attention_operand* K,
+                                    const bsmr_attention_operand* V, uint32_t D, uint32_t Dv, int dtype, float scale,
+                                    const bsmr_attention_operand* O, float* dLse, void* stream) {
+    const char* who = "bsmr_attention_heads";
+    if (!plan) {
+        set_error("bsmr_attention_heads: null plan");
+        return BSMR_ERR_INVALID;
     }
+    if (reinterpret_cast<uintptr_t>(dLse) & 3u) {
+        set_error("bsmr_attention_heads: dLse must be 4-byte aligned");
+        return BSMR_ERR_INVALID;
+    }
+    float c;
+    BSMR_CHECK(attn_validate_scale(who, scale, &c));
+    BSMR_CHECK(attn_validate_dims(who, D, Dv, dtype));
+    const Plan& p = plan->p;
     const u32 esz = dtype == BSMR_F32 ? 4u : 2u;
-    a.pml = a.pacc ? a.pacc + static_cast<size_t>(partials) * Dv : nullptr;
-    a.colidx = p.colidx.data();
-    a.Q = static_cast<const char*>(dQ);
-    a.K = static_cast<const char*>(dK);
-    a.V = static_cast<const char*>(dV);
-    a.O = dO;
-    a.lse = dLse;
-    a.Dv = Dv;
-    a.kBytes = D * esz;
-    a.vBytes = Dv * esz;
-    a.c = c;
-    a.scale = scale;
-    const u32 rowBytes = std::max(a.kBytes, a.vBytes);
-    a.lanes = 4;
-    while (a.lanes * 16u < rowBytes) a.lanes <<= 1;
-    const AttnFn fn = dtype == BSMR_F32   ? pick_attention<BSMR_F32>(rowBytes)
-                      : dtype == BSMR_F16 ? pick_attention<BSMR_F16>(rowBytes)
-                                          : pick_attention<BSMR_BF16>(rowBytes);
-    if (a.nSegs) {
-        const u32 grid = (a.nSegs + ATTN_WAVES - 1) / ATTN_WAVES;
-        hipLaunchKernelGGL(fn, dim3(grid), dim3(ATTN_WAVES * 64), 0, s, a);
-        BSMR_HIP(hipGetLastError());
-    }
-    if (nReds) {
-        const size_t threads = static_cast<size_t>(nReds) * (Dv / 4u);
-        hipLaunchKernelGGL(k_attention_reduce, dim3(static_cast<u32>((threads + 255) / 256)), dim3(256), 0, s, reds,
-                           nReds, a.pacc, a.pml, dO, dLse, Dv, c, scale);
-        BSMR_HIP(hipGetLastError());
-    }
-    return BSMR_OK;
+    BSMR_CHECK(attn_check_operand(who, "Q", Q, batches, heads, p.M, D, esz, false));
+    BSMR_CHECK(attn_check_operand(who, "K", K, batches, heads, p.N, D, esz, false));
+    BSMR_CHECK(attn_check_operand(who, "V", V, batches, heads, p.N, Dv, esz, false));
+    BSMR_CHECK(attn_check_operand(who, "O", O, batches, heads, p.M, Dv, 4u, true));
+    return attention_launch(who, "bsmr_plan_prepare_attention_heads", plan, batches, heads, *Q, *K, *V, D, Dv, dtype, scale,
+                            c, *O, dLse, stream);
+}
+
+extern "C" int bsmr_attention_layout_check(const bsmr_attention_operand* op, uint32_t batches, uint32_t heads,
+                                           uint32_t rows, uint32_t width, uint32_t elem_bytes, int is_output) {
+    return attn_check_operand("bsmr_attention_layout_check", "operand", op, batches, heads, rows, width, elem_bytes,
+                              is_output != 0);
 }
 
 extern "C" int bsmr_plan_prepare_attention(const bsmr_plan* plan, uint32_t D, uint32_t Dv) {
@@ -464,7 +581,7 @@ extern "C" int bsmr_plan_prepare_attention(const bsmr_plan* plan, uint32_t D, ui
     }
     BSMR_CHECK(attn_validate_prepare_dims("bsmr_plan_prepare_attention", D, Dv));
     std::lock_guard<std::mutex> g(plan->p.layout_mu);
-    return build_attention(plan->p, Dv);
+    return build_attention(plan->p, Dv, 1, "bsmr_plan_prepare_attention");
 }
 
 extern "C" int bsmr_plan_attention_prepared(const bsmr_plan* plan, uint32_t D, uint32_t Dv) {
@@ -474,7 +591,30 @@ extern "C" int bsmr_plan_attention_prepared(const bsmr_plan* plan, uint32_t D, u
     }
     if (attn_validate_prepare_dims("bsmr_plan_attention_prepared", D, Dv) != BSMR_OK) return 0;
     std::lock_guard<std::mutex> g(plan->p.layout_mu);
-    return attention_ready(plan->p.attention, Dv) ? 1 : 0;
+    return attention_ready(plan->p.attention, Dv, 1) ? 1 : 0;
+}
+
+extern "C" int bsmr_plan_prepare_attention_heads(const bsmr_plan* plan, uint32_t D, uint32_t Dv, uint32_t slices) {
+    const char* who = "bsmr_plan_prepare_attention_heads";
+    if (!plan) {
+        set_error("bsmr_plan_prepare_attention_heads: null plan");
+        return BSMR_ERR_INVALID;
+    }
+    BSMR_CHECK(attn_check_slices(who, slices));
+    BSMR_CHECK(attn_validate_prepare_dims(who, D, Dv));
+    std::lock_guard<std::mutex> g(plan->p.layout_mu);
+    return build_attention(plan->p, Dv, slices, who);
+}
+
+extern "C" int bsmr_plan_attention_heads_prepared(const bsmr_plan* plan, uint32_t D, uint32_t Dv, uint32_t slices) {
+    const char* who = "bsmr_plan_attention_heads_prepared";
+    if (!plan) {
+        set_error("bsmr_plan_attention_heads_prepared: null plan");
+        return 0;
+    }
+    if (attn_check_slices(who, slices) != BSMR_OK || attn_validate_prepare_dims(who, D, Dv) != BSMR_OK) return 0;
+    std::lock_guard<std::mutex> g(plan->p.layout_mu);
+    return attention_ready(plan->p.attention, Dv, slices) ? 1 : 0;
 }
 
 extern "C" int bsmr_plan_attention_stats(const bsmr_plan* plan, bsmr_attention_stats* out) {

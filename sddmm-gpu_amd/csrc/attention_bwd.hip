@@ -22,6 +22,13 @@
 // where O is a V row. A group accumulates in entry order, one FMA per (entry, element); the groups
 // are added in group order and the partials in segment order. fp32 throughout, no atomics: the
 // order is a function of the destination's list length, D, Dv and the dtype alone.
+//
+// Batch and heads (bsmr_attention_backward_heads): the same kernels over Z = batches x heads slices
+// in one grid, as in attention.hip: blockIdx.x the segment (or row group, or reduce thread block),
+// blockIdx.y the head, blockIdx.z the batch; per-operand batch / head strides (64-bit, bytes) and
+// row strides (32-bit, bytes); slice bases wave-uniform, computed once at kernel entry; LSE and
+// delta dense (slices x M); scratch per slice. bsmr_attention_backward is the one-slice,
+// dense-stride case of the same launch code.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -30,6 +37,7 @@
 #include <vector>
 
 #include "attention_common.hpp"
+#include "attention_layout.hpp"
 #include "plan.hpp"
 #include "row_elems.hpp"
 #include "spmm_schedule.hpp"
@@ -53,16 +61,20 @@ constexpr float LOG2E_F = 1.44269504088896340736f;
 struct BwdArgs {
     const SpmmSeg* segs;
     const u32* idx;      // rows side: the plan's colidx; columns side: the row of every entry
-    const char* Q;       // M rows of kBytes
-    const char* K;       // N rows of kBytes
-    const char* V;       // N rows of vBytes
-    const float* GO;     // M x Dv
-    const float* lse;    // M
-    const float* delta;  // M
-    float* Y0;           // rows side: GQ (M x D); columns side: GK (N x D) or null
-    float* Y1;           // columns side: GV (N x Dv) or null
-    float* P0;           // partial slots x D
-    float* P1;           // columns side: partial slots x Dv
+    const char* Q;       // per slice M rows of kBytes, qRow bytes apart
+    const char* K;       // per slice N rows of kBytes, kRow bytes apart
+    const char* V;       // per slice N rows of vBytes, vRow bytes apart
+    const char* GO;      // per slice M rows of Dv floats, goRow bytes apart
+    const float* lse;    // slices x M
+    const float* delta;  // slices x M
+    char* Y0;            // rows side: GQ (rows of D floats); columns side: GK (rows of D floats) or null
+    char* Y1;            // columns side: GV (rows of Dv floats) or null
+    float* P0;           // per slice: partial slots x D
+    float* P1;           // columns side, per slice: partial slots x Dv
+    u64 qB, qH, kB, kH, vB, vH, goB, goH, y0B, y0H, y1B, y1H;  // batch and head strides in bytes
+    u64 sliceScratch;    // floats of scratch per slice (both of P0 and P1)
+    u32 qRow, kRow, vRow, goRow, y0Row, y1Row;  // row strides in bytes
+    u32 heads, slices, M;  // slices = batches x heads
     u32 nSegs, D, Dv, kBytes, vBytes;
     u32 lanes;           // generic form: lanes per lane group (a power of two, 4 .. 64)
     float scale;
@@ -93,10 +105,10 @@ __device__ __forceinline__ float group_dot(const float* a, const float* b, u32 L
     return d;
 }
 
-// EPL fp32 values of a row of `cols` floats, from element l EPL on
+// EPL fp32 values of the row at `row`, from element l EPL on
 template <int EPL>
-__device__ __forceinline__ void load_f32(const float* X, size_t row, u32 cols, u32 l, float* x) {
-    const float4* p = reinterpret_cast<const float4*>(X + row * cols + static_cast<size_t>(l) * EPL);
+__device__ __forceinline__ void load_f32(const char* row, u32 l, float* x) {
+    const float4* p = reinterpret_cast<const float4*>(row) + static_cast<size_t>(l) * (EPL / 4);
 #pragma unroll
     for (int i = 0; i < EPL; i += 4) {
         const float4 v = p[i / 4];
@@ -129,21 +141,37 @@ __device__ __forceinline__ void group_total(float* acc, u32 L, u32 G, u32 l) {
 
 // delta_i = dot(GO[i,:], O[i,:]) in the lane order of g_e: EPL elements per lane, L lanes per row,
 // 64 / L rows per wave, four waves per workgroup
+struct DeltaArgs {
+    const char* GO;  // per slice M rows of Dv floats, goRow bytes apart
+    const char* O;   // the same, oRow bytes apart
+    float* delta;    // slices x M
+    u64 goB, goH, oB, oH;
+    u32 goRow, oRow, heads, slices, M, Dv, L;
+};
+
 template <int EPL>
-__global__ __launch_bounds__(256) void k_attention_bwd_delta(const float* GO, const float* O, float* delta, u32 M,
-                                                             u32 Dv, u32 L) {
+__global__ __launch_bounds__(256) void k_attention_bwd_delta(const DeltaArgs a) {
+    const char *GO = a.GO, *O = a.O;
+    float* delta = a.delta;
+    if (a.slices > 1u) {  // (one slice branches around the base arithmetic, as in the kernels below)
+        const u32 head = blockIdx.y, bat = blockIdx.z;
+        GO += bat * a.goB + head * a.goH;
+        O += bat * a.oB + head * a.oH;
+        delta += (static_cast<size_t>(bat) * a.heads + head) * a.M;
+    }
+    const u32 M = a.M, Dv = a.Dv, L = a.L;
     const u32 lane = threadIdx.x & 63u;
     const u32 G = 64u / L, g = lane / L, l = lane % L;
     const size_t row = (static_cast<size_t>(blockIdx.x) * 4u + (threadIdx.x >> 6)) * G + g;
     const bool live = row < M && l * static_cast<u32>(EPL) < Dv;
-    float a[EPL], b[EPL];
+    float x[EPL], y[EPL];
 #pragma unroll
-    for (int i = 0; i < EPL; ++i) a[i] = b[i] = 0.f;
+    for (int i = 0; i < EPL; ++i) x[i] = y[i] = 0.f;
     if (live) {
-        load_f32<EPL>(GO, row, Dv, l, a);
-        load_f32<EPL>(O, row, Dv, l, b);
+        load_f32<EPL>(GO + row * a.goRow, l, x);
+        load_f32<EPL>(O + row * a.oRow, l, y);
     }
-    const float d = group_dot<EPL>(a, b, L);
+    const float d = group_dot<EPL>(x, y, L);
     if (row < M && l == 0) delta[row] = d;
 }
 
@@ -158,6 +186,23 @@ __global__ __launch_bounds__(ABW_WAVES * 64) void k_attention_bwd_rows(const Bwd
     const u32 segId = blockIdx.x * ABW_WAVES + wave;
     if (segId >= a.nSegs) return;
     const SpmmSeg sg = a.segs[segId];
+    // the slice (head blockIdx.y of batch blockIdx.z): wave-uniform 64-bit bases, scalar registers.
+    // A call of one slice (bsmr_attention_backward) branches around the arithmetic and its argument loads
+    size_t slice = 0;
+    const char *Qs = a.Q, *Ks = a.K, *Vs = a.V, *GOs = a.GO;
+    char *Y0s = a.Y0, *Y1s = a.Y1;
+    if (a.slices > 1u) {
+        const u32 head = blockIdx.y, bat = blockIdx.z;
+        slice = static_cast<size_t>(bat) * a.heads + head;
+        Qs += bat * a.qB + head * a.qH;
+        Ks += bat * a.kB + head * a.kH;
+        Vs += bat * a.vB + head * a.vH;
+        GOs += bat * a.goB + head * a.goH;
+        Y0s += bat * a.y0B + head * a.y0H;
+        Y1s += bat * a.y1B + head * a.y1H;
+    }
+    const float* const lses = a.lse + slice * a.M;
+    const float* const deltas = a.delta + slice * a.M;
     const u32 L = LANES ? static_cast<u32>(LANES) : a.lanes;
     const u32 G = 64u / L;
     const u32 g = lane / L, l = lane % L;
@@ -167,9 +212,9 @@ __global__ __launch_bounds__(ABW_WAVES * 64) void k_attention_bwd_rows(const Bwd
     float q[EPL], go[EPL], acc[EPL];
 #pragma unroll
     for (int i = 0; i < EPL; ++i) q[i] = go[i] = acc[i] = 0.f;
-    if (liveK) E::unpack(*reinterpret_cast<const uint4*>(a.Q + row * a.kBytes + l * 16u), q);
-    if (liveV) load_f32<EPL>(a.GO, row, a.Dv, l, go);
-    const float lse = a.lse[row], dl = a.delta[row];
+    if (liveK) E::unpack(*reinterpret_cast<const uint4*>(Qs + row * a.qRow + l * 16u), q);
+    if (liveV) load_f32<EPL>(GOs + row * a.goRow, l, go);
+    const float lse = lses[row], dl = deltas[row];
 
     auto batch = [&](u32 b0) {
         return b0 + lane < sg.count ? a.idx[static_cast<size_t>(sg.first) + b0 + lane] : 0u;
@@ -203,8 +248,8 @@ __global__ __launch_bounds__(ABW_WAVES * 64) void k_attention_bwd_rows(const Bwd
 #pragma unroll
             for (u32 u = 0; u < ABW_UNROLL; ++u) {
                 const u32 col = __shfl(cj, static_cast<int>((j + u) * G + g));
-                kw[u] = liveK ? row_of(a.K, a.kBytes, col) : zero;
-                vw[u] = liveV ? row_of(a.V, a.vBytes, col) : zero;
+                kw[u] = liveK ? row_of(Ks, a.kRow, col) : zero;
+                vw[u] = liveV ? row_of(Vs, a.vRow, col) : zero;
             }
 #pragma unroll
             for (u32 u = 0; u < ABW_UNROLL; ++u) entry(kw[u], vw[u], true);
@@ -213,14 +258,16 @@ __global__ __launch_bounds__(ABW_WAVES * 64) void k_attention_bwd_rows(const Bwd
             const u32 idx = j * G + g;
             const u32 col = __shfl(cj, static_cast<int>(idx & 63u));
             const bool valid = idx < nb;
-            entry(liveK && valid ? row_of(a.K, a.kBytes, col) : zero, liveV && valid ? row_of(a.V, a.vBytes, col) : zero,
+            entry(liveK && valid ? row_of(Ks, a.kRow, col) : zero, liveV && valid ? row_of(Vs, a.vRow, col) : zero,
                   valid);
         }
         cj = next;
     }
     group_total<EPL>(acc, L, G, l);
     if (g == 0 && liveK) {
-        float* o = sg.part == SPMM_DIRECT ? a.Y0 + row * a.D : a.P0 + static_cast<size_t>(sg.part) * a.D;
+        float* o = sg.part == SPMM_DIRECT
+                       ? reinterpret_cast<float*>(Y0s + row * a.y0Row)
+                       : a.P0 + slice * a.sliceScratch + static_cast<size_t>(sg.part) * a.D;
         store_f32<EPL>(o + static_cast<size_t>(l) * EPL, acc);
     }
 }
@@ -234,6 +281,23 @@ __global__ __launch_bounds__(ABW_WAVES * 64) void k_attention_bwd_cols(const Bwd
     const u32 segId = blockIdx.x * ABW_WAVES + wave;
     if (segId >= a.nSegs) return;
     const SpmmSeg sg = a.segs[segId];
+    // the slice (head blockIdx.y of batch blockIdx.z): wave-uniform 64-bit bases, scalar registers.
+    // A call of one slice (bsmr_attention_backward) branches around the arithmetic and its argument loads
+    size_t slice = 0;
+    const char *Qs = a.Q, *Ks = a.K, *Vs = a.V, *GOs = a.GO;
+    char *Y0s = a.Y0, *Y1s = a.Y1;
+    if (a.slices > 1u) {
+        const u32 head = blockIdx.y, bat = blockIdx.z;
+        slice = static_cast<size_t>(bat) * a.heads + head;
+        Qs += bat * a.qB + head * a.qH;
+        Ks += bat * a.kB + head * a.kH;
+        Vs += bat * a.vB + head * a.vH;
+        GOs += bat * a.goB + head * a.goH;
+        Y0s += bat * a.y0B + head * a.y0H;
+        Y1s += bat * a.y1B + head * a.y1H;
+    }
+    const float* const lses = a.lse + slice * a.M;
+    const float* const deltas = a.delta + slice * a.M;
     const u32 L = LANES ? static_cast<u32>(LANES) : a.lanes;
     const u32 G = 64u / L;
     const u32 g = lane / L, l = lane % L;
@@ -243,8 +307,8 @@ __global__ __launch_bounds__(ABW_WAVES * 64) void k_attention_bwd_cols(const Bwd
     float k[EPL], v[EPL], accK[EPL], accV[EPL];
 #pragma unroll
     for (int i = 0; i < EPL; ++i) k[i] = v[i] = accK[i] = accV[i] = 0.f;
-    if (liveK) E::unpack(*reinterpret_cast<const uint4*>(a.K + colj * a.kBytes + l * 16u), k);
-    if (liveV) E::unpack(*reinterpret_cast<const uint4*>(a.V + colj * a.vBytes + l * 16u), v);
+    if (liveK) E::unpack(*reinterpret_cast<const uint4*>(Ks + colj * a.kRow + l * 16u), k);
+    if (liveV) E::unpack(*reinterpret_cast<const uint4*>(Vs + colj * a.vRow + l * 16u), v);
 
     // a batch's rows with their LSE and delta, one entry per lane; the next batch's are loaded under
     // the current one's gathers
@@ -253,8 +317,8 @@ __global__ __launch_bounds__(ABW_WAVES * 64) void k_attention_bwd_cols(const Bwd
         ml = md = 0.f;
         if (b0 + lane < sg.count) {
             mi = a.idx[static_cast<size_t>(sg.first) + b0 + lane];
-            ml = a.lse[mi];
-            md = a.delta[mi];
+            ml = lses[mi];
+            md = deltas[mi];
         }
     };
     // an entry's gathered operands: the Q chunk as loaded, the lane's GO elements, the row's LSE and delta
@@ -275,8 +339,8 @@ __global__ __launch_bounds__(ABW_WAVES * 64) void k_attention_bwd_cols(const Bwd
 #pragma unroll
         for (int i = 0; i < EPL; ++i) e.go[i] = 0.f;
         if (valid) {
-            if (liveK) e.qw = *reinterpret_cast<const uint4*>(a.Q + static_cast<size_t>(r) * a.kBytes + l * 16u);
-            if (liveV) load_f32<EPL>(a.GO, r, a.Dv, l, e.go);
+            if (liveK) e.qw = *reinterpret_cast<const uint4*>(Qs + static_cast<size_t>(r) * a.qRow + l * 16u);
+            if (liveV) load_f32<EPL>(GOs + static_cast<size_t>(r) * a.goRow, l, e.go);
         }
         return e;
     };
@@ -323,11 +387,13 @@ __global__ __launch_bounds__(ABW_WAVES * 64) void k_attention_bwd_cols(const Bwd
     if (g == 0) {
         const bool direct = sg.part == SPMM_DIRECT;
         if (liveK && a.Y0) {
-            float* o = direct ? a.Y0 + colj * a.D : a.P0 + static_cast<size_t>(sg.part) * a.D;
+            float* o = direct ? reinterpret_cast<float*>(Y0s + colj * a.y0Row)
+                              : a.P0 + slice * a.sliceScratch + static_cast<size_t>(sg.part) * a.D;
             store_f32<EPL>(o + static_cast<size_t>(l) * EPL, accK);
         }
         if (liveV && a.Y1) {
-            float* o = direct ? a.Y1 + colj * a.Dv : a.P1 + static_cast<size_t>(sg.part) * a.Dv;
+            float* o = direct ? reinterpret_cast<float*>(Y1s + colj * a.y1Row)
+                              : a.P1 + slice * a.sliceScratch + static_cast<size_t>(sg.part) * a.Dv;
             store_f32<EPL>(o + static_cast<size_t>(l) * EPL, accV);
         }
     }
@@ -336,9 +402,17 @@ __global__ __launch_bounds__(ABW_WAVES * 64) void k_attention_bwd_cols(const Bwd
 // k_spmm_reduce for up to two outputs that share the split destinations: Y[dst] = the destination's
 // partial rows added in segment order; one thread per four columns of Y0 (K0 columns, or none: Y0
 // null) followed by Y1 (K1 columns, or none)
-__global__ __launch_bounds__(256) void k_attention_bwd_reduce(const SpmmRed* reds, u32 nReds, const float* P0,
-                                                              float* Y0, u32 K0, const float* P1, float* Y1, u32 K1) {
-    const u32 q0 = Y0 ? K0 / 4u : 0u, q1 = Y1 ? K1 / 4u : 0u, q4 = q0 + q1;
+__global__ __launch_bounds__(256) void k_attention_bwd_reduce(const BwdArgs a, const SpmmRed* reds, u32 nReds) {
+    size_t sliceOff = 0;
+    char *Y0s = a.Y0, *Y1s = a.Y1;
+    if (a.slices > 1u) {
+        const u32 head = blockIdx.y, bat = blockIdx.z;
+        sliceOff = (static_cast<size_t>(bat) * a.heads + head) * a.sliceScratch;
+        Y0s += bat * a.y0B + head * a.y0H;
+        Y1s += bat * a.y1B + head * a.y1H;
+    }
+    const u32 K0 = a.D, K1 = a.Dv;
+    const u32 q0 = a.Y0 ? K0 / 4u : 0u, q1 = a.Y1 ? K1 / 4u : 0u, q4 = q0 + q1;
     const size_t t = static_cast<size_t>(blockIdx.x) * 256u + threadIdx.x;
     if (t >= static_cast<size_t>(nReds) * q4) return;
     const SpmmRed r = reds[t / q4];
@@ -346,8 +420,8 @@ __global__ __launch_bounds__(256) void k_attention_bwd_reduce(const SpmmRed* red
     const bool second = q >= q0;
     if (second) q -= q0;
     const u32 K = second ? K1 : K0;
-    const float* P = second ? P1 : P0;
-    float* Y = second ? Y1 : Y0;
+    const float* P = (second ? a.P1 : a.P0) + sliceOff;
+    char* Y = second ? Y1s + static_cast<size_t>(r.dst) * a.y1Row : Y0s + static_cast<size_t>(r.dst) * a.y0Row;
     const float4* p = reinterpret_cast<const float4*>(P + static_cast<size_t>(r.part0) * K) + q;
     float4 s = p[0];
     for (u32 i = 1; i < r.nparts; ++i) {
@@ -357,7 +431,7 @@ __global__ __launch_bounds__(256) void k_attention_bwd_reduce(const SpmmRed* red
         s.z += x.z;
         s.w += x.w;
     }
-    reinterpret_cast<float4*>(Y + static_cast<size_t>(r.dst) * K)[q] = s;
+    reinterpret_cast<float4*>(Y)[q] = s;
 }
 
 using BwdFn = void (*)(const BwdArgs);
@@ -384,15 +458,17 @@ BwdFn pick_cols(u32 rowBytes) {
     }
 }
 
-bool backward_ready(const Plan::AttentionBwdState& S, u32 D, u32 Dv) {
-    return S.built && S.rowScratch.size() >= static_cast<size_t>(S.rowPartials) * D &&
-           S.colScratch.size() >= static_cast<size_t>(S.colPartials) * (static_cast<size_t>(D) + Dv);
+bool backward_ready(const Plan& p, u32 D, u32 Dv, u32 slices) {
+    const Plan::AttentionBwdState& S = p.attention_bwd;
+    // (DevBuf holds a size only with its memory: a failed grow leaves the old buffer and its size)
+    return S.built && S.delta.size() >= attn_sat_mul(slices, p.M) &&
+           S.rowScratch.size() >= attn_sat_mul(slices, S.rowPartials, D) &&
+           S.colScratch.size() >= attn_sat_mul(slices, S.colPartials, static_cast<size_t>(D) + Dv);
 }
 
-// build both sides' lists and delta (once) and size the scratches for (D, Dv); layout_mu held.
-// Synchronous on the plan's stream.
-int build_backward(const Plan& p, u32 D, u32 Dv) {
-    const char* who = "bsmr_plan_prepare_attention_backward";
+// build both sides' lists (once) and size delta and the per-slice scratches for (D, Dv, slices):
+// they grow and never shrink; layout_mu held. Synchronous on the plan's stream.
+int build_backward(const Plan& p, u32 D, u32 Dv, u32 slices, const char* who) {
     Plan::AttentionBwdState& S = p.attention_bwd;
     const hipStream_t s = p.stream;
     if (!S.built) {
@@ -428,7 +504,6 @@ int build_backward(const Plan& p, u32 D, u32 Dv) {
         BSMR_CHECK(S.csegs.upload(C.segs.data(), C.segs.size(), s));
         BSMR_CHECK(S.creds.upload(C.reds.data(), C.reds.size(), s));
         BSMR_CHECK(S.csrc.upload(C.src.data(), C.src.size(), s));
-        BSMR_CHECK(S.delta.alloc(p.M));
         BSMR_HIP(hipStreamSynchronize(s));
         S.rowShared = share;
         if (share) {
@@ -452,10 +527,136 @@ int build_backward(const Plan& p, u32 D, u32 Dv) {
         S.colMax = C.maxList;
         S.built = true;
     }
-    const size_t rowNeed = static_cast<size_t>(S.rowPartials) * D;
-    const size_t colNeed = static_cast<size_t>(S.colPartials) * (static_cast<size_t>(D) + Dv);
-    if (S.rowScratch.size() < rowNeed) BSMR_CHECK(S.rowScratch.alloc(rowNeed));
-    if (S.colScratch.size() < colNeed) BSMR_CHECK(S.colScratch.alloc(colNeed));
+    BSMR_CHECK(S.delta.grow(attn_sat_mul(slices, p.M)));
+    BSMR_CHECK(S.rowScratch.grow(attn_sat_mul(slices, S.rowPartials, D)));
+    BSMR_CHECK(S.colScratch.grow(attn_sat_mul(slices, S.colPartials, static_cast<size_t>(D) + Dv)));
+    return BSMR_OK;
+}
+
+struct BwdOperands {
+    const bsmr_attention_operand *Q, *K, *V, *O, *GO, *GQ, *GK, *GV;  // the last three may be null, not all
+};
+
+// the launches of bsmr_attention_backward and bsmr_attention_backward_heads, arguments already
+// validated: `who` and `prep` name the entry point and its prepare call in errors
+int backward_launch(const char* who, const char* prep, const bsmr_plan* plan, u32 batches, u32 heads,
+                    const BwdOperands& x, const float* dLse, u32 D, u32 Dv, int dtype, float scale, void* stream) {
+    const Plan& p = plan->p;
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    const Plan::AttentionBwdState& S = p.attention_bwd;
+    const u32 slices = batches * heads;  // (both at most 65535)
+    BwdArgs r{}, cs{};
+    const SpmmRed *rreds = nullptr, *creds = nullptr;
+    u32 rowReds = 0, colReds = 0, rowPartials = 0, colPartials = 0;
+    float* colScratch = nullptr;
+    {
+        std::lock_guard<std::mutex> g(p.layout_mu);
+        if (!backward_ready(p, D, Dv, slices)) {
+            const LaunchSite at{s, who, prep, D, dtype};
+            const int st = lazy_build_guard(at);
+            if (st == BSMR_ERR_NOT_PREPARED)  // (the guard's own message names a (K, dtype) layout)
+                set_error(std::string(who) + ": stream is capturing and the backward lists (or their scratch for D = " +
+                          std::to_string(D) + ", Dv = " + std::to_string(Dv) +
+                          (slices > 1 ? ", " + std::to_string(slices) + " slices" : std::string()) +
+                          ") are not built; call " + prep + " first");
+            BSMR_CHECK(st);
+            BSMR_CHECK(build_backward(p, D, Dv, slices, prep));
+        }
+        r.segs = S.row_segs(p.attention);
+        r.nSegs = S.rowSegs;
+        r.P0 = S.rowScratch.data();
+        r.delta = S.delta.data();
+        rreds = S.row_reds(p.attention);
+        rowReds = S.rowReds;
+        rowPartials = S.rowPartials;
+        cs.segs = S.csegs.data();
+        cs.nSegs = S.colSegs;
+        cs.idx = S.csrc.data();
+        creds = S.creds.data();
+        colReds = S.colReds;
+        colPartials = S.colPartials;
+        colScratch = S.colScratch.data();
+    }
+    const u32 esz = dtype == BSMR_F32 ? 4u : 2u;
+    const AttnOpBytes q = attn_op_bytes(x.Q, batches, heads, p.M, esz), k = attn_op_bytes(x.K, batches, heads, p.N, esz),
+                  v = attn_op_bytes(x.V, batches, heads, p.N, esz), o = attn_op_bytes(x.O, batches, heads, p.M, 4u),
+                  go = attn_op_bytes(x.GO, batches, heads, p.M, 4u), gq = attn_op_bytes(x.GQ, batches, heads, p.M, 4u),
+                  gk = attn_op_bytes(x.GK, batches, heads, p.N, 4u), gv = attn_op_bytes(x.GV, batches, heads, p.N, 4u);
+    r.idx = p.colidx.data();
+    r.Q = cs.Q = q.ptr, r.qB = cs.qB = q.batch, r.qH = cs.qH = q.head, r.qRow = cs.qRow = q.row;
+    r.K = cs.K = k.ptr, r.kB = cs.kB = k.batch, r.kH = cs.kH = k.head, r.kRow = cs.kRow = k.row;
+    r.V = cs.V = v.ptr, r.vB = cs.vB = v.batch, r.vH = cs.vH = v.head, r.vRow = cs.vRow = v.row;
+    r.GO = cs.GO = go.ptr, r.goB = cs.goB = go.batch, r.goH = cs.goH = go.head, r.goRow = cs.goRow = go.row;
+    r.lse = cs.lse = dLse;
+    cs.delta = r.delta;
+    r.heads = cs.heads = heads;
+    r.slices = cs.slices = slices;
+    r.M = cs.M = p.M;
+    r.D = cs.D = D;
+    r.Dv = cs.Dv = Dv;
+    r.kBytes = cs.kBytes = D * esz;
+    r.vBytes = cs.vBytes = Dv * esz;
+    r.scale = cs.scale = scale;
+    const u32 rowBytes = std::max(r.kBytes, r.vBytes);
+    r.lanes = cs.lanes = attn_lanes(rowBytes);
+    r.Y0 = gq.ptr, r.y0B = gq.batch, r.y0H = gq.head, r.y0Row = gq.row;
+    r.sliceScratch = static_cast<u64>(rowPartials) * D;
+    cs.Y0 = gk.ptr, cs.y0B = gk.batch, cs.y0H = gk.head, cs.y0Row = gk.row;
+    cs.Y1 = gv.ptr, cs.y1B = gv.batch, cs.y1H = gv.head, cs.y1Row = gv.row;
+    cs.P0 = colScratch;
+    cs.P1 = colScratch ? colScratch + static_cast<size_t>(colPartials) * D : nullptr;
+    cs.sliceScratch = static_cast<u64>(colPartials) * (static_cast<u64>(D) + Dv);
+
+    if (p.M) {
+        const u32 epl = 16u / esz, perBlock = 4u * (64u / r.lanes);
+        const u32 grid = static_cast<u32>((static_cast<size_t>(p.M) + perBlock - 1) / perBlock);
+        DeltaArgs d{};
+        d.GO = go.ptr, d.goB = go.batch, d.goH = go.head, d.goRow = go.row;
+        d.O = o.ptr, d.oB = o.batch, d.oH = o.head, d.oRow = o.row;
+        d.delta = const_cast<float*>(r.delta);
+        d.heads = heads;
+        d.slices = slices;
+        d.M = p.M;
+        d.Dv = Dv;
+        d.L = r.lanes;
+        if (epl == 4)
+            hipLaunchKernelGGL(k_attention_bwd_delta<4>, dim3(grid, heads, batches), dim3(256), 0, s, d);
+        else
+            hipLaunchKernelGGL(k_attention_bwd_delta<8>, dim3(grid, heads, batches), dim3(256), 0, s, d);
+        BSMR_HIP(hipGetLastError());
+    }
+    if (x.GQ) {
+        const BwdFn fn = dtype == BSMR_F32   ? pick_rows<BSMR_F32>(rowBytes)
+                         : dtype == BSMR_F16 ? pick_rows<BSMR_F16>(rowBytes)
+                                             : pick_rows<BSMR_BF16>(rowBytes);
+        if (r.nSegs) {
+            hipLaunchKernelGGL(fn, dim3((r.nSegs + ABW_WAVES - 1) / ABW_WAVES, heads, batches), dim3(ABW_WAVES * 64), 0, s,
+                               r);
+            BSMR_HIP(hipGetLastError());
+        }
+        if (rowReds) {
+            const size_t threads = static_cast<size_t>(rowReds) * (D / 4u);
+            hipLaunchKernelGGL(k_attention_bwd_reduce, dim3(static_cast<u32>((threads + 255) / 256), heads, batches),
+                               dim3(256), 0, s, r, rreds, rowReds);
+            BSMR_HIP(hipGetLastError());
+        }
+    }
+    if (x.GK || x.GV) {
+        const BwdFn fn = dtype == BSMR_F32   ? pick_cols<BSMR_F32>(rowBytes)
+                         : dtype == BSMR_F16 ? pick_cols<BSMR_F16>(rowBytes)
+                                             : pick_cols<BSMR_BF16>(rowBytes);
+        if (cs.nSegs) {
+            hipLaunchKernelGGL(fn, dim3((cs.nSegs + ABW_WAVES - 1) / ABW_WAVES, heads, batches), dim3(ABW_WAVES * 64), 0, s,
+                               cs);
+            BSMR_HIP(hipGetLastError());
+        }
+        if (colReds) {
+            const size_t threads = static_cast<size_t>(colReds) * ((x.GK ? D / 4u : 0u) + (x.GV ? Dv / 4u : 0u));
+            hipLaunchKernelGGL(k_attention_bwd_reduce, dim3(static_cast<u32>((threads + 255) / 256), heads, batches),
+                               dim3(256), 0, s, cs, creds, colReds);
+            BSMR_HIP(hipGetLastError());
+        }
+    }
     return BSMR_OK;
 }
 
@@ -490,100 +691,50 @@ extern "C" int bsmr_attention_backward(const bsmr_plan* plan, const void* dQ, co
     BSMR_CHECK(attn_validate_scale(who, scale, &c));
     BSMR_CHECK(attn_validate_dims(who, D, Dv, dtype));
     const Plan& p = plan->p;
-    const hipStream_t s = static_cast<hipStream_t>(stream);
-    const Plan::AttentionBwdState& S = p.attention_bwd;
-    BwdArgs r{}, cs{};
-    const SpmmRed *rreds = nullptr, *creds = nullptr;
-    u32 rowReds = 0, colReds = 0, colPartials = 0;
-    float* colScratch = nullptr;
-    {
-        std::lock_guard<std::mutex> g(p.layout_mu);
-        if (!backward_ready(S, D, Dv)) {
-            const LaunchSite at{s, who, "bsmr_plan_prepare_attention_backward", D, dtype};
-            const int st = lazy_build_guard(at);
-            if (st == BSMR_ERR_NOT_PREPARED)  // (the guard's own message names a (K, dtype) layout)
-                set_error("bsmr_attention_backward: stream is capturing and the backward lists (or their scratch for D = " +
-                          std::to_string(D) + ", Dv = " + std::to_string(Dv) +
-                          ") are not built; call bsmr_plan_prepare_attention_backward first");
-            BSMR_CHECK(st);
-            BSMR_CHECK(build_backward(p, D, Dv));
-        }
-        r.segs = S.row_segs(p.attention);
-        r.nSegs = S.rowSegs;
-        r.P0 = S.rowScratch.data();
-        r.delta = S.delta.data();
-        rreds = S.row_reds(p.attention);
-        rowReds = S.rowReds;
-        cs.segs = S.csegs.data();
-        cs.nSegs = S.colSegs;
-        cs.idx = S.csrc.data();
-        creds = S.creds.data();
-        colReds = S.colReds;
-        colPartials = S.colPartials;
-        colScratch = S.colScratch.data();
-    }
-    const u32 esz = dtype == BSMR_F32 ? 4u : 2u;
-    r.idx = p.colidx.data();
-    r.Q = cs.Q = static_cast<const char*>(dQ);
-    r.K = cs.K = static_cast<const char*>(dK);
-    r.V = cs.V = static_cast<const char*>(dV);
-    r.GO = cs.GO = dGO;
-    r.lse = cs.lse = dLse;
-    cs.delta = r.delta;
-    r.D = cs.D = D;
-    r.Dv = cs.Dv = Dv;
-    r.kBytes = cs.kBytes = D * esz;
-    r.vBytes = cs.vBytes = Dv * esz;
-    r.scale = cs.scale = scale;
-    const u32 rowBytes = std::max(r.kBytes, r.vBytes);
-    r.lanes = cs.lanes = attn_lanes(rowBytes);
-    r.Y0 = dGQ;
-    cs.Y0 = dGK;
-    cs.Y1 = dGV;
-    cs.P0 = colScratch;
-    cs.P1 = colScratch ? colScratch + static_cast<size_t>(colPartials) * D : nullptr;
+    const bsmr_attention_operand q = attention_dense_operand(dQ, 1, p.M, D), k = attention_dense_operand(dK, 1, p.N, D),
+                                 v = attention_dense_operand(dV, 1, p.N, Dv), o = attention_dense_operand(dO, 1, p.M, Dv),
+                                 go = attention_dense_operand(dGO, 1, p.M, Dv), gq = attention_dense_operand(dGQ, 1, p.M, D),
+                                 gk = attention_dense_operand(dGK, 1, p.N, D), gv = attention_dense_operand(dGV, 1, p.N, Dv);
+    const BwdOperands x{&q, &k, &v, &o, &go, dGQ ? &gq : nullptr, dGK ? &gk : nullptr, dGV ? &gv : nullptr};
+    return backward_launch(who, "bsmr_plan_prepare_attention_backward", plan, 1, 1, x, dLse, D, Dv, dtype, scale, stream);
+}
 
-    if (p.M) {
-        const u32 epl = 16u / esz, perBlock = 4u * (64u / r.lanes);
-        const u32 grid = static_cast<u32>((static_cast<size_t>(p.M) + perBlock - 1) / perBlock);
-        float* delta = const_cast<float*>(r.delta);
-        if (epl == 4)
-            hipLaunchKernelGGL(k_attention_bwd_delta<4>, dim3(grid), dim3(256), 0, s, dGO, dO, delta, p.M, Dv, r.lanes);
-        else
-            hipLaunchKernelGGL(k_attention_bwd_delta<8>, dim3(grid), dim3(256), 0, s, dGO, dO, delta, p.M, Dv, r.lanes);
-        BSMR_HIP(hipGetLastError());
+extern "C" int bsmr_attention_backward_heads(const bsmr_plan* plan, uint32_t batches, uint32_t heads,
+                                             const bsmr_attention_operand* Q, const bsmr_attention_operand* K,
+                                             const bsmr_attention_operand* V, const bsmr_attention_operand* O,
+                                             const bsmr_attention_operand* GO, const float* dLse, uint32_t D, uint32_t Dv,
+                                             int dtype, float scale, const bsmr_attention_operand* GQ,
+                                             const bsmr_attention_operand* GK, const bsmr_attention_operand* GV,
+                                             void* stream) {
+    const char* who = "bsmr_attention_backward_heads";
+    if (!plan) {
+        set_error("bsmr_attention_backward_heads: null plan");
+        return BSMR_ERR_INVALID;
     }
-    if (dGQ) {
-        const BwdFn fn = dtype == BSMR_F32   ? pick_rows<BSMR_F32>(rowBytes)
-                         : dtype == BSMR_F16 ? pick_rows<BSMR_F16>(rowBytes)
-                                             : pick_rows<BSMR_BF16>(rowBytes);
-        if (r.nSegs) {
-            hipLaunchKernelGGL(fn, dim3((r.nSegs + ABW_WAVES - 1) / ABW_WAVES), dim3(ABW_WAVES * 64), 0, s, r);
-            BSMR_HIP(hipGetLastError());
-        }
-        if (rowReds) {
-            const size_t threads = static_cast<size_t>(rowReds) * (D / 4u);
-            hipLaunchKernelGGL(k_attention_bwd_reduce, dim3(static_cast<u32>((threads + 255) / 256)), dim3(256), 0, s, rreds,
-                               rowReds, r.P0, dGQ, D, static_cast<const float*>(nullptr), static_cast<float*>(nullptr), 0u);
-            BSMR_HIP(hipGetLastError());
-        }
+    if (!dLse || (reinterpret_cast<uintptr_t>(dLse) & 3u)) {
+        set_error("bsmr_attention_backward_heads: dLse must be non-null and 4-byte aligned");
+        return BSMR_ERR_INVALID;
     }
-    if (dGK || dGV) {
-        const BwdFn fn = dtype == BSMR_F32   ? pick_cols<BSMR_F32>(rowBytes)
-                         : dtype == BSMR_F16 ? pick_cols<BSMR_F16>(rowBytes)
-                                             : pick_cols<BSMR_BF16>(rowBytes);
-        if (cs.nSegs) {
-            hipLaunchKernelGGL(fn, dim3((cs.nSegs + ABW_WAVES - 1) / ABW_WAVES), dim3(ABW_WAVES * 64), 0, s, cs);
-            BSMR_HIP(hipGetLastError());
-        }
-        if (colReds) {
-            const size_t threads = static_cast<size_t>(colReds) * ((dGK ? D / 4u : 0u) + (dGV ? Dv / 4u : 0u));
-            hipLaunchKernelGGL(k_attention_bwd_reduce, dim3(static_cast<u32>((threads + 255) / 256)), dim3(256), 0, s, creds,
-                               colReds, cs.P0, dGK, D, cs.P1, dGV, Dv);
-            BSMR_HIP(hipGetLastError());
-        }
+    if (!GQ && !GK && !GV) {
+        set_error("bsmr_attention_backward_heads: GQ, GK and GV are all null: nothing to compute");
+        return BSMR_ERR_INVALID;
     }
-    return BSMR_OK;
+    float c;
+    BSMR_CHECK(attn_validate_scale(who, scale, &c));
+    BSMR_CHECK(attn_validate_dims(who, D, Dv, dtype));
+    const Plan& p = plan->p;
+    const u32 esz = dtype == BSMR_F32 ? 4u : 2u;
+    BSMR_CHECK(attn_check_operand(who, "Q", Q, batches, heads, p.M, D, esz, false));
+    BSMR_CHECK(attn_check_operand(who, "K", K, batches, heads, p.N, D, esz, false));
+    BSMR_CHECK(attn_check_operand(who, "V", V, batches, heads, p.N, Dv, esz, false));
+    BSMR_CHECK(attn_check_operand(who, "O", O, batches, heads, p.M, Dv, 4u, false));
+    BSMR_CHECK(attn_check_operand(who, "GO", GO, batches, heads, p.M, Dv, 4u, false));
+    if (GQ) BSMR_CHECK(attn_check_operand(who, "GQ", GQ, batches, heads, p.M, D, 4u, true));
+    if (GK) BSMR_CHECK(attn_check_operand(who, "GK", GK, batches, heads, p.N, D, 4u, true));
+    if (GV) BSMR_CHECK(attn_check_operand(who, "GV", GV, batches, heads, p.N, Dv, 4u, true));
+    const BwdOperands x{Q, K, V, O, GO, GQ, GK, GV};
+    return backward_launch(who, "bsmr_plan_prepare_attention_backward_heads", plan, batches, heads, x, dLse, D, Dv, dtype,
+                           scale, stream);
 }
 
 extern "C" int bsmr_plan_prepare_attention_backward(const bsmr_plan* plan, uint32_t D, uint32_t Dv) {
@@ -593,7 +744,7 @@ extern "C" int bsmr_plan_prepare_attention_backward(const bsmr_plan* plan, uint3
     }
     BSMR_CHECK(attn_validate_prepare_dims("bsmr_plan_prepare_attention_backward", D, Dv));
     std::lock_guard<std::mutex> g(plan->p.layout_mu);
-    return build_backward(plan->p, D, Dv);
+    return build_backward(plan->p, D, Dv, 1, "bsmr_plan_prepare_attention_backward");
 }
 
 extern "C" int bsmr_plan_attention_backward_prepared(const bsmr_plan* plan, uint32_t D, uint32_t Dv) {
@@ -603,7 +754,32 @@ extern "C" int bsmr_plan_attention_backward_prepared(const bsmr_plan* plan, uint
     }
     if (attn_validate_prepare_dims("bsmr_plan_attention_backward_prepared", D, Dv) != BSMR_OK) return 0;
     std::lock_guard<std::mutex> g(plan->p.layout_mu);
-    return backward_ready(plan->p.attention_bwd, D, Dv) ? 1 : 0;
+    return backward_ready(plan->p, D, Dv, 1) ? 1 : 0;
+}
+
+extern "C" int bsmr_plan_prepare_attention_backward_heads(const bsmr_plan* plan, uint32_t D, uint32_t Dv,
+                                                          uint32_t slices) {
+    const char* who = "bsmr_plan_prepare_attention_backward_heads";
+    if (!plan) {
+        set_error("bsmr_plan_prepare_attention_backward_heads: null plan");
+        return BSMR_ERR_INVALID;
+    }
+    BSMR_CHECK(attn_check_slices(who, slices));
+    BSMR_CHECK(attn_validate_prepare_dims(who, D, Dv));
+    std::lock_guard<std::mutex> g(plan->p.layout_mu);
+    return build_backward(plan->p, D, Dv, slices, who);
+}
+
+extern "C" int bsmr_plan_attention_backward_heads_prepared(const bsmr_plan* plan, uint32_t D, uint32_t Dv,
+                                                           uint32_t slices) {
+    const char* who = "bsmr_plan_attention_backward_heads_prepared";
+    if (!plan) {
+        set_error("bsmr_plan_attention_backward_heads_prepared: null plan");
+        return 0;
+    }
+    if (attn_check_slices(who, slices) != BSMR_OK || attn_validate_prepare_dims(who, D, Dv) != BSMR_OK) return 0;
+    std::lock_guard<std::mutex> g(plan->p.layout_mu);
+    return backward_ready(plan->p, D, Dv, slices) ? 1 : 0;
 }
 
 extern "C" int bsmr_plan_attention_backward_stats(const bsmr_plan* plan, bsmr_attention_backward_stats* out) {

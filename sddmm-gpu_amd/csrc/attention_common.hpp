@@ -27,6 +27,35 @@ inline u32 attn_lanes(u32 rowBytes) {
     while (lanes * 16u < rowBytes) lanes <<= 1;
     return lanes;
 }
+// one operand of a heads call against the layout rules (attention_layout.hpp, the only place they
+// are written); else BSMR_ERR_INVALID with the message set: "<who>: <name>: <rule>"
+int attn_check_operand(const char* who, const char* name, const bsmr_attention_operand* op, u32 batches, u32 heads,
+                       u32 rows, u32 width, u32 esz, bool is_output);
+// a b c saturating at the largest size_t: a scratch size that does not fit is never "ready" and
+// never allocated
+inline size_t attn_sat_mul(size_t a, size_t b, size_t c = 1) {
+    size_t ab, abc;
+    if (__builtin_mul_overflow(a, b, &ab) || __builtin_mul_overflow(ab, c, &abc)) return static_cast<size_t>(-1);
+    return abc;
+}
+// slices = batches x heads of a prepare / prepared call: 1 .. the product of the two limits
+int attn_check_slices(const char* who, u32 slices);
+// one strided operand as the kernels take it: strides in bytes; a dimension of extent 1 is never
+// stepped over, so its stride is dropped; a null operand (an output not asked for) is all zeros
+struct AttnOpBytes {
+    char* ptr;
+    u64 batch, head;
+    u32 row;
+};
+inline AttnOpBytes attn_op_bytes(const bsmr_attention_operand* op, u32 batches, u32 heads, u32 rows, u32 esz) {
+    AttnOpBytes o{};
+    if (!op) return o;
+    o.ptr = static_cast<char*>(op->ptr);
+    o.batch = batches > 1 ? op->batch * esz : 0;
+    o.head = heads > 1 ? op->head * esz : 0;
+    o.row = rows > 1 ? static_cast<u32>(op->row * esz) : 0;
+    return o;
+}
 // the forward's segment chunk (ATTN_CHUNK of attention.hip)
 u32 attn_forward_chunk();
 // spmm_lists at side 1 over the plan's CSR in the plan's reordered row order, `chunk` entries per

@@ -58,11 +58,33 @@ struct DevBuf {
         p = nullptr;
         n = 0;
     }
+    // (n is set only once the memory exists: after a failed allocation the buffer is empty, never
+    // a null pointer with a size)
     int alloc(size_t count) {
         release();
-        n = count;
         if (count == 0) return BSMR_OK;
         BSMR_HIP(hipMalloc(&p, count * sizeof(T)));
+        n = count;
+        return BSMR_OK;
+    }
+    // at least `count` elements, contents undefined: a buffer that already holds them is kept, and
+    // so is the old buffer when the larger allocation fails (it grows and never shrinks)
+    int grow(size_t count) {
+        if (count <= n) return BSMR_OK;
+        if (count > static_cast<size_t>(-1) / sizeof(T)) {
+            ::bsmr::set_error("device buffer of " + std::to_string(count) + " elements does not fit in 64 bits of bytes");
+            return BSMR_ERR_HIP;
+        }
+        T* q = nullptr;
+        const hipError_t e = hipMalloc(&q, count * sizeof(T));
+        if (e != hipSuccess) {
+            (void)hipGetLastError();  // the refusal is reported here; it must not fail the next launch's check
+            ::bsmr::set_error("hipMalloc of " + std::to_string(count * sizeof(T)) + " bytes: " + hipGetErrorString(e));
+            return BSMR_ERR_HIP;
+        }
+        if (p) (void)hipFree(p);
+        p = q;
+        n = count;
         return BSMR_OK;
     }
     int upload(const T* h, size_t count, hipStream_t s) {

@@ -272,13 +272,15 @@ struct Plan {
 
     // fused sparse attention (attention.hip; bsmr_attention): the rows' segments of at most
     // ATTN_CHUNK entries (spmm_lists at side 1: src is colidx and vpos the identity, so neither is
-    // kept), the split rows, and their partials: partials x scratchDv accumulator rows followed
-    // by partials (m, l) pairs. Built on first use or by bsmr_plan_prepare_attention, under
+    // kept), the split rows, and their partials: slices x partials x Dv accumulator rows followed by
+    // slices x partials (m, l) pairs (bsmr_attention_heads; one slice for bsmr_attention); the
+    // scratch holds what the largest slices x (Dv + 2) so far needs and never shrinks. Built on first use or by
+    // bsmr_plan_prepare_attention / bsmr_plan_prepare_attention_heads, under
     // layout_mu; its own lists, which bsmr_plan_prepare_spmm never touches, and which depend on S
     // and the row order only, so build_columns keeps them
     struct AttentionState {
         bool built = false;
-        u32 nSegs = 0, nReds = 0, splitRows = 0, partials = 0, maxRow = 0, scratchDv = 0;
+        u32 nSegs = 0, nReds = 0, splitRows = 0, partials = 0, maxRow = 0;
         DevBuf<SpmmSeg> segs;
         DevBuf<SpmmRed> reds;
         DevBuf<float> scratch;
@@ -289,8 +291,9 @@ struct Plan {
     // segments (the forward's lists: AttentionState's buffers when they were built before this
     // state and the two chunks agree, rowShared, else lists of its own built the same way), the
     // columns' segments with the row of every entry (spmm_lists at side 2; no vpos: there are no
-    // nnz values), the M floats of delta = dot(GO, O), and the partial rows of the split
-    // destinations: rowPartials x D floats, and colPartials x D followed by colPartials x Dv. Built
+    // nnz values), and per slice (bsmr_attention_backward_heads; one for bsmr_attention_backward)
+    // the M floats of delta = dot(GO, O) and the partial rows of the split destinations:
+    // rowPartials x D floats, and colPartials x D followed by colPartials x Dv. Built
     // on first use or by bsmr_plan_prepare_attention_backward, under layout_mu; neither
     // bsmr_plan_prepare_spmm nor build_columns touches it, and it never writes AttentionState
     struct AttentionBwdState {

@@ -39,6 +39,30 @@ Per case (the C2 nips-like and C3 cop20k-like stand-in patterns, fp32, D = Dv = 
     backward_peak_bytes: torch's peak over forward + backward through bsmr.autograd (attention,
     attention_fused, attention_fused(backward="fused")) above what was allocated before;
     attention_backward_stats carries the plan-owned scratch of the fused backward.
+
+    python3 tools/attention_bench.py --heads H --batches B [--dtype f32|f16] [--layout bmhd|bhmd]
+                                     [--baseline-only] [--package DIR]
+
+With --heads / --batches (Z = B H slices of the case's pattern) the tool times,
+by the same protocol (graphs of `steps`, median of `rounds` alternating replays), forward and fused
+backward:
+  * heads_fwd / heads_bwd: one Plan.attention_heads / Plan.attention_backward_heads call on views of
+    (B, M, H D) projections (--layout bmhd: head stride D, row stride H D) or on dense (B, H, M, D);
+  * seq_fwd / seq_bwd: Z sequential single-slice Plan.attention / Plan.attention_backward calls on
+    contiguous per-slice copies (the copies are made before, not timed);
+  * heads_over_seq, floor_us (every slice's dense operands and outputs once, the K and V rows some
+    entry references, LSE and delta, and the index arrays once: 4 nnz forward, 8 nnz backward) and
+    the plan-owned scratch per slice in bytes.
+--order-probe adds four split forms of the backward that tell the launch order from the grid (each
+is the row side, GQ alone, and the column side, GK and GV alone; delta runs in both):
+  seq_split_slice_major   per slice the row-side call, then the column-side call (a slice's operands
+                          are reused between its kernels, as in seq_bwd);
+  seq_split_kernel_major  the row-side calls of all Z slices, then the column-side calls of all Z;
+  heads_split             one row-side heads call, then one column-side heads call;
+  heads_rows / heads_cols those two calls alone, beside seq_rows / seq_cols (Z single-slice calls each).
+--baseline-only times the sequential form alone and needs no heads entry point; with --package DIR
+(a directory holding a bsmr package with its built library, e.g. a checkout of another commit) that
+form can be taken from another build in the same session, for A/B runs.
 """
 import argparse
 import json
@@ -58,7 +82,16 @@ def main():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--d", type=int, default=64)
+    ap.add_argument("--heads", type=int, default=0)
+    ap.add_argument("--batches", type=int, default=0)
+    ap.add_argument("--dtype", default="f32", choices=["f32", "f16"])
+    ap.add_argument("--layout", default="bmhd", choices=["bmhd", "bhmd"])
+    ap.add_argument("--baseline-only", action="store_true")
+    ap.add_argument("--order-probe", action="store_true")
+    ap.add_argument("--package", default=None)
     args = ap.parse_args()
+    if args.package:
+        sys.path.insert(0, os.path.abspath(args.package))
     import numpy as np
     import torch
 
@@ -107,6 +140,9 @@ def main():
 
     D = args.d
     scale = D ** -0.5
+    if args.heads or args.batches:
+        heads_bench(args, torch, np, dev, graph_of, alternate)
+        return
     for case in args.cases.split(","):
         if case == "C2":
             M, N, rp, ci = synth.nips_like()
@@ -253,6 +289,107 @@ def main():
                 "launches": launches, "backward_peak_bytes": peaks, "nnz_bytes": 4 * nnz, "attention_backward_stats": bst,
                 "fused_bwd_over_composed_bwd": round(graph_us["fused_bwd"] / graph_us["composed_bwd"], 3),
                 "fused_bwd_over_recompute_bwd": round(graph_us["fused_bwd"] / graph_us["recompute_bwd"], 3), "check": check, "torch": torch.__version__}
+        print(json.dumps(line), flush=True)
+
+
+def heads_bench(args, torch, np, dev, graph_of, alternate):
+    """The --heads / --batches mode (module docstring)."""
+    import bsmr
+    from bsmr import F16, F32, Plan, make_data, synth
+
+    B, H, D = max(args.batches, 1), max(args.heads, 1), args.d
+    Z = B * H
+    scale = D ** -0.5
+    tdt, dtype, esz = (torch.float32, F32, 4) if args.dtype == "f32" else (torch.float16, F16, 2)
+    p = lambda t: t.data_ptr()  # noqa: E731
+    for case in args.cases.split(","):
+        if case not in ("C2", "C3"):
+            raise SystemExit(f"unknown case {case}")
+        M, N, rp, ci = synth.nips_like() if case == "C2" else synth.cop20k_like()
+        nnz = len(ci)
+        plan = Plan(M, N, rp, ci, alpha=0.3, delta=0.3)
+        plan.prepare_attention(D, D)
+        plan.prepare_attention_backward(D, D)
+
+        def data(rows):
+            t = (torch.from_numpy(make_data(B * rows * H * D)).to(dev) - 1.0).reshape(B, rows, H, D)
+            if args.layout == "bhmd":
+                t = t.permute(0, 2, 1, 3).contiguous().permute(0, 2, 1, 3)
+            return t.to(tdt)
+
+        z = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)  # noqa: E731
+        like = lambda t: torch.zeros_like(t, dtype=torch.float32)  # noqa: E731
+        # (B, H, rows, D) views of the chosen layout
+        bQ, bK, bV, bdO = data(M), data(N), data(N), data(M).float()
+        Q, K, V, dO = (t.permute(0, 2, 1, 3) for t in (bQ, bK, bV, bdO))
+        O, gQ, gK, gV = (like(t).permute(0, 2, 1, 3) for t in (bQ, bQ, bK, bV))
+        L = z(B, H, M)
+        slices = [(b, h) for b in range(B) for h in range(H)]
+        sQ, sK, sV, sdO = ([t[b, h].contiguous() for b, h in slices] for t in (Q, K, V, dO))
+        sO, sgQ, sgK, sgV = ([z(r, D) for _ in slices] for r in (M, M, N, N))
+        sL = [z(M) for _ in slices]
+
+        def seq_fwd(s):
+            for i in range(Z):
+                plan.attention(p(sQ[i]), p(sK[i]), p(sV[i]), D, D, p(sO[i]), p(sL[i]), scale, stream=s, dtype=dtype)
+
+        def seq_bwd(s):
+            for i in range(Z):
+                plan.attention_backward(p(sQ[i]), p(sK[i]), p(sV[i]), p(sO[i]), p(sdO[i]), p(sL[i]), D, D, p(sgQ[i]),
+                                        p(sgK[i]), p(sgV[i]), scale, stream=s, dtype=dtype)
+
+        ours = {"seq_fwd": seq_fwd, "seq_bwd": seq_bwd}
+        if not args.baseline_only:
+            plan.prepare_attention_heads(D, D, Z)
+            plan.prepare_attention_backward_heads(D, D, Z)
+            ours["heads_fwd"] = lambda s: plan.attention_heads(B, H, Q, K, V, D, D, O, p(L), scale, stream=s, dtype=dtype)
+            ours["heads_bwd"] = lambda s: plan.attention_backward_heads(B, H, Q, K, V, O, dO, p(L), D, D, gQ, gK, gV, scale,
+                                                                        stream=s, dtype=dtype)
+        if args.order_probe and not args.baseline_only:
+            def seq_side(i, s, rows):
+                plan.attention_backward(p(sQ[i]), p(sK[i]), p(sV[i]), p(sO[i]), p(sdO[i]), p(sL[i]), D, D,
+                                        p(sgQ[i]) if rows else 0, 0 if rows else p(sgK[i]), 0 if rows else p(sgV[i]), scale,
+                                        stream=s, dtype=dtype)
+
+            def heads_side(s, rows):
+                plan.attention_backward_heads(B, H, Q, K, V, O, dO, p(L), D, D, gQ if rows else None, None if rows else gK,
+                                              None if rows else gV, scale, stream=s, dtype=dtype)
+
+            def slice_major(s):
+                for i in range(Z):
+                    seq_side(i, s, True)
+                    seq_side(i, s, False)
+
+            def kernel_major(s, sides=(True, False)):
+                for rows in sides:
+                    for i in range(Z):
+                        seq_side(i, s, rows)
+
+            ours.update({"seq_split_slice_major_bwd": slice_major, "seq_split_kernel_major_bwd": kernel_major,
+                         "heads_split_bwd": lambda s: (heads_side(s, True), heads_side(s, False)),
+                         "seq_rows_bwd": lambda s: kernel_major(s, (True,)), "seq_cols_bwd": lambda s: kernel_major(s, (False,)),
+                         "heads_rows_bwd": lambda s: heads_side(s, True), "heads_cols_bwd": lambda s: heads_side(s, False)})
+        # forward first: the backward reads O and LSE
+        graphs = {k: graph_of(ours[k]) for k in sorted(ours, key=lambda k: k.endswith("bwd"))}
+        graph_us = alternate({k: g.replay for k, g in graphs.items()})
+        used = len(np.unique(ci))
+        inputs = esz * D * (M + 2 * used)
+        floor = {"fwd": (Z * (inputs + 4 * D * M + 4 * M) + 4 * nnz) / HBM_BYTES_PER_S * 1e6,
+                 "bwd": (Z * (inputs + 8 * D * M + 4 * D * (M + 2 * N) + 12 * M) + 8 * nnz) / HBM_BYTES_PER_S * 1e6}
+        line = {"case": case, "mode": "heads", "M": M, "N": N, "nnz": nnz, "D": D, "dtype": args.dtype, "batches": B,
+                "heads": H, "slices": Z, "layout": args.layout, "steps": args.steps, "rounds": args.rounds,
+                "package": os.path.dirname(os.path.abspath(bsmr.__file__)), "graph_us": graph_us,
+                "floor_us": {k: round(v, 3) for k, v in floor.items()}}
+        if not args.baseline_only:
+            same = all(torch.equal(O[b, h], sO[i]) and torch.equal(gK[b, h], sgK[i]) for i, (b, h) in enumerate(slices))
+            ast, bst = plan.attention_stats(), plan.attention_backward_stats()
+            line.update({"heads_over_seq": {d: round(graph_us[f"heads_{d}"] / graph_us[f"seq_{d}"], 3) for d in ("fwd", "bwd")},
+                         "floor_fraction": {d: round(floor[d] / graph_us[f"heads_{d}"], 3) for d in ("fwd", "bwd")},
+                         "slices_bit_equal": same,
+                         "scratch_bytes_per_slice": {"fwd": 4 * ast["partials"] * (D + 2), "bwd_delta": bst["delta_bytes"] // Z,
+                                                     "bwd_rows": bst["row_scratch_bytes"] // Z,
+                                                     "bwd_cols": bst["col_scratch_bytes"] // Z},
+                         "attention_stats": ast})
         print(json.dumps(line), flush=True)
 
 

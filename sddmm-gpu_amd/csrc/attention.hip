@@ -38,6 +38,7 @@
 #include "attention_layout.hpp"
 #include "plan.hpp"
 #include "row_elems.hpp"
+#include "seg_walk.hpp"  // exp2_hw
 #include "spmm_schedule.hpp"
 
 namespace bsmr {
@@ -71,8 +72,6 @@ struct AttnArgs {
     float c, scale;     // scale log2(e), rounded once from double; scale
 };
 
-// v_exp_f32: 2^x to 1 ulp, 0 for -inf (and for results under 2^-126)
-__device__ __forceinline__ float exp2_hw(float x) { return __builtin_amdgcn_exp2f(x); }
 // softmax.hip's conventions: a maximum of -inf (every score -inf, or no entry) shifts by 0, and
 // a sum of 0 gives weights 0
 __device__ __forceinline__ float shift_of(float m) { return m == -INFINITY ? 0.f : m; }

@@ -40,6 +40,7 @@
 #include "attention_layout.hpp"
 #include "plan.hpp"
 #include "row_elems.hpp"
+#include "seg_walk.hpp"
 #include "spmm_schedule.hpp"
 
 namespace bsmr {
@@ -61,27 +62,22 @@ constexpr float LOG2E_F = 1.44269504088896340736f;
 struct BwdArgs {
     const SpmmSeg* segs;
     const u32* idx;      // rows side: the plan's colidx; columns side: the row of every entry
-    const char* Q;       // per slice M rows of kBytes, qRow bytes apart
-    const char* K;       // per slice N rows of kBytes, kRow bytes apart
-    const char* V;       // per slice N rows of vBytes, vRow bytes apart
-    const char* GO;      // per slice M rows of Dv floats, goRow bytes apart
+    AttnOpBytes Q;       // per slice M rows of kBytes
+    AttnOpBytes K;       // per slice N rows of kBytes
+    AttnOpBytes V;       // per slice N rows of vBytes
+    AttnOpBytes GO;      // per slice M rows of Dv floats
     const float* lse;    // slices x M
     const float* delta;  // slices x M
-    char* Y0;            // rows side: GQ (rows of D floats); columns side: GK (rows of D floats) or null
-    char* Y1;            // columns side: GV (rows of Dv floats) or null
+    AttnOpBytes Y0;      // rows side: GQ (rows of D floats); columns side: GK (rows of D floats) or null
+    AttnOpBytes Y1;      // columns side: GV (rows of Dv floats) or null
     float* P0;           // per slice: partial slots x D
     float* P1;           // columns side, per slice: partial slots x Dv
-    u64 qB, qH, kB, kH, vB, vH, goB, goH, y0B, y0H, y1B, y1H;  // batch and head strides in bytes
     u64 sliceScratch;    // floats of scratch per slice (both of P0 and P1)
-    u32 qRow, kRow, vRow, goRow, y0Row, y1Row;  // row strides in bytes
     u32 heads, slices, M;  // slices = batches x heads
     u32 nSegs, D, Dv, kBytes, vBytes;
     u32 lanes;           // generic form: lanes per lane group (a power of two, 4 .. 64)
     float scale;
 };
-
-// v_exp_f32: 2^x to 1 ulp, 0 for -inf (and for results under 2^-126)
-__device__ __forceinline__ float exp2_hw(float x) { return __builtin_amdgcn_exp2f(x); }
 
 // the entry's weight and score gradient, every product and difference rounded on its own: the
 // exponent is (p scale - LSE) log2e, so a score that equals LSE bit for bit has weight exactly 1
@@ -96,37 +92,9 @@ __device__ __forceinline__ void weight_of(float p, float g, float lse, float dl,
     dp = wg * scale;
 }
 
-template <int EPL>
-__device__ __forceinline__ float group_dot(const float* a, const float* b, u32 L) {
-    float d = 0.f;
-#pragma unroll
-    for (int i = 0; i < EPL; ++i) d = __builtin_fmaf(a[i], b[i], d);
-    for (u32 off = L >> 1; off >= 1u; off >>= 1) d += __shfl_xor(d, static_cast<int>(off));
-    return d;
-}
-
-// EPL fp32 values of the row at `row`, from element l EPL on
-template <int EPL>
-__device__ __forceinline__ void load_f32(const char* row, u32 l, float* x) {
-    const float4* p = reinterpret_cast<const float4*>(row) + static_cast<size_t>(l) * (EPL / 4);
-#pragma unroll
-    for (int i = 0; i < EPL; i += 4) {
-        const float4 v = p[i / 4];
-        x[i] = v.x;
-        x[i + 1] = v.y;
-        x[i + 2] = v.z;
-        x[i + 3] = v.w;
-    }
-}
-
-template <int EPL>
-__device__ __forceinline__ void store_f32(float* o, const float* x) {
-#pragma unroll
-    for (int i = 0; i < EPL; i += 4) *reinterpret_cast<float4*>(o + i) = make_float4(x[i], x[i + 1], x[i + 2], x[i + 3]);
-}
-
 // the lane groups in group order (group g held entries g, g + G, ... of the segment): every lane
-// ends with the same totals
+// ends with the same totals. (The forward's inline form of this lacks the unroll pragma below and
+// stays apart: it keeps a 64-VGPR cap, and was neither built nor measured with it.)
 template <int EPL>
 __device__ __forceinline__ void group_total(float* acc, u32 L, u32 G, u32 l) {
     if (G <= 1u) return;
@@ -142,38 +110,59 @@ __device__ __forceinline__ void group_total(float* acc, u32 L, u32 G, u32 l) {
 // delta_i = dot(GO[i,:], O[i,:]) in the lane order of g_e: EPL elements per lane, L lanes per row,
 // 64 / L rows per wave, four waves per workgroup
 struct DeltaArgs {
-    const char* GO;  // per slice M rows of Dv floats, goRow bytes apart
-    const char* O;   // the same, oRow bytes apart
+    AttnOpBytes GO;  // per slice M rows of Dv floats
+    AttnOpBytes O;   // the same
     float* delta;    // slices x M
-    u64 goB, goH, oB, oH;
-    u32 goRow, oRow, heads, slices, M, Dv, L;
+    u32 heads, slices, M, Dv, L;
 };
 
 template <int EPL>
 __global__ __launch_bounds__(256) void k_attention_bwd_delta(const DeltaArgs a) {
-    const char *GO = a.GO, *O = a.O;
+    const char *GO = a.GO.ptr, *O = a.O.ptr;
     float* delta = a.delta;
     if (a.slices > 1u) {  // (one slice branches around the base arithmetic, as in the kernels below)
         const u32 head = blockIdx.y, bat = blockIdx.z;
-        GO += bat * a.goB + head * a.goH;
-        O += bat * a.oB + head * a.oH;
+        GO = attn_slice_base(a.GO, bat, head);
+        O = attn_slice_base(a.O, bat, head);
         delta += (static_cast<size_t>(bat) * a.heads + head) * a.M;
     }
-    const u32 M = a.M, Dv = a.Dv, L = a.L;
-    const u32 lane = threadIdx.x & 63u;
-    const u32 G = 64u / L, g = lane / L, l = lane % L;
-    const size_t row = (static_cast<size_t>(blockIdx.x) * 4u + (threadIdx.x >> 6)) * G + g;
+    const u32 M = a.M, Dv = a.Dv;
+    const LaneGroups lg(a.L, threadIdx.x & 63u);
+    const u32 L = lg.L, l = lg.l;
+    const size_t row = (static_cast<size_t>(blockIdx.x) * 4u + (threadIdx.x >> 6)) * lg.G + lg.g;
     const bool live = row < M && l * static_cast<u32>(EPL) < Dv;
     float x[EPL], y[EPL];
 #pragma unroll
     for (int i = 0; i < EPL; ++i) x[i] = y[i] = 0.f;
     if (live) {
-        load_f32<EPL>(GO + row * a.goRow, l, x);
-        load_f32<EPL>(O + row * a.oRow, l, y);
+        load_f32<EPL>(GO + row * a.GO.row, l, x);
+        load_f32<EPL>(O + row * a.O.row, l, y);
     }
     const float d = group_dot<EPL>(x, y, L);
     if (row < M && l == 0) delta[row] = d;
 }
+
+// what the segment kernels and the reduce start from: the slice (head blockIdx.y of batch
+// blockIdx.z) and its operands' bases, wave-uniform and 64-bit, in scalar registers. A call of one
+// slice (bsmr_attention_backward) branches around the arithmetic and its argument loads
+struct BwdSlice {
+    size_t slice = 0;
+    const char *Q, *K, *V, *GO;
+    char *Y0, *Y1;
+    __device__ __forceinline__ explicit BwdSlice(const BwdArgs& a)
+        : Q(a.Q.ptr), K(a.K.ptr), V(a.V.ptr), GO(a.GO.ptr), Y0(a.Y0.ptr), Y1(a.Y1.ptr) {
+        if (a.slices > 1u) {
+            const u32 head = blockIdx.y, bat = blockIdx.z;
+            slice = static_cast<size_t>(bat) * a.heads + head;
+            Q = attn_slice_base(a.Q, bat, head);
+            K = attn_slice_base(a.K, bat, head);
+            V = attn_slice_base(a.V, bat, head);
+            GO = attn_slice_base(a.GO, bat, head);
+            Y0 = attn_slice_base(a.Y0, bat, head);
+            Y1 = attn_slice_base(a.Y1, bat, head);
+        }
+    }
+};
 
 // LANES: lanes per lane group, compile-time (8, 16, 32, 64: rows of 128 .. 1024 bytes) or 0 =
 // a.lanes (every other row size). Lanes past the K row or the V row idle for that operand
@@ -186,48 +175,40 @@ __global__ __launch_bounds__(ABW_WAVES * 64) void k_attention_bwd_rows(const Bwd
     const u32 segId = blockIdx.x * ABW_WAVES + wave;
     if (segId >= a.nSegs) return;
     const SpmmSeg sg = a.segs[segId];
-    // the slice (head blockIdx.y of batch blockIdx.z): wave-uniform 64-bit bases, scalar registers.
-    // A call of one slice (bsmr_attention_backward) branches around the arithmetic and its argument loads
-    size_t slice = 0;
-    const char *Qs = a.Q, *Ks = a.K, *Vs = a.V, *GOs = a.GO;
-    char *Y0s = a.Y0, *Y1s = a.Y1;
-    if (a.slices > 1u) {
-        const u32 head = blockIdx.y, bat = blockIdx.z;
-        slice = static_cast<size_t>(bat) * a.heads + head;
-        Qs += bat * a.qB + head * a.qH;
-        Ks += bat * a.kB + head * a.kH;
-        Vs += bat * a.vB + head * a.vH;
-        GOs += bat * a.goB + head * a.goH;
-        Y0s += bat * a.y0B + head * a.y0H;
-        Y1s += bat * a.y1B + head * a.y1H;
-    }
-    const float* const lses = a.lse + slice * a.M;
-    const float* const deltas = a.delta + slice * a.M;
-    const u32 L = LANES ? static_cast<u32>(LANES) : a.lanes;
-    const u32 G = 64u / L;
-    const u32 g = lane / L, l = lane % L;
+    const BwdSlice s(a);
+    const LaneGroups lg(LANES ? static_cast<u32>(LANES) : a.lanes, lane);
+    const u32 L = lg.L, G = lg.G, g = lg.g, l = lg.l;
     const bool liveK = l * 16u < a.kBytes, liveV = l * 16u < a.vBytes;
     const size_t row = sg.dst;
 
     float q[EPL], go[EPL], acc[EPL];
 #pragma unroll
     for (int i = 0; i < EPL; ++i) q[i] = go[i] = acc[i] = 0.f;
-    if (liveK) E::unpack(*reinterpret_cast<const uint4*>(Qs + row * a.qRow + l * 16u), q);
-    if (liveV) load_f32<EPL>(GOs + row * a.goRow, l, go);
-    const float lse = lses[row], dl = deltas[row];
+    if (liveK) E::unpack(*reinterpret_cast<const uint4*>(s.Q + row * a.Q.row + l * 16u), q);
+    if (liveV) load_f32<EPL>(s.GO + row * a.GO.row, l, go);
+    const float lse = a.lse[s.slice * a.M + row], dl = a.delta[s.slice * a.M + row];
 
+    // an entry's K and V chunks as loaded (zeros for a lane past the row or an idle tail entry; a
+    // zero by name in `cond ? *ptr : zero` would be selected by address, from scratch)
+    struct Ent {
+        uint4 kw, vw;
+    };
     auto batch = [&](u32 b0) {
         return b0 + lane < sg.count ? a.idx[static_cast<size_t>(sg.first) + b0 + lane] : 0u;
     };
-    auto row_of = [&](const char* X, u32 rowBytes, u32 col) {
-        return *reinterpret_cast<const uint4*>(X + static_cast<size_t>(col) * rowBytes + l * 16u);
+    auto row_of = [&](const char* X, u32 rowBytes, size_t col) {
+        return *reinterpret_cast<const uint4*>(X + col * rowBytes + l * 16u);
     };
-    const uint4 zero = make_uint4(0, 0, 0, 0);
+    auto fetch = [&](u32 cj, u32 idx, bool valid, Ent& e) {
+        const u32 col = __shfl(cj, static_cast<int>(idx & 63u));
+        e.kw = liveK && valid ? row_of(s.K, a.K.row, col) : make_uint4(0, 0, 0, 0);
+        e.vw = liveV && valid ? row_of(s.V, a.V.row, col) : make_uint4(0, 0, 0, 0);
+    };
     // every lane takes part in the shuffles; only the loads and the FMAs into acc are predicated
-    auto entry = [&](const uint4& kw, const uint4& vw, bool valid) {
+    auto use = [&](const Ent& e, u32, bool valid) {
         float kx[EPL], vx[EPL];
-        E::unpack(kw, kx);
-        E::unpack(vw, vx);
+        E::unpack(e.kw, kx);
+        E::unpack(e.vw, vx);
         const float p = group_dot<EPL>(q, kx, L);
         const float gg = group_dot<EPL>(go, vx, L);
         float w, dp;
@@ -237,41 +218,18 @@ __global__ __launch_bounds__(ABW_WAVES * 64) void k_attention_bwd_rows(const Bwd
             for (int i = 0; i < EPL; ++i) acc[i] = __builtin_fmaf(dp, kx[i], acc[i]);
         }
     };
-    u32 cj = batch(0);
-    for (u32 b0 = 0; b0 < sg.count; b0 += 64u) {
-        const u32 next = b0 + 64u < sg.count ? batch(b0 + 64u) : 0u;
-        const u32 nb = min(64u, sg.count - b0);
-        const u32 full = nb / G;  // steps in which every lane group has an entry
-        u32 j = 0;
-        for (; j + ABW_UNROLL <= full; j += ABW_UNROLL) {
-            uint4 kw[ABW_UNROLL], vw[ABW_UNROLL];
-#pragma unroll
-            for (u32 u = 0; u < ABW_UNROLL; ++u) {
-                const u32 col = __shfl(cj, static_cast<int>((j + u) * G + g));
-                kw[u] = liveK ? row_of(Ks, a.kRow, col) : zero;
-                vw[u] = liveV ? row_of(Vs, a.vRow, col) : zero;
-            }
-#pragma unroll
-            for (u32 u = 0; u < ABW_UNROLL; ++u) entry(kw[u], vw[u], true);
-        }
-        for (; j * G < nb; ++j) {  // the remaining steps; the last may be partly filled
-            const u32 idx = j * G + g;
-            const u32 col = __shfl(cj, static_cast<int>(idx & 63u));
-            const bool valid = idx < nb;
-            entry(liveK && valid ? row_of(Ks, a.kRow, col) : zero, liveV && valid ? row_of(Vs, a.vRow, col) : zero,
-                  valid);
-        }
-        cj = next;
-    }
+    seg_walk<ABW_UNROLL, Ent>(sg.count, G, g, batch(0), batch, fetch, use);
     group_total<EPL>(acc, L, G, l);
     if (g == 0 && liveK) {
         float* o = sg.part == SPMM_DIRECT
-                       ? reinterpret_cast<float*>(Y0s + row * a.y0Row)
-                       : a.P0 + slice * a.sliceScratch + static_cast<size_t>(sg.part) * a.D;
+                       ? reinterpret_cast<float*>(s.Y0 + row * a.Y0.row)
+                       : a.P0 + s.slice * a.sliceScratch + static_cast<size_t>(sg.part) * a.D;
         store_f32<EPL>(o + static_cast<size_t>(l) * EPL, acc);
     }
 }
 
+// The columns side keeps its hand-written copy of the loop that the rows side takes from seg_walk:
+// on the walker it measured 1.1 % slower at fp32 D = 64 on C3
 template <int DT, int LANES>
 __global__ __launch_bounds__(ABW_WAVES * 64) void k_attention_bwd_cols(const BwdArgs a) {
     using E = Elem<DT>;
@@ -281,34 +239,22 @@ __global__ __launch_bounds__(ABW_WAVES * 64) void k_attention_bwd_cols(const Bwd
     const u32 segId = blockIdx.x * ABW_WAVES + wave;
     if (segId >= a.nSegs) return;
     const SpmmSeg sg = a.segs[segId];
-    // the slice (head blockIdx.y of batch blockIdx.z): wave-uniform 64-bit bases, scalar registers.
-    // A call of one slice (bsmr_attention_backward) branches around the arithmetic and its argument loads
-    size_t slice = 0;
-    const char *Qs = a.Q, *Ks = a.K, *Vs = a.V, *GOs = a.GO;
-    char *Y0s = a.Y0, *Y1s = a.Y1;
-    if (a.slices > 1u) {
-        const u32 head = blockIdx.y, bat = blockIdx.z;
-        slice = static_cast<size_t>(bat) * a.heads + head;
-        Qs += bat * a.qB + head * a.qH;
-        Ks += bat * a.kB + head * a.kH;
-        Vs += bat * a.vB + head * a.vH;
-        GOs += bat * a.goB + head * a.goH;
-        Y0s += bat * a.y0B + head * a.y0H;
-        Y1s += bat * a.y1B + head * a.y1H;
-    }
+    const BwdSlice s(a);
+    const size_t slice = s.slice;
+    const char *Qs = s.Q, *Ks = s.K, *Vs = s.V, *GOs = s.GO;
+    char *Y0s = s.Y0, *Y1s = s.Y1;
     const float* const lses = a.lse + slice * a.M;
     const float* const deltas = a.delta + slice * a.M;
-    const u32 L = LANES ? static_cast<u32>(LANES) : a.lanes;
-    const u32 G = 64u / L;
-    const u32 g = lane / L, l = lane % L;
+    const LaneGroups lg(LANES ? static_cast<u32>(LANES) : a.lanes, lane);
+    const u32 L = lg.L, G = lg.G, g = lg.g, l = lg.l;
     const bool liveK = l * 16u < a.kBytes, liveV = l * 16u < a.vBytes;
     const size_t colj = sg.dst;
 
     float k[EPL], v[EPL], accK[EPL], accV[EPL];
 #pragma unroll
     for (int i = 0; i < EPL; ++i) k[i] = v[i] = accK[i] = accV[i] = 0.f;
-    if (liveK) E::unpack(*reinterpret_cast<const uint4*>(Ks + colj * a.kRow + l * 16u), k);
-    if (liveV) E::unpack(*reinterpret_cast<const uint4*>(Vs + colj * a.vRow + l * 16u), v);
+    if (liveK) E::unpack(*reinterpret_cast<const uint4*>(Ks + colj * a.K.row + l * 16u), k);
+    if (liveV) E::unpack(*reinterpret_cast<const uint4*>(Vs + colj * a.V.row + l * 16u), v);
 
     // a batch's rows with their LSE and delta, one entry per lane; the next batch's are loaded under
     // the current one's gathers
@@ -339,8 +285,8 @@ __global__ __launch_bounds__(ABW_WAVES * 64) void k_attention_bwd_cols(const Bwd
 #pragma unroll
         for (int i = 0; i < EPL; ++i) e.go[i] = 0.f;
         if (valid) {
-            if (liveK) e.qw = *reinterpret_cast<const uint4*>(Qs + static_cast<size_t>(r) * a.qRow + l * 16u);
-            if (liveV) load_f32<EPL>(GOs + static_cast<size_t>(r) * a.goRow, l, e.go);
+            if (liveK) e.qw = *reinterpret_cast<const uint4*>(Qs + static_cast<size_t>(r) * a.Q.row + l * 16u);
+            if (liveV) load_f32<EPL>(GOs + static_cast<size_t>(r) * a.GO.row, l, e.go);
         }
         return e;
     };
@@ -386,13 +332,13 @@ __global__ __launch_bounds__(ABW_WAVES * 64) void k_attention_bwd_cols(const Bwd
     group_total<EPL>(accV, L, G, l);
     if (g == 0) {
         const bool direct = sg.part == SPMM_DIRECT;
-        if (liveK && a.Y0) {
-            float* o = direct ? reinterpret_cast<float*>(Y0s + colj * a.y0Row)
+        if (liveK && a.Y0.ptr) {
+            float* o = direct ? reinterpret_cast<float*>(Y0s + colj * a.Y0.row)
                               : a.P0 + slice * a.sliceScratch + static_cast<size_t>(sg.part) * a.D;
             store_f32<EPL>(o + static_cast<size_t>(l) * EPL, accK);
         }
-        if (liveV && a.Y1) {
-            float* o = direct ? reinterpret_cast<float*>(Y1s + colj * a.y1Row)
+        if (liveV && a.Y1.ptr) {
+            float* o = direct ? reinterpret_cast<float*>(Y1s + colj * a.Y1.row)
                               : a.P1 + slice * a.sliceScratch + static_cast<size_t>(sg.part) * a.Dv;
             store_f32<EPL>(o + static_cast<size_t>(l) * EPL, accV);
         }
@@ -403,16 +349,10 @@ __global__ __launch_bounds__(ABW_WAVES * 64) void k_attention_bwd_cols(const Bwd
 // partial rows added in segment order; one thread per four columns of Y0 (K0 columns, or none: Y0
 // null) followed by Y1 (K1 columns, or none)
 __global__ __launch_bounds__(256) void k_attention_bwd_reduce(const BwdArgs a, const SpmmRed* reds, u32 nReds) {
-    size_t sliceOff = 0;
-    char *Y0s = a.Y0, *Y1s = a.Y1;
-    if (a.slices > 1u) {
-        const u32 head = blockIdx.y, bat = blockIdx.z;
-        sliceOff = (static_cast<size_t>(bat) * a.heads + head) * a.sliceScratch;
-        Y0s += bat * a.y0B + head * a.y0H;
-        Y1s += bat * a.y1B + head * a.y1H;
-    }
+    const BwdSlice sl(a);
+    const size_t sliceOff = sl.slice * a.sliceScratch;
     const u32 K0 = a.D, K1 = a.Dv;
-    const u32 q0 = a.Y0 ? K0 / 4u : 0u, q1 = a.Y1 ? K1 / 4u : 0u, q4 = q0 + q1;
+    const u32 q0 = a.Y0.ptr ? K0 / 4u : 0u, q1 = a.Y1.ptr ? K1 / 4u : 0u, q4 = q0 + q1;
     const size_t t = static_cast<size_t>(blockIdx.x) * 256u + threadIdx.x;
     if (t >= static_cast<size_t>(nReds) * q4) return;
     const SpmmRed r = reds[t / q4];
@@ -421,7 +361,7 @@ __global__ __launch_bounds__(256) void k_attention_bwd_reduce(const BwdArgs a, c
     if (second) q -= q0;
     const u32 K = second ? K1 : K0;
     const float* P = (second ? a.P1 : a.P0) + sliceOff;
-    char* Y = second ? Y1s + static_cast<size_t>(r.dst) * a.y1Row : Y0s + static_cast<size_t>(r.dst) * a.y0Row;
+    char* Y = second ? sl.Y1 + static_cast<size_t>(r.dst) * a.Y1.row : sl.Y0 + static_cast<size_t>(r.dst) * a.Y0.row;
     const float4* p = reinterpret_cast<const float4*>(P + static_cast<size_t>(r.part0) * K) + q;
     float4 s = p[0];
     for (u32 i = 1; i < r.nparts; ++i) {
@@ -436,26 +376,22 @@ __global__ __launch_bounds__(256) void k_attention_bwd_reduce(const BwdArgs a, c
 
 using BwdFn = void (*)(const BwdArgs);
 
+// the segment kernel of a side (rows or columns) for rows of rowBytes: the fixed sizes or the generic form
 template <int DT>
-BwdFn pick_rows(u32 rowBytes) {
+BwdFn pick_side(bool rows, u32 rowBytes) {
     switch (rowBytes) {
-        case 128: return k_attention_bwd_rows<DT, 8>;
-        case 256: return k_attention_bwd_rows<DT, 16>;
-        case 512: return k_attention_bwd_rows<DT, 32>;
-        case 1024: return k_attention_bwd_rows<DT, 64>;
-        default: return k_attention_bwd_rows<DT, 0>;
+        case 128: return rows ? k_attention_bwd_rows<DT, 8> : k_attention_bwd_cols<DT, 8>;
+        case 256: return rows ? k_attention_bwd_rows<DT, 16> : k_attention_bwd_cols<DT, 16>;
+        case 512: return rows ? k_attention_bwd_rows<DT, 32> : k_attention_bwd_cols<DT, 32>;
+        case 1024: return rows ? k_attention_bwd_rows<DT, 64> : k_attention_bwd_cols<DT, 64>;
+        default: return rows ? k_attention_bwd_rows<DT, 0> : k_attention_bwd_cols<DT, 0>;
     }
 }
 
-template <int DT>
-BwdFn pick_cols(u32 rowBytes) {
-    switch (rowBytes) {
-        case 128: return k_attention_bwd_cols<DT, 8>;
-        case 256: return k_attention_bwd_cols<DT, 16>;
-        case 512: return k_attention_bwd_cols<DT, 32>;
-        case 1024: return k_attention_bwd_cols<DT, 64>;
-        default: return k_attention_bwd_cols<DT, 0>;
-    }
+BwdFn pick_side(int dtype, bool rows, u32 rowBytes) {
+    return dtype == BSMR_F32   ? pick_side<BSMR_F32>(rows, rowBytes)
+           : dtype == BSMR_F16 ? pick_side<BSMR_F16>(rows, rowBytes)
+                               : pick_side<BSMR_BF16>(rows, rowBytes);
 }
 
 bool backward_ready(const Plan& p, u32 D, u32 Dv, u32 slices) {
@@ -578,15 +514,11 @@ int backward_launch(const char* who, const char* prep, const bsmr_plan* plan, u3
         colScratch = S.colScratch.data();
     }
     const u32 esz = dtype == BSMR_F32 ? 4u : 2u;
-    const AttnOpBytes q = attn_op_bytes(x.Q, batches, heads, p.M, esz), k = attn_op_bytes(x.K, batches, heads, p.N, esz),
-                  v = attn_op_bytes(x.V, batches, heads, p.N, esz), o = attn_op_bytes(x.O, batches, heads, p.M, 4u),
-                  go = attn_op_bytes(x.GO, batches, heads, p.M, 4u), gq = attn_op_bytes(x.GQ, batches, heads, p.M, 4u),
-                  gk = attn_op_bytes(x.GK, batches, heads, p.N, 4u), gv = attn_op_bytes(x.GV, batches, heads, p.N, 4u);
     r.idx = p.colidx.data();
-    r.Q = cs.Q = q.ptr, r.qB = cs.qB = q.batch, r.qH = cs.qH = q.head, r.qRow = cs.qRow = q.row;
-    r.K = cs.K = k.ptr, r.kB = cs.kB = k.batch, r.kH = cs.kH = k.head, r.kRow = cs.kRow = k.row;
-    r.V = cs.V = v.ptr, r.vB = cs.vB = v.batch, r.vH = cs.vH = v.head, r.vRow = cs.vRow = v.row;
-    r.GO = cs.GO = go.ptr, r.goB = cs.goB = go.batch, r.goH = cs.goH = go.head, r.goRow = cs.goRow = go.row;
+    r.Q = cs.Q = attn_op_bytes(x.Q, batches, heads, p.M, esz);
+    r.K = cs.K = attn_op_bytes(x.K, batches, heads, p.N, esz);
+    r.V = cs.V = attn_op_bytes(x.V, batches, heads, p.N, esz);
+    r.GO = cs.GO = attn_op_bytes(x.GO, batches, heads, p.M, 4u);
     r.lse = cs.lse = dLse;
     cs.delta = r.delta;
     r.heads = cs.heads = heads;
@@ -599,10 +531,10 @@ int backward_launch(const char* who, const char* prep, const bsmr_plan* plan, u3
     r.scale = cs.scale = scale;
     const u32 rowBytes = std::max(r.kBytes, r.vBytes);
     r.lanes = cs.lanes = attn_lanes(rowBytes);
-    r.Y0 = gq.ptr, r.y0B = gq.batch, r.y0H = gq.head, r.y0Row = gq.row;
+    r.Y0 = attn_op_bytes(x.GQ, batches, heads, p.M, 4u);
     r.sliceScratch = static_cast<u64>(rowPartials) * D;
-    cs.Y0 = gk.ptr, cs.y0B = gk.batch, cs.y0H = gk.head, cs.y0Row = gk.row;
-    cs.Y1 = gv.ptr, cs.y1B = gv.batch, cs.y1H = gv.head, cs.y1Row = gv.row;
+    cs.Y0 = attn_op_bytes(x.GK, batches, heads, p.N, 4u);
+    cs.Y1 = attn_op_bytes(x.GV, batches, heads, p.N, 4u);
     cs.P0 = colScratch;
     cs.P1 = colScratch ? colScratch + static_cast<size_t>(colPartials) * D : nullptr;
     cs.sliceScratch = static_cast<u64>(colPartials) * (static_cast<u64>(D) + Dv);
@@ -611,8 +543,8 @@ int backward_launch(const char* who, const char* prep, const bsmr_plan* plan, u3
         const u32 epl = 16u / esz, perBlock = 4u * (64u / r.lanes);
         const u32 grid = static_cast<u32>((static_cast<size_t>(p.M) + perBlock - 1) / perBlock);
         DeltaArgs d{};
-        d.GO = go.ptr, d.goB = go.batch, d.goH = go.head, d.goRow = go.row;
-        d.O = o.ptr, d.oB = o.batch, d.oH = o.head, d.oRow = o.row;
+        d.GO = r.GO;
+        d.O = attn_op_bytes(x.O, batches, heads, p.M, 4u);
         d.delta = const_cast<float*>(r.delta);
         d.heads = heads;
         d.slices = slices;
@@ -626,9 +558,7 @@ int backward_launch(const char* who, const char* prep, const bsmr_plan* plan, u3
         BSMR_HIP(hipGetLastError());
     }
     if (x.GQ) {
-        const BwdFn fn = dtype == BSMR_F32   ? pick_rows<BSMR_F32>(rowBytes)
-                         : dtype == BSMR_F16 ? pick_rows<BSMR_F16>(rowBytes)
-                                             : pick_rows<BSMR_BF16>(rowBytes);
+        const BwdFn fn = pick_side(dtype, true, rowBytes);
         if (r.nSegs) {
             hipLaunchKernelGGL(fn, dim3((r.nSegs + ABW_WAVES - 1) / ABW_WAVES, heads, batches), dim3(ABW_WAVES * 64), 0, s,
                                r);
@@ -642,9 +572,7 @@ int backward_launch(const char* who, const char* prep, const bsmr_plan* plan, u3
         }
     }
     if (x.GK || x.GV) {
-        const BwdFn fn = dtype == BSMR_F32   ? pick_cols<BSMR_F32>(rowBytes)
-                         : dtype == BSMR_F16 ? pick_cols<BSMR_F16>(rowBytes)
-                                             : pick_cols<BSMR_BF16>(rowBytes);
+        const BwdFn fn = pick_side(dtype, false, rowBytes);
         if (cs.nSegs) {
             hipLaunchKernelGGL(fn, dim3((cs.nSegs + ABW_WAVES - 1) / ABW_WAVES, heads, batches), dim3(ABW_WAVES * 64), 0, s,
                                cs);

@@ -1,6 +1,7 @@
 // attention_common.hpp — what the fused attention forward (attention.hip) and backward
-// (attention_bwd.hip) share on the host: the argument rules and the rows' segment lists. One copy,
-// defined in attention.hip, so that the two entry points cannot drift apart.
+// (attention_bwd.hip) share on the host: the argument rules and the rows' segment lists (one copy,
+// defined in attention.hip, so that the two entry points cannot drift apart). Also the operand
+// record that the backward's kernels and launches are written with.
 #pragma once
 
 #include <string>
@@ -55,6 +56,10 @@ inline AttnOpBytes attn_op_bytes(const bsmr_attention_operand* op, u32 batches, 
     o.head = heads > 1 ? op->head * esz : 0;
     o.row = rows > 1 ? static_cast<u32>(op->row * esz) : 0;
     return o;
+}
+// the operand's base in slice (bat, head): wave-uniform, 64-bit, scalar registers
+__device__ __forceinline__ char* attn_slice_base(const AttnOpBytes& op, u32 bat, u32 head) {
+    return op.ptr + bat * op.batch + head * op.head;
 }
 // the forward's segment chunk (ATTN_CHUNK of attention.hip)
 u32 attn_forward_chunk();

@@ -204,7 +204,7 @@ std::vector<u32> apportion(const std::vector<double>& cost, u32 q, double cap = 
 }
 
 // Static piece order of one row-block item (piece_balance). The kernel deals phase ph's
-// pieces [ph NG, (ph + 1) NG) to row-groups gr, reversed in odd phases (sddmm.hip: piece
+// pieces [ph NG, (ph + 1) NG) to row-groups gr, reversed in odd phases (rb_kernel.hpp: piece
 // ph NG + (ph odd ? NG - 1 - gr : gr)); a wave's 64 / G row-groups run a phase in lockstep, so a
 // wave pays per phase its longest piece plus one gather (w entry-steps, the item cost model's
 // piece weight). With the pieces longest first in position order, the waves that also run the
@@ -695,7 +695,7 @@ void build_pieces(const RbScheduleIn& in, RbScheduleOut& out) {
     // (balance_pieces; items with kept MFMA tiles keep the longest-first order, whose shortest
     // pieces sit with the tile waves)
     if (!out.dyn && kn.piece_balance == 1) {
-        const u32 G = rowBytes >= 2048 ? 16 : rowBytes >= 1024 ? 8 : 4;  // sddmm.hip RowGeom
+        const u32 G = rowBytes >= 2048 ? 16 : rowBytes >= 1024 ? 8 : 4;  // rb_kernel.hpp RowGeom
         par_for(items.size(), [&](unsigned, size_t i0, size_t i1) {
             for (size_t i = i0; i < i1; ++i)
                 if (items[i].y == items[i].z) balance_pieces(ipc[i], NT, G, kn.piece_weight);

@@ -36,7 +36,7 @@ Bound: |P - ref| <= min(2 K, 8 sqrt K) 2^-24 S + 1e-6 scale.
   error / bound ratio (DESIGN.md §11.1 records them).
 
 CASES: one entry per kernel instantiation the dispatch can reach (csrc/launch_select.cpp
-choose_launch, rb_form; csrc/sddmm.hip pick_kernel / pick_k, pick_rb, launch_rb;
+choose_launch, rb_form; csrc/sddmm.hip pick_kernel / pick_k, launch_rb; csrc/rb_kernel.hpp pick_rb;
 csrc/sddmm_half.hip launch_half, launch_ptile; csrc/sddmm_dense.hip launch_dense), on the smallest
 pattern of the suite that takes it, with the plan options that select the path, the Plan.stats()
 evidence that it ran and the library's own account of the launch (check_stats):

@@ -5,7 +5,8 @@ tests/test_store_ref_cpu.py checks this module).
 
 A staged row-block layout (csrc/plan.hpp RowBlockLayout::outLds != 0) keeps each item's results
 in LDS slots, slot t = the item's t-th entry by CSR position, and writes them to P at the end of
-the item. csrc/sddmm.hip has these forms of that pass:
+the item. csrc/rb_kernel.hpp has these forms of that pass (the store passes of
+k_sddmm_rb and of the pair's rb_item, store_sorted):
 
   R  run table (outRuns): the slots cut into runs of up to 64 consecutive positions, descriptor
      {position, slot | length << 16}; lane l of wave w holds run w + NW l; a wave stores its runs

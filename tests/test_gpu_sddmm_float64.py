@@ -21,9 +21,9 @@ import pytest
 
 import bsmr
 from bsmr import Plan
-from gpu_util import nan_output, path_evidence, sddmm_once, to_device, torch_cuda
+from gpu_util import nan_output, path_evidence, plan_launch, rb_store, sddmm_once, to_device, torch_cuda
 from sddmm_cases import (BY_NAME, CASES, ONE_PER_KIND, PANEL_CASES, assert_bound, assert_exact, pattern,
-                         plan_kwargs, reference)
+                         plan_kwargs, rb_slot, reference)
 from spmm_cases import entry_rows
 
 pytestmark = pytest.mark.gpu
@@ -46,6 +46,52 @@ def test_case_matches_float64(name):
     A, B, ref, S = reference(case.pattern, case.K, case.dtype, "signed")
     assert_bound(sddmm_once(plan, A, B, case.K, nnz, case.dtype), ref, S, case.K, name, case.kind)
     assert not path_evidence(case, plan)
+
+
+def _trace_words(plan):
+    """The timeline of the plan's last traced launch (debug export bsmr_debug_trace, not in the
+    header): 4 u64 per wave {start, mid, end, XCC id << 60 | tile end}."""
+    import ctypes as C
+    L = bsmr.lib()
+    L.bsmr_debug_trace.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
+    n = C.c_uint64()
+    assert L.bsmr_debug_trace(plan.h, None, C.byref(n)) == 0
+    buf = np.zeros(n.value, np.uint64)
+    assert L.bsmr_debug_trace(plan.h, buf.ctypes.data, C.byref(n)) == 0
+    return buf
+
+
+@pytest.mark.parametrize("name", ["rb_K256_bf16", "rb_staged_K128_f32"])
+def test_full_form_timeline(name):
+    """diag = 32 (the tools' timeline) on a case that keeps MFMA tiles and on a staged fp32 one: the
+    launch is the full single-item form, P is still right, and the trace holds 4 words per wave of
+    every item slot: 0 < start <= mid <= end for the waves of a real item, zeros (the launch clears
+    the buffer, Plan::prepare_trace, and a padding item returns at once) for a padding one."""
+    base = BY_NAME[name]
+    case = base._replace(tuning=dict(base.tuning, diag=32))
+    K, dtype, nnz = case.K, case.dtype, len(pattern(case.pattern)[3])
+    plan = _plan(case)
+    A, B, ref, _ = reference(case.pattern, K, dtype, "grid")
+    assert_exact(sddmm_once(plan, A, B, K, nnz, dtype), ref, name + " traced grid")
+    A, B, ref, S = reference(case.pattern, K, dtype, "signed")
+    assert_bound(sddmm_once(plan, A, B, K, nnz, dtype), ref, S, K, name + " traced", case.kind + "/trace")
+    assert not path_evidence(case, plan)
+    launch = plan_launch(plan, K, dtype)
+    assert launch["kind"] == "rowblock" and not launch["lite"] and not launch["pairs"], launch
+    st, slot = plan.stats(), rb_slot(K, dtype)
+    if name == "rb_K256_bf16":
+        assert st["rb_tiles"][slot] > 0
+    else:
+        assert rb_store(plan, K, dtype, raw=False)["outLds"] > 0
+    nw = launch["NT"] // 64
+    words = _trace_words(plan)
+    assert len(words) == 4 * st["rb_items"][slot] * nw
+    t = words.reshape(-1, nw, 4)
+    real = rb_store(plan, K, dtype, raw=False)["real"]
+    assert len(real) == len(t) and real.any()
+    t0, tm, t1 = (t[real][:, :, i] for i in range(3))
+    assert (t0 > 0).all() and (t0 <= tm).all() and (tm <= t1).all()
+    assert not t[~real].any()
 
 
 @pytest.mark.parametrize("name", ONE_PER_KIND)

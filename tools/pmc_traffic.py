@@ -17,7 +17,8 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-KERNEL_SOURCES = ["sddmm-gpu_amd/csrc/sddmm.hip", "sddmm-gpu_amd/csrc/sddmm_half.hip",
+KERNEL_SOURCES = ["sddmm-gpu_amd/csrc/sddmm.hip", "sddmm-gpu_amd/csrc/rb_kernel.hpp",
+                  "sddmm-gpu_amd/csrc/sddmm_device.hpp", "sddmm-gpu_amd/csrc/sddmm_half.hip",
                   "sddmm-gpu_amd/csrc/sddmm_dense.hip", "sddmm-gpu_amd/csrc/plan.hip",
                   "sddmm-gpu_amd/csrc/plan.hpp"]
 

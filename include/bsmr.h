@@ -53,7 +53,10 @@ extern "C" {
                               (fused sparse attention backward); bsmr_attention_heads,
                               bsmr_attention_backward_heads, their four prepare / prepared calls
                               and bsmr_attention_layout_check (batch and heads, strided operands:
-                              new declarations only) */
+                              new declarations only); bsmr_attention_panels, its heads form, their
+                              prepare / prepared / stats / limits calls and
+                              bsmr_attention_panel_lists (the panel MFMA forward: new declarations
+                              only) */
 
 typedef enum {
     BSMR_OK = 0,
@@ -740,6 +743,86 @@ int bsmr_plan_attention_backward_heads_prepared(const bsmr_plan* plan, uint32_t 
  * elements of `elem_bytes` bytes; BSMR_OK or BSMR_ERR_INVALID with bsmr_last_error naming the rule. */
 int bsmr_attention_layout_check(const bsmr_attention_operand* op, uint32_t batches, uint32_t heads,
                                 uint32_t rows, uint32_t width, uint32_t elem_bytes, int is_output);
+
+/* --------------------- fused sparse attention forward on matrix instructions, per panel ---- */
+/* The same O and LSE as bsmr_attention, for fp16 / bf16 operands, computed per 16-row panel of the
+ * plan's reordered rows on v_mfma_f32_16x16x32_{f16,bf16}: a K or V row that
+ * several rows of a panel reference is loaded once for the panel, not once per entry. It pays where
+ * the rows of a panel share columns (block, banded and clustered masks; fill_permille of
+ * bsmr_attention_panels_stats says how much); bsmr_attention stays the path for scattered
+ * patterns, and nothing chooses between the two but the caller.
+ * dtype is BSMR_F16 or BSMR_BF16 and D and Dv are each one of 32, 64, 128, 256; anything else
+ * (BSMR_F32 too) gives BSMR_ERR_UNSUPPORTED. Every other argument rule, status code, the
+ * untouched outputs on error, the capture rule (BSMR_ERR_NOT_PREPARED on a capturing stream until
+ * bsmr_plan_prepare_attention_panels ran), at most two launches per call and the plan-owned scratch
+ * that grows and never shrinks are bsmr_attention's.
+ * Arithmetic: scores in fp32 from the MFMA; per row an online softmax over steps of 32 columns of
+ * the panel's ascending column union (the maximum so far m, t = 2^((p - m) c) in fp32, l summed in
+ * fp32 from the unrounded t); the weights are rounded to the operand dtype for the second MFMA and
+ * the accumulator is rescaled once per step. A panel of more than item_steps steps is split into
+ * items whose partials are each rescaled once against the row's maximum and added in item order.
+ * No atomics: results are bitwise reproducible and equal between a lazily built and a prepared plan.
+ * Conventions: bsmr_attention's (every element of O and LSE written; an empty or all -inf row gives
+ * O = 0 and LSE = -inf; a NaN or +inf score makes exactly that row NaN), with one difference: a
+ * NaN / inf in a V row reaches every row of the panels whose column union holds that column (0 x NaN
+ * inside the MFMA is NaN), and no row of any other panel. */
+int bsmr_attention_panels(const bsmr_plan* plan, const void* dQ, const void* dK, const void* dV, uint32_t D,
+                          uint32_t Dv, int dtype, float scale, float* dO, float* dLse, void* stream);
+/* bsmr_attention_panels over batches x heads slices of one pattern in one call: operands, layout
+ * rules and LSE as bsmr_attention_heads; every slice equals the single-slice call bit for bit. */
+int bsmr_attention_panels_heads(const bsmr_plan* plan, uint32_t batches, uint32_t heads,
+                                const bsmr_attention_operand* Q, const bsmr_attention_operand* K,
+                                const bsmr_attention_operand* V, uint32_t D, uint32_t Dv, int dtype, float scale,
+                                const bsmr_attention_operand* O, float* dLse, void* stream);
+/* Build now what the first launch at Dv (and that many slices) would build: the panel lists and the
+ * scratch of the split panels. Synchronous and idempotent; the lists are this path's own (no other
+ * prepare call touches them) and bsmr_plan_recolumn keeps them. */
+int bsmr_plan_prepare_attention_panels(const bsmr_plan* plan, uint32_t D, uint32_t Dv);
+int bsmr_plan_prepare_attention_panels_heads(const bsmr_plan* plan, uint32_t D, uint32_t Dv, uint32_t slices);
+/* 1 when a launch would make no allocation, copy or synchronisation, else 0; no device call. */
+int bsmr_plan_attention_panels_prepared(const bsmr_plan* plan, uint32_t D, uint32_t Dv);
+int bsmr_plan_attention_panels_heads_prepared(const bsmr_plan* plan, uint32_t D, uint32_t Dv, uint32_t slices);
+typedef struct {
+    uint32_t panels;        /* 16-row panels of the launch order (the last may be short) */
+    uint32_t items;         /* waves of the launch (every panel has at least one) */
+    uint32_t steps;         /* 32-column steps over all panels */
+    uint32_t split_panels;  /* panels of more than item_steps steps */
+    uint32_t partials;      /* their items = partial slots (16 rows each) of scratch */
+    uint32_t fill_permille; /* 1000 nnz / (16 x 32 x steps): 1000 is a pattern of full 16 x 32 blocks */
+    uint32_t step_cols;     /* the library's constants (always filled) */
+    uint32_t item_steps;
+} bsmr_attention_panels_stats;
+/* Counts are zeros while the lists are not built. */
+int bsmr_plan_attention_panels_stats(const bsmr_plan* plan, bsmr_attention_panels_stats* out);
+/* The constants of the panel path without a plan (either pointer may be NULL). */
+void bsmr_attention_panels_limits(uint32_t* step_cols, uint32_t* item_steps);
+/* Host-only form of the panel lists (no plan, no device) from a CSR and a row order of `norder`
+ * rows. rows (M entries): the launch order, `order` followed by the rows it does not name in
+ * ascending index; a panel is 16 consecutive rows of it. A step holds 32 ascending columns of its
+ * panel's column union and 16 row masks (bit c of mask r: panel row r stores cols[c]); the padding
+ * slots of a panel's last step repeat cols[0] of that step with bit 0 in every mask. An item is
+ * steps step0 .. step0 + nsteps - 1 (nsteps <= item_steps) of the panel that starts at rows[row0];
+ * part is 0xFFFFFFFF for a panel's only item, else its partial slot; a panel without entries is
+ * one item of 0 steps. A red names a split panel's consecutive slots part0 .. part0 + nparts - 1.
+ * Any of rows / steps / items / reds may be NULL (not written); the three counts are always set, so
+ * a first call sizes the buffers. BSMR_ERR_INVALID for a null rowptr or count pointer, a rowptr
+ * not non-decreasing from 0, a column >= N or stored twice in a row, an order entry >= M or twice;
+ * BSMR_ERR_UNSUPPORTED for more than 2^32 - 1 steps, items or partials. The rows that `order` does
+ * not name are computed from their entries like any other (a plan's unnamed rows are its empty
+ * ones and so give O = 0, LSE = -inf, but the lists do not rely on that). */
+typedef struct {
+    uint32_t cols[32], masks[16];
+} bsmr_attention_panel_step;
+typedef struct {
+    uint32_t row0, step0, nsteps, part;
+} bsmr_attention_panel_item;
+typedef struct {
+    uint32_t row0, part0, nparts, pad;
+} bsmr_attention_panel_red;
+int bsmr_attention_panel_lists(uint32_t M, uint32_t N, const uint32_t* rowptr, const uint32_t* colidx,
+                               const uint32_t* order, uint32_t norder, uint32_t* rows,
+                               bsmr_attention_panel_step* steps, uint64_t* nsteps, bsmr_attention_panel_item* items,
+                               uint64_t* nitems, bsmr_attention_panel_red* reds, uint64_t* nreds);
 
 /* Timing: run `iters` back-to-back SDDMMs on `stream`, timing each kernel with HIP events on
  * that stream (BSMR_ERR_UNSUPPORTED on a capturing stream). Outputs average ms per launch of the dense-tile kernel, the residual kernel and

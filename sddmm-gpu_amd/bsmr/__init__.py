@@ -8,7 +8,8 @@ Reference interface mirrored (paths relative to the reference root):
   * evaluationReordering                               -> Plan.evaluate   (src/BSMR.cpp:826-994)
 Beyond the reference: the gradients of the SDDMM as SpMM over the same plan (Plan.spmm,
 Plan.spmm_t, Plan.sddmm_backward), the row softmax over the plan's pattern (Plan.softmax,
-Plan.softmax_backward), the fused sparse attention forward and backward (Plan.attention, Plan.attention_backward; Plan.attention_heads and Plan.attention_backward_heads over batch and heads on strided
+Plan.softmax_backward), the fused sparse attention forward and backward (Plan.attention, its panel form on
+matrix instructions Plan.attention_panels, Plan.attention_backward; Plan.attention_heads and Plan.attention_backward_heads over batch and heads on strided
 operands), and bsmr.autograd,
 which wraps SDDMM, softmax and SpMM for torch.autograd and composes them into sparse attention.
 
@@ -168,6 +169,16 @@ class AttentionStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class AttentionPanelsStats(C.Structure):
+    """bsmr_attention_panels_stats: the panel lists of the MFMA attention forward (counts zero when
+    not built), how full their 16 x 32 masks are, and the library's two constants."""
+    _fields_ = [(k, C.c_uint32) for k in ("panels", "items", "steps", "split_panels", "partials", "fill_permille",
+                                          "step_cols", "item_steps")]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class AttentionBackwardStats(C.Structure):
     """bsmr_attention_backward_stats: the fused attention backward's row and column segment lists
     and plan-owned scratch (zeros when not built) and the library's constant chunks."""
@@ -238,6 +249,10 @@ EXPORTS = [
     "bsmr_attention_heads", "bsmr_attention_backward_heads", "bsmr_plan_prepare_attention_heads",
     "bsmr_plan_attention_heads_prepared", "bsmr_plan_prepare_attention_backward_heads",
     "bsmr_plan_attention_backward_heads_prepared", "bsmr_attention_layout_check",
+    "bsmr_attention_panels", "bsmr_attention_panels_heads", "bsmr_plan_prepare_attention_panels",
+    "bsmr_plan_prepare_attention_panels_heads", "bsmr_plan_attention_panels_prepared",
+    "bsmr_plan_attention_panels_heads_prepared", "bsmr_plan_attention_panels_stats",
+    "bsmr_attention_panels_limits", "bsmr_attention_panel_lists",
 ]
 
 # include/bsmr.h BSMR_ATTENTION_MAX_BATCHES, BSMR_ATTENTION_MAX_HEADS
@@ -379,6 +394,23 @@ def lib():
         getattr(L, f).restype = C.c_int
     L.bsmr_attention_layout_check.argtypes = [op] + [C.c_uint32] * 5 + [C.c_int]
     L.bsmr_attention_layout_check.restype = C.c_int
+    L.bsmr_attention_panels.argtypes = L.bsmr_attention.argtypes
+    L.bsmr_attention_panels.restype = C.c_int
+    L.bsmr_attention_panels_heads.argtypes = L.bsmr_attention_heads.argtypes
+    L.bsmr_attention_panels_heads.restype = C.c_int
+    for f in ("bsmr_plan_prepare_attention_panels", "bsmr_plan_attention_panels_prepared"):
+        getattr(L, f).argtypes = [vp, C.c_uint32, C.c_uint32]
+        getattr(L, f).restype = C.c_int
+    for f in ("bsmr_plan_prepare_attention_panels_heads", "bsmr_plan_attention_panels_heads_prepared"):
+        getattr(L, f).argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32]
+        getattr(L, f).restype = C.c_int
+    L.bsmr_plan_attention_panels_stats.argtypes = [vp, C.POINTER(AttentionPanelsStats)]
+    L.bsmr_plan_attention_panels_stats.restype = C.c_int
+    L.bsmr_attention_panels_limits.argtypes = [C.POINTER(C.c_uint32)] * 2
+    L.bsmr_attention_panels_limits.restype = None
+    u64p = C.POINTER(C.c_uint64)
+    L.bsmr_attention_panel_lists.argtypes = [C.c_uint32, C.c_uint32, vp, vp, vp, C.c_uint32, vp, vp, u64p, vp, u64p, vp, u64p]
+    L.bsmr_attention_panel_lists.restype = C.c_int
     L.bsmr_plan_check.argtypes = [vp, C.c_uint32, C.c_int, C.c_int]
     L.bsmr_plan_check.restype = C.c_int
     L.bsmr_check_rphm_arrays.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32] + [_u32p] * 2 + \
@@ -768,6 +800,42 @@ class Plan:
     def attention_backward_heads_prepared(self, D, Dv, slices):
         return bool(lib().bsmr_plan_attention_backward_heads_prepared(self.h, D, Dv, slices))
 
+    def attention_panels(self, dQ, dK, dV, D, Dv, dO, dLse=0, scale=1.0, stream=0, dtype=F16):
+        """bsmr_attention_panels: Plan.attention's O and LSE for fp16 / bf16 operands and D, Dv in
+        {32, 64, 128, 256}, per 16-row panel on matrix instructions: one load of a K / V row per
+        panel that references it (attention_panels_stats()["fill_permille"] says how well the
+        pattern suits it). Opt-in; nothing selects it automatically."""
+        _check(lib().bsmr_attention_panels(self.h, dQ, dK, dV, D, Dv, dtype, scale, dO, dLse or None,
+                                           stream or None), "bsmr_attention_panels")
+
+    def attention_panels_heads(self, batches, heads, Q, K, V, D, Dv, O, dLse=0, scale=1.0, stream=0, dtype=F16):
+        """bsmr_attention_panels_heads: attention_panels over batches x heads slices in one call;
+        operands as in attention_heads."""
+        ops = [AttentionOperand.of(x) for x in (Q, K, V, O)]
+        ref = [None if o is None else C.byref(o) for o in ops]
+        _check(lib().bsmr_attention_panels_heads(self.h, batches, heads, ref[0], ref[1], ref[2], D, Dv, dtype, scale,
+                                                 ref[3], dLse or None, stream or None), "bsmr_attention_panels_heads")
+
+    def prepare_attention_panels(self, D, Dv):
+        """bsmr_plan_prepare_attention_panels: the panel lists and the scratch of the split panels
+        for Dv now, so that the first attention_panels launch can be captured."""
+        _check(lib().bsmr_plan_prepare_attention_panels(self.h, D, Dv), "bsmr_plan_prepare_attention_panels")
+
+    def prepare_attention_panels_heads(self, D, Dv, slices):
+        _check(lib().bsmr_plan_prepare_attention_panels_heads(self.h, D, Dv, slices),
+               "bsmr_plan_prepare_attention_panels_heads")
+
+    def attention_panels_prepared(self, D, Dv):
+        return bool(lib().bsmr_plan_attention_panels_prepared(self.h, D, Dv))
+
+    def attention_panels_heads_prepared(self, D, Dv, slices):
+        return bool(lib().bsmr_plan_attention_panels_heads_prepared(self.h, D, Dv, slices))
+
+    def attention_panels_stats(self):
+        s = AttentionPanelsStats()
+        _check(lib().bsmr_plan_attention_panels_stats(self.h, C.byref(s)), "bsmr_plan_attention_panels_stats")
+        return s.as_dict()
+
     def sddmm_backward(self, dG, dA, dB, K, dGA, dGB, stream=0, dtype=F32):
         """The gradients of P = sddmm(A, B) from dG = dL/dP (fp32, nnz): dGA (M x K fp32) =
         S(G) B and dGB (N x K fp32) = S(G)^T A. Either output may be 0: that side is skipped."""
@@ -885,6 +953,33 @@ def attention_limits():
     c, b = C.c_uint32(), C.c_uint32()
     lib().bsmr_attention_limits(C.byref(c), C.byref(b))
     return dict(chunk=c.value, max_row_bytes=b.value)
+
+
+def attention_panels_limits():
+    """bsmr_attention_panels_limits (host only): dict(step_cols, item_steps), the constants of
+    Plan.attention_panels without a plan."""
+    c, i = C.c_uint32(), C.c_uint32()
+    lib().bsmr_attention_panels_limits(C.byref(c), C.byref(i))
+    return dict(step_cols=c.value, item_steps=i.value)
+
+
+def attention_panel_lists(M, N, rowptr, colidx, order=()):
+    """bsmr_attention_panel_lists (host only): (rows, cols, masks, items, reds) of the panel form of
+    the attention forward over the launch order `order` + the rows it does not name: rows (M,), cols
+    (steps, 32) and masks (steps, 16) of the steps, items (n, 4) {row0, step0, nsteps, part} and
+    reds (n, 4) {row0, part0, nparts, 0}, all uint32."""
+    rowptr, colidx, order = (np.ascontiguousarray(x, np.uint32) for x in (rowptr, colidx, order))
+    if len(rowptr) != M + 1 or len(colidx) != int(rowptr[-1]):
+        raise ValueError("attention_panel_lists: rowptr needs M + 1 entries and colidx rowptr[M]")
+    n = [C.c_uint64() for _ in range(3)]
+    args = (M, N, rowptr.ctypes.data, colidx.ctypes.data, order.ctypes.data, len(order))
+    _check(lib().bsmr_attention_panel_lists(*args, None, None, C.byref(n[0]), None, C.byref(n[1]), None, C.byref(n[2])),
+           "bsmr_attention_panel_lists")
+    rows = np.zeros(M, np.uint32)
+    steps, items, reds = (np.zeros((c.value, w), np.uint32) for c, w in zip(n, (48, 4, 4)))
+    _check(lib().bsmr_attention_panel_lists(*args, rows.ctypes.data, steps.ctypes.data, C.byref(n[0]), items.ctypes.data,
+                                            C.byref(n[1]), reds.ctypes.data, C.byref(n[2])), "bsmr_attention_panel_lists")
+    return rows, steps[:, :32], steps[:, 32:], items, reds
 
 
 def attention_backward_limits():

@@ -257,12 +257,12 @@ def _validate_fused(plan, Q, K, V):
 
 class _AttentionFused(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, Q, K, V, plan, scale, want_lse):
+    def forward(ctx, Q, K, V, plan, scale, want_lse, panels=False):
         D, Dv, dtype = _validate_fused(plan, Q, K, V)
         O = torch.empty((plan.M, Dv), dtype=torch.float32, device=Q.device)
         lse = torch.empty(plan.M, dtype=torch.float32, device=Q.device) if want_lse else None
-        plan.attention(Q.data_ptr(), K.data_ptr(), V.data_ptr(), D, Dv, O.data_ptr(),
-                       lse.data_ptr() if want_lse else 0, scale, stream=_stream(), dtype=dtype)
+        (plan.attention_panels if panels else plan.attention)(Q.data_ptr(), K.data_ptr(), V.data_ptr(), D, Dv, O.data_ptr(),
+            lse.data_ptr() if want_lse else 0, scale, stream=_stream(), dtype=dtype)
         ctx.plan, ctx.scale, ctx.dims = plan, scale, (D, Dv, dtype)
         ctx.save_for_backward(Q, K, V)
         if not want_lse:
@@ -304,7 +304,7 @@ class _AttentionFused(torch.autograd.Function):
                                 gK.data_ptr() if gK is not None else 0, stream=s, dtype=dtype)
             gQ = None if gQ is None else gQ.to(Q.dtype)
             gK = None if gK is None else gK.to(K.dtype)
-        return gQ, gK, gV, None, None, None
+        return gQ, gK, gV, None, None, None, None
 
 
 class _AttentionFusedBwd(torch.autograd.Function):
@@ -312,12 +312,13 @@ class _AttentionFusedBwd(torch.autograd.Function):
     LSE; the backward is one Plan.attention_backward call."""
 
     @staticmethod
-    def forward(ctx, Q, K, V, plan, scale, want_lse):
+    def forward(ctx, Q, K, V, plan, scale, want_lse, panels=False):
         D, Dv, dtype = _validate_fused(plan, Q, K, V)
         O = torch.empty((plan.M, Dv), dtype=torch.float32, device=Q.device)
         lse = torch.empty(max(plan.M, 1), dtype=torch.float32, device=Q.device)
-        plan.attention(Q.data_ptr(), K.data_ptr(), V.data_ptr(), D, Dv, O.data_ptr(), lse.data_ptr(), scale,
-                       stream=_stream(), dtype=dtype)
+        (plan.attention_panels if panels else plan.attention)(
+            Q.data_ptr(), K.data_ptr(), V.data_ptr(), D, Dv, O.data_ptr(), lse.data_ptr(), scale, stream=_stream(),
+            dtype=dtype)
         lse = lse[:plan.M]
         ctx.plan, ctx.scale, ctx.dims = plan, scale, (D, Dv, dtype)
         ctx.save_for_backward(Q, K, V, O, lse)
@@ -332,7 +333,7 @@ class _AttentionFusedBwd(torch.autograd.Function):
         plan = ctx.plan
         D, Dv, dtype = ctx.dims
         if not any(ctx.needs_input_grad[:3]):
-            return None, None, None, None, None, None
+            return None, None, None, None, None, None, None
         dO = grad.contiguous().float()
         out = [torch.empty(shape, dtype=torch.float32, device=Q.device) if need else None
                for need, shape in zip(ctx.needs_input_grad[:3], ((plan.M, D), (plan.N, D), (plan.N, Dv)))]
@@ -341,10 +342,21 @@ class _AttentionFusedBwd(torch.autograd.Function):
                                 _launchable(lse).data_ptr(), D, Dv, ptr[0], ptr[1], ptr[2], ctx.scale,
                                 stream=_stream(), dtype=dtype)
         gQ, gK, gV = (None if t is None else t.to(X.dtype) for t, X in zip(out, (Q, K, V)))
-        return gQ, gK, gV, None, None, None
+        return gQ, gK, gV, None, None, None, None
 
 
-def attention_fused(plan, Q, K, V, scale=None, return_lse=False, backward="recompute"):
+def _validate_forward(who, forward, Q, D, Dv):
+    """forward = "gather" (Plan.attention) or "panels" (Plan.attention_panels: float16 / bfloat16 and
+    D, Dv in {32, 64, 128, 256}); ValueError before any launch otherwise. Returns forward == "panels"."""
+    if forward not in ("gather", "panels"):
+        raise ValueError(f"{who}: forward = {forward!r} must be \"gather\" or \"panels\"")
+    if forward == "panels" and (Q.dtype == torch.float32 or D not in (32, 64, 128, 256) or Dv not in (32, 64, 128, 256)):
+        raise ValueError(f"{who}: forward = \"panels\" takes float16 / bfloat16 and D, Dv in 32, 64, 128, 256; got "
+                         f"{Q.dtype}, D = {D}, Dv = {Dv}")
+    return forward == "panels"
+
+
+def attention_fused(plan, Q, K, V, scale=None, return_lse=False, backward="recompute", forward="gather"):
     """O (M, Dv) float32 of attention(plan, Q, K, V, scale) from one fused forward launch
     (Plan.attention: no nnz-sized scores or weights are written), and with return_lse=True also
     LSE (M,) float32 = max * scale + ln(sum) per row (-inf for an empty row), returned
@@ -363,7 +375,12 @@ def attention_fused(plan, Q, K, V, scale=None, return_lse=False, backward="recom
     one Plan.attention_backward call (at most five launches) that computes dQ, dK and dV per entry
     in registers and allocates no nnz-sized tensor, skipping the side no input needs. Its gradients
     agree with the default path's within the two paths' error bounds, not bit for bit. Any other
-    value of `backward` raises ValueError before any launch."""
+    value of `backward` raises ValueError before any launch.
+
+    forward="panels": the forward is Plan.attention_panels (float16 / bfloat16, D and Dv in {32, 64,
+    128, 256}; matrix instructions per 16-row panel, for patterns whose panel rows share columns)
+    instead of Plan.attention; either backward takes it, the fused one from this forward's O and
+    LSE. The default "gather" is the path as it was; nothing chooses between them automatically."""
     if backward not in ("recompute", "fused"):
         raise ValueError(f"attention_fused: backward = {backward!r} must be \"recompute\" or \"fused\"")
     if scale is None:
@@ -371,9 +388,10 @@ def attention_fused(plan, Q, K, V, scale=None, return_lse=False, backward="recom
             raise ValueError("attention_fused: Q must be an (M, D) tensor with D > 0")
         scale = Q.shape[1] ** -0.5
     scale = _valid_scale("attention_fused", scale)
-    _validate_fused(plan, Q, K, V)
+    D, Dv, _ = _validate_fused(plan, Q, K, V)
+    panels = _validate_forward("attention_fused", forward, Q, D, Dv)
     fn = _AttentionFusedBwd if backward == "fused" else _AttentionFused
-    return fn.apply(Q, K, V, plan, scale, bool(return_lse))
+    return fn.apply(Q, K, V, plan, scale, bool(return_lse), panels)
 
 
 def _validate_heads(plan, Q, K, V):
@@ -432,12 +450,12 @@ class _AttentionFusedHeads(torch.autograd.Function):
     is one Plan.attention_backward_heads call."""
 
     @staticmethod
-    def forward(ctx, Q, K, V, plan, scale, want_lse, checked):
+    def forward(ctx, Q, K, V, plan, scale, want_lse, checked, panels=False):
         lead, D, Dv, dtype = checked  # (_validate_heads, run once by attention_fused_heads)
         B, H = (1,) * (2 - len(lead)) + lead
         O = _dense_like(Q, lead + (plan.M, Dv))
         lse = torch.empty(lead + (plan.M,), dtype=torch.float32, device=Q.device)
-        plan.attention_heads(B, H, Q, K, V, D, Dv, O, lse.data_ptr(), scale, stream=_stream(), dtype=dtype)
+        (plan.attention_panels_heads if panels else plan.attention_heads)(B, H, Q, K, V, D, Dv, O, lse.data_ptr(), scale, stream=_stream(), dtype=dtype)
         ctx.plan, ctx.scale, ctx.dims = plan, scale, (B, H, D, Dv, dtype)
         ctx.save_for_backward(Q, K, V, O, lse)
         if not want_lse:
@@ -451,7 +469,7 @@ class _AttentionFusedHeads(torch.autograd.Function):
         plan = ctx.plan
         B, H, D, Dv, dtype = ctx.dims
         if not any(ctx.needs_input_grad[:3]):
-            return None, None, None, None, None, None, None
+            return None, None, None, None, None, None, None, None
         dO = grad if grad.dtype == torch.float32 else grad.float()
         if dO.stride(-1) != 1 or attention_layout_check(dO, B, H, plan.M, Dv, 4, False) is not None:
             dO = dO.contiguous()
@@ -459,10 +477,10 @@ class _AttentionFusedHeads(torch.autograd.Function):
         plan.attention_backward_heads(B, H, Q, K, V, O, dO, lse.data_ptr(), D, Dv, out[0], out[1], out[2], ctx.scale,
                                       stream=_stream(), dtype=dtype)
         gQ, gK, gV = (None if t is None else t.to(X.dtype) for t, X in zip(out, (Q, K, V)))
-        return gQ, gK, gV, None, None, None, None
+        return gQ, gK, gV, None, None, None, None, None
 
 
-def attention_fused_heads(plan, Q, K, V, scale=None, return_lse=False):
+def attention_fused_heads(plan, Q, K, V, scale=None, return_lse=False, forward="gather"):
     """attention_fused(..., backward="fused") over heads and an optional batch of one sparsity
     pattern: Q (H, M, D) or (B, H, M, D), K and V the same with N rows (V of width Dv). Returns O
     (..., M, Dv) float32 and, with return_lse=True, LSE (..., M) float32, non-differentiable.
@@ -480,11 +498,13 @@ def attention_fused_heads(plan, Q, K, V, scale=None, return_lse=False):
     outputs no input needs. Gradients are dense, in their input's dimension order, and cast to the
     input's dtype; for an expanded input they are dense in standard order and torch's expand
     backward sums them. Slice (b, h) of every result equals, bit for bit, attention_fused(...,
-    backward="fused") on contiguous copies of that slice."""
+    backward="fused") on contiguous copies of that slice. forward="panels" as in attention_fused:
+    one Plan.attention_panels_heads call instead of Plan.attention_heads."""
     if scale is None:
         if not isinstance(Q, torch.Tensor) or Q.dim() not in (3, 4) or Q.shape[-1] == 0:
             raise ValueError("attention_fused_heads: Q must be an (H, M, D) or (B, H, M, D) tensor with D > 0")
         scale = Q.shape[-1] ** -0.5
     scale = _valid_scale("attention_fused_heads", scale)
     checked = _validate_heads(plan, Q, K, V)
-    return _AttentionFusedHeads.apply(Q, K, V, plan, scale, bool(return_lse), checked)
+    panels = _validate_forward("attention_fused_heads", forward, Q, checked[1], checked[2])
+    return _AttentionFusedHeads.apply(Q, K, V, plan, scale, bool(return_lse), checked, panels)

@@ -1,0 +1,559 @@
+// attention_panels.hip — fused sparse attention forward for gfx950 on matrix instructions, per
+// 16-row panel of the plan's reordered rows (bsmr_attention_panels; fp16 / bf16 operands):
+//
+//   O[i,:] = sum_e W_e V[j_e,:],  W = softmax over row i of scale dot(Q[i,:], K[j_e,:])
+//
+// The gather kernel (attention.hip) loads a K row and a V row per entry. Here a wave takes an item
+// (attention_panels.hpp): up to PANEL_ITEM_STEPS steps of 32 columns of one panel's column union,
+// and loads every K and V row of the union once for the panel's 16 rows. Both products run on
+// v_mfma_f32_16x16x32_{f16,bf16}, transposed, so that every per-row quantity of query row r lives
+// on the lanes l with (l & 15) == r and nothing is shuffled between the two products. With
+// r = l & 15 and g = l >> 4:
+//   Q        lane (r, g) keeps Q[row r][32 s + 8 g, +8) of every k-step s in registers (D / 32
+//            16-byte loads for the whole item; a row past a short panel's end is zeros);
+//   scores   per step and 16-column tile, S^T = K_tile Q^T: the A operand of lane (i, g) is the
+//            gathered K row of tile column i, elements [32 s + 8 g, +8) (a 16-byte load from L2;
+//            the next step's K rows are requested as soon as this step's score MFMAs are issued),
+//            the B operand the Q registers. Lane (r, g) gets the scores of its own row at step
+//            columns 4 g + j (tile 0) and 16 + 4 g + j (tile 1), j = 0 .. 3;
+//   mask     a select per score on bit (column) of the row's 32-bit mask: -inf where the row does
+//            not store the column, whatever the product was (a NaN of another row's K row too);
+//   softmax  online, per row: the step's maximum over the lane's eight scores and the two xor
+//            steps 16 and 32; m' = max(m, m_step); f = 2^((m - m') c), t = 2^((p - m') c) with
+//            c = scale log2(e) rounded once from double; shift_of as in attention.hip, so a row
+//            that has seen only -inf keeps m = -inf, l = 0, acc = 0. A lane's l holds the fp32 t
+//            of its own eight columns per step (l = l f + sum t, in column order); the four lanes
+//            of a row are added in g order at the end;
+//   O        O^T += V^T P^T per 16 columns of Dv: the B operand is the lane's eight t rounded to
+//            the operand type (k-slot 8 g + j is step column 4 g + j for j < 4, 16 + 4 g + j - 4
+//            else), the A operand V[those eight columns][dv]. The step's 32 V rows are staged in
+//            LDS by 16-byte loads and stores, rows 2 Dv + 16 bytes apart; lane (i, g) reads the
+//            32-bit word of elements (32 n + 2 i, 32 n + 2 i + 1) of its eight rows and splits it
+//            with two byte permutes per row pair into the A operands of two MFMAs: the even
+//            elements of [32 n, +32) and the odd ones. One instruction's 64 reads fall on 64
+//            different banks: the word index is (4 g + j)(Dv / 2 + 4) + 16 n + i = 16 g + i + const
+//            (mod 64). Lane (r, g) then holds O[row r][32 n + 8 g, +8): the row's rescale by f,
+//            the final 1 / l and two 16-byte stores per pair sit on the lane that owns the row.
+// An item that is its panel's only one stores acc / l and m scale + ln l; an item of a split
+// panel stores (m, l, acc) per row to plan-owned scratch and k_attention_panels_reduce combines
+// the items as k_attention_reduce does: M = max m_i, every partial scaled once by 2^((m_i - M) c)
+// (a rounded product), added in item order. No atomics; the order is a function of the panel's
+// column union alone.
+//
+// Conventions: bsmr_attention's, but for a NaN or inf in a V row, which reaches every row of the
+// panels whose column union holds that column (0 x NaN inside the MFMA is NaN) and no row of any
+// other panel.
+//
+// Resources: four waves per workgroup, one item each, with 32 (2 Dv + 16) bytes of LDS per wave
+// (66 KiB per workgroup at Dv = 256: two workgroups per CU, two waves per SIMD, which is what
+// amdgpu_waves_per_eu(2) lets the register allocator count on: 256 VGPRs).
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "attention_common.hpp"
+#include "attention_layout.hpp"
+#include "attention_panels.hpp"
+#include "plan.hpp"
+#include "seg_walk.hpp"  // exp2_hw
+
+namespace bsmr {
+namespace {
+
+constexpr u32 PANEL_WAVES = 4;  // waves (items) per workgroup
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 h16x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 b16x2 __attribute__((ext_vector_type(2)));
+typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 b16x8 __attribute__((ext_vector_type(8)));
+
+struct PanelArgs {
+    const PanelItem* items;
+    const PanelStep* steps;
+    const u32* rows;
+    AttnOpBytes Q, K, V, O;  // strides in bytes
+    float* lse;              // slices x M, or null
+    float* pacc;             // slices x partials x 16 x Dv
+    float* pml;              // behind them: slices x partials x 16 x (m, l)
+    u32 partials, heads, M, nItems;
+    float c, scale;  // scale log2(e), rounded once from double; scale
+};
+
+// attention.hip's conventions
+__device__ __forceinline__ float shift_of(float m) { return m == -INFINITY ? 0.f : m; }
+__device__ __forceinline__ float inverse_of(float s) { return s == 0.f ? 0.f : 1.0f / s; }
+
+template <int DT>
+__device__ __forceinline__ f32x4 mfma32(const uint4& a, const uint4& b, const f32x4 c) {
+    if constexpr (DT == BSMR_F16)
+        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h16x8, a), __builtin_bit_cast(h16x8, b), c, 0, 0, 0);
+    else
+        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(b16x8, a), __builtin_bit_cast(b16x8, b), c, 0, 0, 0);
+}
+
+// two weights rounded to the operand type (nearest even), lo in the low half
+template <int DT>
+__device__ __forceinline__ u32 pack2(float lo, float hi) {
+    if constexpr (DT == BSMR_F16) {
+        const h16x2 h = {static_cast<_Float16>(lo), static_cast<_Float16>(hi)};
+        return __builtin_bit_cast(u32, h);
+    } else {
+        const b16x2 h = {static_cast<__bf16>(lo), static_cast<__bf16>(hi)};
+        return __builtin_bit_cast(u32, h);
+    }
+}
+
+__device__ __forceinline__ uint4 load16(const char* p) { return *reinterpret_cast<const uint4*>(p); }
+
+__device__ __forceinline__ void wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+template <int DT, int D, int DV>
+__global__ __launch_bounds__(PANEL_WAVES * 64) __attribute__((amdgpu_waves_per_eu(2)))
+void k_attention_panels(const PanelArgs a) {
+    constexpr int KS = D / 32;                // k-steps of a score tile
+    constexpr int NP = DV / 32;               // pairs of output tiles
+    constexpr u32 VROW = 2u * DV + 16u;       // bytes between staged V rows
+    constexpr u32 CPR = DV / 8;               // 16-byte chunks per V row
+    constexpr int VLOADS = DV / 16;           // chunks per lane and step (32 rows)
+    constexpr int VBATCH = VLOADS < 8 ? VLOADS : 8;
+    __shared__ __attribute__((aligned(16))) char vstage[PANEL_WAVES][PANEL_STEP_COLS * VROW];
+
+    const u32 lane = threadIdx.x & 63u;
+    const u32 wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const u32 itemId = blockIdx.x * PANEL_WAVES + wave;
+    if (itemId >= a.nItems) return;
+    const PanelItem it = a.items[itemId];
+    const u32 head = blockIdx.y, bat = blockIdx.z;
+    const size_t slice = static_cast<size_t>(bat) * a.heads + head;
+    const char* Qs = attn_slice_base(a.Q, bat, head);
+    const char* Ks = attn_slice_base(a.K, bat, head);
+    const char* Vs = attn_slice_base(a.V, bat, head);
+    char* Os = attn_slice_base(a.O, bat, head);
+    char* vl = vstage[wave];
+
+    const u32 r = lane & 15u, g = lane >> 4;
+    const bool live = it.row0 + r < a.M;  // (a row of a short last panel is neither loaded nor stored)
+    const u32 row = live ? a.rows[it.row0 + r] : 0u;
+    uint4 q[KS];
+#pragma unroll
+    for (int s = 0; s < KS; ++s)
+        q[s] = live ? load16(Qs + static_cast<size_t>(row) * a.Q.row + (32u * s + 8u * g) * 2u) : make_uint4(0, 0, 0, 0);
+
+    float m = -INFINITY, l = 0.f;
+    f32x4 acc[2 * NP];
+#pragma unroll
+    for (int n = 0; n < 2 * NP; ++n) acc[n] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    const PanelStep* st = a.steps + it.step0;
+    uint4 k0[KS], k1[KS];
+    auto load_k = [&](const PanelStep* sp) {
+        const u32 c0 = sp->cols[r], c1 = sp->cols[16u + r];
+#pragma unroll
+        for (int s = 0; s < KS; ++s) {
+            k0[s] = load16(Ks + static_cast<size_t>(c0) * a.K.row + (32u * s + 8u * g) * 2u);
+            k1[s] = load16(Ks + static_cast<size_t>(c1) * a.K.row + (32u * s + 8u * g) * 2u);
+        }
+    };
+    if (it.nsteps) load_k(st);
+    for (u32 step = 0; step < it.nsteps; ++step, ++st) {
+        const u32 colv = st->cols[lane & 31u];  // lane x holds step column x & 31
+        const u32 mask = st->masks[r];
+        f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int s = 0; s < KS; ++s) {
+            s0 = mfma32<DT>(k0[s], q[s], s0);
+            s1 = mfma32<DT>(k1[s], q[s], s1);
+        }
+        if (step + 1 < it.nsteps) load_k(st + 1);
+
+        // the step's V rows into LDS: chunk x = 64 u + lane is 16 bytes of row x / CPR. The reads
+        // of the step before are done first
+        wave_lds_sync();
+#pragma unroll
+        for (int u0 = 0; u0 < VLOADS; u0 += VBATCH) {
+            uint4 v[VBATCH];
+#pragma unroll
+            for (int u = 0; u < VBATCH; ++u) {
+                const u32 x = 64u * (u0 + u) + lane;
+                const u32 col = __shfl(colv, static_cast<int>(x / CPR));
+                v[u] = load16(Vs + static_cast<size_t>(col) * a.V.row + (x % CPR) * 16u);
+            }
+#pragma unroll
+            for (int u = 0; u < VBATCH; ++u) {
+                const u32 x = 64u * (u0 + u) + lane;
+                *reinterpret_cast<uint4*>(vl + (x / CPR) * VROW + (x % CPR) * 16u) = v[u];
+            }
+        }
+
+        // masked scores of the lane's row, the step's maximum and the weights
+        float p[8];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            p[j] = (mask >> (4u * g + j)) & 1u ? s0[j] : -INFINITY;
+            p[4 + j] = (mask >> (16u + 4u * g + j)) & 1u ? s1[j] : -INFINITY;
+        }
+        float ms = p[0];
+#pragma unroll
+        for (int j = 1; j < 8; ++j) ms = fmaxf(ms, p[j]);
+        ms = fmaxf(ms, __shfl_xor(ms, 16));
+        ms = fmaxf(ms, __shfl_xor(ms, 32));
+        const float mn = fmaxf(m, ms);
+        const float shift = shift_of(mn);
+        const float f = exp2_hw((m - shift) * a.c);
+        m = mn;
+        float t[8], ts = 0.f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            t[j] = exp2_hw((p[j] - shift) * a.c);
+            ts += t[j];
+        }
+        l = l * f + ts;
+        const uint4 pb = make_uint4(pack2<DT>(t[0], t[1]), pack2<DT>(t[2], t[3]), pack2<DT>(t[4], t[5]), pack2<DT>(t[6], t[7]));
+#pragma unroll
+        for (int n = 0; n < 2 * NP; ++n) acc[n] *= f;
+
+        wave_lds_sync();
+#pragma unroll
+        for (int n = 0; n < NP; ++n) {
+            u32 w[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const u32 cc = (j < 4 ? 4u * g + j : 16u + 4u * g + (j - 4));
+                w[j] = *reinterpret_cast<const u32*>(vl + cc * VROW + (32u * n + 2u * r) * 2u);
+            }
+            uint4 even, odd;
+            even.x = __builtin_amdgcn_perm(w[1], w[0], 0x05040100u), odd.x = __builtin_amdgcn_perm(w[1], w[0], 0x07060302u);
+            even.y = __builtin_amdgcn_perm(w[3], w[2], 0x05040100u), odd.y = __builtin_amdgcn_perm(w[3], w[2], 0x07060302u);
+            even.z = __builtin_amdgcn_perm(w[5], w[4], 0x05040100u), odd.z = __builtin_amdgcn_perm(w[5], w[4], 0x07060302u);
+            even.w = __builtin_amdgcn_perm(w[7], w[6], 0x05040100u), odd.w = __builtin_amdgcn_perm(w[7], w[6], 0x07060302u);
+            acc[2 * n] = mfma32<DT>(even, pb, acc[2 * n]);
+            acc[2 * n + 1] = mfma32<DT>(odd, pb, acc[2 * n + 1]);
+        }
+    }
+
+    // the row's four lanes in g order: every lane of the row ends with the same sum
+    const float lt = ((__shfl(l, static_cast<int>(r)) + __shfl(l, static_cast<int>(16u + r))) +
+                      __shfl(l, static_cast<int>(32u + r))) + __shfl(l, static_cast<int>(48u + r));
+    if (!live) return;
+    // acc[2 n][j] and acc[2 n + 1][j] are columns 32 n + 8 g + 2 j and + 2 j + 1 of the row
+    if (it.part == PANEL_DIRECT) {
+        const float inv = inverse_of(lt);
+        float* o = reinterpret_cast<float*>(Os + static_cast<size_t>(row) * a.O.row) + 8u * g;
+#pragma unroll
+        for (int n = 0; n < NP; ++n) {
+            const f32x4 e = acc[2 * n], d = acc[2 * n + 1];
+            *reinterpret_cast<float4*>(o + 32 * n) = make_float4(e[0] * inv, d[0] * inv, e[1] * inv, d[1] * inv);
+            *reinterpret_cast<float4*>(o + 32 * n + 4) = make_float4(e[2] * inv, d[2] * inv, e[3] * inv, d[3] * inv);
+        }
+        if (g == 0 && a.lse) a.lse[slice * a.M + row] = m * a.scale + logf(lt);
+    } else {
+        const size_t slot = (slice * a.partials + it.part) * PANEL_ROWS + r;
+        float* o = a.pacc + slot * DV + 8u * g;
+#pragma unroll
+        for (int n = 0; n < NP; ++n) {
+            const f32x4 e = acc[2 * n], d = acc[2 * n + 1];
+            *reinterpret_cast<float4*>(o + 32 * n) = make_float4(e[0], d[0], e[1], d[1]);
+            *reinterpret_cast<float4*>(o + 32 * n + 4) = make_float4(e[2], d[2], e[3], d[3]);
+        }
+        if (g == 0) {
+            a.pml[2u * slot] = m;
+            a.pml[2u * slot + 1u] = lt;
+        }
+    }
+}
+
+// a split panel's rows: M = max m_i, then every partial scaled once by f_i = 2^((m_i - M) c) (a
+// rounded product each, never fused into the sum) and added in item order; one thread per row and
+// four columns
+__global__ __launch_bounds__(256) void k_attention_panels_reduce(const PanelArgs a, const PanelRed* reds, u32 nReds, u32 Dv) {
+#pragma clang fp contract(off)
+    const u32 head = blockIdx.y, bat = blockIdx.z;
+    const size_t slice = static_cast<size_t>(bat) * a.heads + head;
+    char* O = attn_slice_base(a.O, bat, head);
+    const u32 q4 = Dv / 4u;
+    const size_t t = static_cast<size_t>(blockIdx.x) * 256u + threadIdx.x;
+    if (t >= static_cast<size_t>(nReds) * PANEL_ROWS * q4) return;
+    const PanelRed rd = reds[t / (PANEL_ROWS * q4)];
+    const u32 r = static_cast<u32>(t / q4) % PANEL_ROWS, q = static_cast<u32>(t % q4);
+    if (rd.row0 + r >= a.M) return;
+    const u32 row = a.rows[rd.row0 + r];
+    const size_t slot0 = (slice * a.partials + rd.part0) * PANEL_ROWS + r;
+    const float* ml = a.pml + 2u * slot0;  // partials are 16 slots apart
+    const float4* p = reinterpret_cast<const float4*>(a.pacc + slot0 * Dv) + q;
+    float m = ml[0];
+    for (u32 i = 1; i < rd.nparts; ++i) m = fmaxf(m, ml[2u * PANEL_ROWS * i]);
+    const float shift = shift_of(m);
+    float ls = 0.f;
+    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (u32 i = 0; i < rd.nparts; ++i) {
+        const float f = exp2_hw((ml[2u * PANEL_ROWS * i] - shift) * a.c);
+        const float4 x = p[static_cast<size_t>(i) * PANEL_ROWS * q4];
+        const float fl = f * ml[2u * PANEL_ROWS * i + 1u], fx = f * x.x, fy = f * x.y, fz = f * x.z, fw = f * x.w;
+        ls = i ? ls + fl : fl;
+        s.x = i ? s.x + fx : fx;
+        s.y = i ? s.y + fy : fy;
+        s.z = i ? s.z + fz : fz;
+        s.w = i ? s.w + fw : fw;
+    }
+    const float inv = inverse_of(ls);
+    reinterpret_cast<float4*>(O + static_cast<size_t>(row) * a.O.row)[q] = make_float4(s.x * inv, s.y * inv, s.z * inv, s.w * inv);
+    if (q == 0 && a.lse) a.lse[slice * a.M + row] = m * a.scale + logf(ls);
+}
+
+using PanelFn = void (*)(const PanelArgs);
+
+template <int DT, int D>
+PanelFn pick_dv(u32 Dv) {
+    switch (Dv) {
+        case 32: return k_attention_panels<DT, D, 32>;
+        case 64: return k_attention_panels<DT, D, 64>;
+        case 128: return k_attention_panels<DT, D, 128>;
+        case 256: return k_attention_panels<DT, D, 256>;
+        default: return nullptr;
+    }
+}
+
+template <int DT>
+PanelFn pick_d(u32 D, u32 Dv) {
+    switch (D) {
+        case 32: return pick_dv<DT, 32>(Dv);
+        case 64: return pick_dv<DT, 64>(Dv);
+        case 128: return pick_dv<DT, 128>(Dv);
+        case 256: return pick_dv<DT, 256>(Dv);
+        default: return nullptr;
+    }
+}
+
+bool panel_dim(u32 d) { return d == 32 || d == 64 || d == 128 || d == 256; }
+
+// fp16 / bf16 and the compile-time forms; else BSMR_ERR_UNSUPPORTED with the message set
+int panels_validate_dims(const char* who, u32 D, u32 Dv, int dtype) {
+    if ((dtype != BSMR_F16 && dtype != BSMR_BF16) || !panel_dim(D) || !panel_dim(Dv)) {
+        set_error(std::string(who) + ": dtype must be BSMR_F16 or BSMR_BF16 and D and Dv each one of 32, 64, 128, 256");
+        return BSMR_ERR_UNSUPPORTED;
+    }
+    return BSMR_OK;
+}
+
+size_t panels_scratch_floats(const Plan::AttentionPanelsState& S, u32 Dv, u32 slices) {
+    return attn_sat_mul(attn_sat_mul(slices, S.partials, PANEL_ROWS), Dv + 2u);
+}
+
+bool panels_ready(const Plan::AttentionPanelsState& S, u32 Dv, u32 slices) {
+    return S.built && S.scratch.size() >= panels_scratch_floats(S, Dv, slices);
+}
+
+// build the lists (once) and size the per-slice scratch for (Dv, slices): it grows and never
+// shrinks; layout_mu held. Synchronous on the plan's stream.
+int build_panels(const Plan& p, u32 Dv, u32 slices, const char* who) {
+    Plan::AttentionPanelsState& S = p.attention_panels;
+    const hipStream_t s = p.stream;
+    if (!S.built) {
+        std::vector<u32> hrp, hci, hrows;
+        BSMR_CHECK(p.rowptr.download(hrp, s));
+        BSMR_CHECK(p.colidx.download(hci, s));
+        BSMR_CHECK(p.rows.download(hrows, s));
+        hrows.resize(std::min<size_t>(hrows.size(), p.R));
+        PanelLists L;
+        std::string err;
+        // (the rows the plan's order does not name, its empty ones, get trailing panels of 0 steps; the
+        // lists would compute them from their entries all the same)
+        if (const int st = attention_panel_lists(p.M, p.N, hrp.data(), hci.data(), hrows.data(), static_cast<u32>(hrows.size()), L, err)) {
+            set_error(std::string(who) + ": " + err);
+            return st == 2 ? BSMR_ERR_UNSUPPORTED : BSMR_ERR_INVALID;  // 2: past the lists' capacity
+        }
+        if (L.nItems > (1ull << 31)) {
+            set_error(std::string(who) + ": more than 2^31 items");
+            return BSMR_ERR_UNSUPPORTED;
+        }
+        BSMR_CHECK(S.rows.upload(L.rows.data(), L.rows.size(), s));
+        BSMR_CHECK(S.steps.upload(L.steps.data(), L.steps.size(), s));
+        BSMR_CHECK(S.items.upload(L.items.data(), L.items.size(), s));
+        BSMR_CHECK(S.reds.upload(L.reds.data(), L.reds.size(), s));
+        BSMR_HIP(hipStreamSynchronize(s));
+        S.nItems = static_cast<u32>(L.nItems);
+        S.nSteps = static_cast<u32>(L.nSteps);
+        S.nReds = static_cast<u32>(L.reds.size());
+        S.panels = L.panels;
+        S.splitPanels = L.splitPanels;
+        S.partials = L.partials;
+        S.built = true;
+    }
+    return S.scratch.grow(panels_scratch_floats(S, Dv, slices));
+}
+
+// the launches of bsmr_attention_panels and bsmr_attention_panels_heads, arguments already validated
+int panels_launch(const char* who, const char* prep, const bsmr_plan* plan, u32 batches, u32 heads,
+                  const bsmr_attention_operand& Q, const bsmr_attention_operand& K, const bsmr_attention_operand& V, u32 D,
+                  u32 Dv, int dtype, float scale, float c, const bsmr_attention_operand& O, float* dLse, void* stream) {
+    const Plan& p = plan->p;
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    const Plan::AttentionPanelsState& S = p.attention_panels;
+    const u32 slices = batches * heads;  // (both at most 65535)
+    PanelArgs a{};
+    const PanelRed* reds = nullptr;
+    u32 nReds = 0;
+    {
+        std::lock_guard<std::mutex> g(p.layout_mu);
+        if (!panels_ready(S, Dv, slices)) {
+            const LaunchSite at{s, who, prep, D, dtype};
+            const int st = lazy_build_guard(at);
+            if (st == BSMR_ERR_NOT_PREPARED)
+                set_error(std::string(who) + ": stream is capturing and the panel lists (or their scratch for Dv = " +
+                          std::to_string(Dv) + (slices > 1 ? ", " + std::to_string(slices) + " slices" : std::string()) +
+                          ") are not built; call " + prep + " first");
+            BSMR_CHECK(st);
+            BSMR_CHECK(build_panels(p, Dv, slices, prep));
+        }
+        a.items = S.items.data();
+        a.steps = S.steps.data();
+        a.rows = S.rows.data();
+        a.nItems = S.nItems;
+        a.partials = S.partials;
+        a.pacc = S.scratch.data();
+        reds = S.reds.data();
+        nReds = S.nReds;
+    }
+    a.pml = a.pacc ? a.pacc + static_cast<size_t>(slices) * a.partials * PANEL_ROWS * Dv : nullptr;
+    a.Q = attn_op_bytes(&Q, batches, heads, p.M, 2u);
+    a.K = attn_op_bytes(&K, batches, heads, p.N, 2u);
+    a.V = attn_op_bytes(&V, batches, heads, p.N, 2u);
+    a.O = attn_op_bytes(&O, batches, heads, p.M, 4u);
+    a.lse = dLse;
+    a.heads = heads;
+    a.M = p.M;
+    a.c = c;
+    a.scale = scale;
+    const PanelFn fn = dtype == BSMR_F16 ? pick_d<BSMR_F16>(D, Dv) : pick_d<BSMR_BF16>(D, Dv);
+    if (a.nItems) {
+        const u32 grid = (a.nItems + PANEL_WAVES - 1) / PANEL_WAVES;
+        hipLaunchKernelGGL(fn, dim3(grid, heads, batches), dim3(PANEL_WAVES * 64), 0, s, a);
+        BSMR_HIP(hipGetLastError());
+    }
+    if (nReds) {
+        const size_t threads = static_cast<size_t>(nReds) * PANEL_ROWS * (Dv / 4u);
+        const dim3 rgrid(static_cast<u32>((threads + 255) / 256), heads, batches);
+        hipLaunchKernelGGL(k_attention_panels_reduce, rgrid, dim3(256), 0, s, a, reds, nReds, Dv);
+        BSMR_HIP(hipGetLastError());
+    }
+    return BSMR_OK;
+}
+
+// the prepare calls carry no dtype
+int panels_prepare_args(const char* who, const bsmr_plan* plan, u32 D, u32 Dv, u32 slices) {
+    if (!plan) {
+        set_error(std::string(who) + ": null plan");
+        return BSMR_ERR_INVALID;
+    }
+    BSMR_CHECK(attn_check_slices(who, slices));
+    return panels_validate_dims(who, D, Dv, BSMR_F16);
+}
+
+}  // namespace
+}  // namespace bsmr
+
+using namespace bsmr;
+
+extern "C" int bsmr_attention_panels(const bsmr_plan* plan, const void* dQ, const void* dK, const void* dV, uint32_t D,
+                                     uint32_t Dv, int dtype, float scale, float* dO, float* dLse, void* stream) {
+    const char* who = "bsmr_attention_panels";
+    if (!plan) {
+        set_error("bsmr_attention_panels: null plan");
+        return BSMR_ERR_INVALID;
+    }
+    if (!dQ || !dK || !dV || !dO) {
+        set_error("bsmr_attention_panels: null device pointer");
+        return BSMR_ERR_INVALID;
+    }
+    if (!attn_aligned16(dQ) || !attn_aligned16(dK) || !attn_aligned16(dV) || !attn_aligned16(dO) ||
+        (reinterpret_cast<uintptr_t>(dLse) & 3u)) {
+        set_error("bsmr_attention_panels: dQ, dK, dV and dO must be 16-byte aligned");
+        return BSMR_ERR_INVALID;
+    }
+    float c;
+    BSMR_CHECK(attn_validate_scale(who, scale, &c));
+    BSMR_CHECK(panels_validate_dims(who, D, Dv, dtype));
+    const Plan& p = plan->p;
+    return panels_launch(who, "bsmr_plan_prepare_attention_panels", plan, 1, 1, attention_dense_operand(dQ, 1, p.M, D),
+                         attention_dense_operand(dK, 1, p.N, D), attention_dense_operand(dV, 1, p.N, Dv), D, Dv, dtype, scale,
+                         c, attention_dense_operand(dO, 1, p.M, Dv), dLse, stream);
+}
+
+extern "C" int bsmr_attention_panels_heads(const bsmr_plan* plan, uint32_t batches, uint32_t heads,
+                                           const bsmr_attention_operand* Q, const bsmr_attention_operand* K,
+                                           const bsmr_attention_operand* V, uint32_t D, uint32_t Dv, int dtype, float scale,
+                                           const bsmr_attention_operand* O, float* dLse, void* stream) {
+    const char* who = "bsmr_attention_panels_heads";
+    if (!plan) {
+        set_error("bsmr_attention_panels_heads: null plan");
+        return BSMR_ERR_INVALID;
+    }
+    if (reinterpret_cast<uintptr_t>(dLse) & 3u) {
+        set_error("bsmr_attention_panels_heads: dLse must be 4-byte aligned");
+        return BSMR_ERR_INVALID;
+    }
+    float c;
+    BSMR_CHECK(attn_validate_scale(who, scale, &c));
+    BSMR_CHECK(panels_validate_dims(who, D, Dv, dtype));
+    const Plan& p = plan->p;
+    BSMR_CHECK(attn_check_operand(who, "Q", Q, batches, heads, p.M, D, 2u, false));
+    BSMR_CHECK(attn_check_operand(who, "K", K, batches, heads, p.N, D, 2u, false));
+    BSMR_CHECK(attn_check_operand(who, "V", V, batches, heads, p.N, Dv, 2u, false));
+    BSMR_CHECK(attn_check_operand(who, "O", O, batches, heads, p.M, Dv, 4u, true));
+    return panels_launch(who, "bsmr_plan_prepare_attention_panels_heads", plan, batches, heads, *Q, *K, *V, D, Dv, dtype,
+                         scale, c, *O, dLse, stream);
+}
+
+extern "C" int bsmr_plan_prepare_attention_panels_heads(const bsmr_plan* plan, uint32_t D, uint32_t Dv, uint32_t slices) {
+    const char* who = "bsmr_plan_prepare_attention_panels_heads";
+    BSMR_CHECK(panels_prepare_args(who, plan, D, Dv, slices));
+    std::lock_guard<std::mutex> g(plan->p.layout_mu);
+    return build_panels(plan->p, Dv, slices, who);
+}
+
+extern "C" int bsmr_plan_prepare_attention_panels(const bsmr_plan* plan, uint32_t D, uint32_t Dv) {
+    const char* who = "bsmr_plan_prepare_attention_panels";
+    BSMR_CHECK(panels_prepare_args(who, plan, D, Dv, 1));
+    std::lock_guard<std::mutex> g(plan->p.layout_mu);
+    return build_panels(plan->p, Dv, 1, who);
+}
+
+extern "C" int bsmr_plan_attention_panels_heads_prepared(const bsmr_plan* plan, uint32_t D, uint32_t Dv, uint32_t slices) {
+    if (panels_prepare_args("bsmr_plan_attention_panels_heads_prepared", plan, D, Dv, slices) != BSMR_OK) return 0;
+    std::lock_guard<std::mutex> g(plan->p.layout_mu);
+    return panels_ready(plan->p.attention_panels, Dv, slices) ? 1 : 0;
+}
+
+extern "C" int bsmr_plan_attention_panels_prepared(const bsmr_plan* plan, uint32_t D, uint32_t Dv) {
+    return bsmr_plan_attention_panels_heads_prepared(plan, D, Dv, 1);
+}
+
+extern "C" int bsmr_plan_attention_panels_stats(const bsmr_plan* plan, bsmr_attention_panels_stats* out) {
+    if (!plan || !out) {
+        set_error("bsmr_plan_attention_panels_stats: null argument");
+        return BSMR_ERR_INVALID;
+    }
+    const Plan& p = plan->p;
+    std::lock_guard<std::mutex> g(p.layout_mu);
+    const Plan::AttentionPanelsState& S = p.attention_panels;
+    *out = bsmr_attention_panels_stats{};
+    out->step_cols = PANEL_STEP_COLS;
+    out->item_steps = PANEL_ITEM_STEPS;
+    if (S.built) {
+        out->panels = S.panels;
+        out->items = S.nItems;
+        out->steps = S.nSteps;
+        out->split_panels = S.splitPanels;
+        out->partials = S.partials;
+        out->fill_permille = panel_fill_permille(p.nnz, S.nSteps);
+    }
+    return BSMR_OK;
+}

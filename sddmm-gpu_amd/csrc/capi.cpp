@@ -544,6 +544,39 @@ extern "C" void bsmr_softmax_limits(uint32_t* wave_max, uint32_t* block_pass) {
     if (block_pass) *block_pass = SOFTMAX_BLOCK_PASS;
 }
 
+extern "C" int bsmr_attention_panel_lists(uint32_t M, uint32_t N, const uint32_t* rowptr, const uint32_t* colidx,
+                                          const uint32_t* order, uint32_t norder, uint32_t* rows,
+                                          bsmr_attention_panel_step* steps, uint64_t* nsteps,
+                                          bsmr_attention_panel_item* items, uint64_t* nitems,
+                                          bsmr_attention_panel_red* reds, uint64_t* nreds) {
+    static_assert(sizeof(bsmr_attention_panel_step) == sizeof(PanelStep) && sizeof(bsmr_attention_panel_item) == sizeof(PanelItem) &&
+                      sizeof(bsmr_attention_panel_red) == sizeof(PanelRed),
+                  "the public records mirror attention_panels.hpp");
+    if (!rowptr || !nsteps || !nitems || !nreds) {
+        set_error("bsmr_attention_panel_lists: null argument");
+        return BSMR_ERR_INVALID;
+    }
+    PanelLists L;
+    std::string err;
+    if (const int st = attention_panel_lists(M, N, rowptr, colidx, order, norder, L, err)) {
+        set_error("bsmr_attention_panel_lists: " + err);
+        return st == 2 ? BSMR_ERR_UNSUPPORTED : BSMR_ERR_INVALID;
+    }
+    *nsteps = L.steps.size();
+    *nitems = L.items.size();
+    *nreds = L.reds.size();
+    if (rows) std::copy(L.rows.begin(), L.rows.end(), rows);
+    if (steps) std::memcpy(steps, L.steps.data(), L.steps.size() * sizeof(PanelStep));
+    if (items) std::memcpy(items, L.items.data(), L.items.size() * sizeof(PanelItem));
+    if (reds) std::memcpy(reds, L.reds.data(), L.reds.size() * sizeof(PanelRed));
+    return BSMR_OK;
+}
+
+extern "C" void bsmr_attention_panels_limits(uint32_t* step_cols, uint32_t* item_steps) {
+    if (step_cols) *step_cols = PANEL_STEP_COLS;
+    if (item_steps) *item_steps = PANEL_ITEM_STEPS;
+}
+
 extern "C" int bsmr_plan_shard_rebalance(const bsmr_plan* plan, uint32_t K, int dtype, int world,
                                          const uint32_t* prev_cuts, const float* shard_ms,
                                          uint32_t* cuts) {

@@ -6,6 +6,7 @@
 #include <mutex>
 #include <vector>
 
+#include "attention_panels.hpp"
 #include "common.hpp"
 #include "knobs.hpp"
 #include "launch_select.hpp"
@@ -286,6 +287,25 @@ struct Plan {
         DevBuf<float> scratch;
     };
     mutable AttentionState attention;
+
+    // fused sparse attention forward on matrix instructions (attention_panels.hip;
+    // bsmr_attention_panels): the launch order of the rows, the panels' steps, the items and the
+    // split panels (attention_panels.hpp), and their partials: slices x partials x 16 rows of Dv
+    // accumulator floats followed by slices x partials x 16 (m, l) pairs; the scratch holds what
+    // the largest slices x (Dv + 2) so far needs and never shrinks. Built on first use or by
+    // bsmr_plan_prepare_attention_panels / _heads, under layout_mu; a state of its own, which no
+    // other path reads or writes, and which depends on S and the row order only, so build_columns
+    // keeps it
+    struct AttentionPanelsState {
+        bool built = false;
+        u32 nItems = 0, nReds = 0, nSteps = 0, panels = 0, splitPanels = 0, partials = 0;
+        DevBuf<u32> rows;
+        DevBuf<PanelStep> steps;
+        DevBuf<PanelItem> items;
+        DevBuf<PanelRed> reds;
+        DevBuf<float> scratch;
+    };
+    mutable AttentionPanelsState attention_panels;
 
     // fused sparse attention backward (attention_bwd.hip; bsmr_attention_backward): the rows'
     // segments (the forward's lists: AttentionState's buffers when they were built before this

@@ -63,6 +63,16 @@ is the row side, GQ alone, and the column side, GK and GV alone; delta runs in b
 --baseline-only times the sequential form alone and needs no heads entry point; with --package DIR
 (a directory holding a bsmr package with its built library, e.g. a checkout of another commit) that
 form can be taken from another build in the same session, for A/B runs.
+
+    python3 tools/attention_bench.py --forward panels [--cases C2,C5,C3] [--dtype f16|bf16] [--d 64]
+
+With --forward panels the tool times one Plan.attention_panels (the panel form on matrix
+instructions) against one Plan.attention (the gather form) on the same plan
+and the same fp16 / bf16 tensors, D = Dv = --d, by the same protocol (graphs of `steps`, median of
+`rounds` alternating replays). C5 is the 2,048 x 2,048 mask of 16 x 16 blocks. Per case:
+attention_panels_stats (fill_permille, steps, items, split panels), graph_us of both, their ratio,
+the largest |O_panels - O_gather|, and floor_us: Q, O and LSE once, the step records, and the K and
+V rows of every panel's column union once per panel (32 rows per step, padding included).
 """
 import argparse
 import json
@@ -84,12 +94,17 @@ def main():
     ap.add_argument("--d", type=int, default=64)
     ap.add_argument("--heads", type=int, default=0)
     ap.add_argument("--batches", type=int, default=0)
-    ap.add_argument("--dtype", default="f32", choices=["f32", "f16"])
+    ap.add_argument("--dtype", default="f32", choices=["f32", "f16", "bf16"])
+    ap.add_argument("--forward", default="gather", choices=["gather", "panels"])
     ap.add_argument("--layout", default="bmhd", choices=["bmhd", "bhmd"])
     ap.add_argument("--baseline-only", action="store_true")
     ap.add_argument("--order-probe", action="store_true")
     ap.add_argument("--package", default=None)
     args = ap.parse_args()
+    if args.forward == "panels" and args.dtype == "f32":
+        raise SystemExit("--forward panels takes --dtype f16 or bf16")
+    if args.forward != "panels" and args.dtype == "bf16":
+        raise SystemExit("--dtype bf16 is for --forward panels only")
     if args.package:
         sys.path.insert(0, os.path.abspath(args.package))
     import numpy as np
@@ -140,6 +155,9 @@ def main():
 
     D = args.d
     scale = D ** -0.5
+    if args.forward == "panels":
+        panels_bench(args, torch, dev, graph_of, alternate)
+        return
     if args.heads or args.batches:
         heads_bench(args, torch, np, dev, graph_of, alternate)
         return
@@ -289,6 +307,42 @@ def main():
                 "launches": launches, "backward_peak_bytes": peaks, "nnz_bytes": 4 * nnz, "attention_backward_stats": bst,
                 "fused_bwd_over_composed_bwd": round(graph_us["fused_bwd"] / graph_us["composed_bwd"], 3),
                 "fused_bwd_over_recompute_bwd": round(graph_us["fused_bwd"] / graph_us["recompute_bwd"], 3), "check": check, "torch": torch.__version__}
+        print(json.dumps(line), flush=True)
+
+
+def panels_bench(args, torch, dev, graph_of, alternate):
+    """The --forward panels mode (module docstring)."""
+    from bsmr import BF16, F16, Plan, make_data, synth
+
+    D = args.d
+    scale = D ** -0.5
+    tdt, dtype = (torch.bfloat16, BF16) if args.dtype == "bf16" else (torch.float16, F16)
+    p = lambda t: t.data_ptr()  # noqa: E731
+    patterns = {"C2": synth.nips_like, "C3": synth.cop20k_like, "C5": lambda: synth.dlmc_like("block")}
+    for case in args.cases.split(","):
+        if case not in patterns:
+            raise SystemExit(f"unknown case {case}")
+        M, N, rp, ci = patterns[case]()
+        nnz = len(ci)
+        plan = Plan(M, N, rp, ci, alpha=0.3, delta=0.3)
+        plan.prepare_attention(D, D)
+        plan.prepare_attention_panels(D, D)
+        data = lambda rows: (torch.from_numpy(make_data(rows * D)).to(dev) - 1.0).reshape(rows, D).to(tdt)  # noqa: E731
+        Q, K, V = data(M), data(N), data(N)
+        out = {k: (torch.zeros(M, D, device=dev), torch.zeros(M, device=dev)) for k in ("gather", "panels")}
+        ours = {"gather": lambda s: plan.attention(p(Q), p(K), p(V), D, D, p(out["gather"][0]), p(out["gather"][1]), scale,
+                                                   stream=s, dtype=dtype),
+                "panels": lambda s: plan.attention_panels(p(Q), p(K), p(V), D, D, p(out["panels"][0]), p(out["panels"][1]),
+                                                          scale, stream=s, dtype=dtype)}
+        graphs = {k: graph_of(f) for k, f in ours.items()}
+        graph_us = alternate({k: g.replay for k, g in graphs.items()})
+        st = plan.attention_panels_stats()
+        floor = (2 * D * M + 4 * D * M + 4 * M + 192 * st["steps"] + 2 * 2 * D * 32 * st["steps"]) / HBM_BYTES_PER_S * 1e6
+        line = {"case": case, "mode": "panels", "M": M, "N": N, "nnz": nnz, "D": D, "dtype": args.dtype, "steps": args.steps,
+                "rounds": args.rounds, "attention_panels_stats": st, "attention_stats": plan.attention_stats(),
+                "graph_us": graph_us, "panels_over_gather": round(graph_us["panels"] / graph_us["gather"], 3),
+                "floor_us": round(floor, 3), "floor_fraction": round(floor / graph_us["panels"], 3),
+                "max_abs_diff": (out["panels"][0] - out["gather"][0]).abs().max().item()}
         print(json.dumps(line), flush=True)
 
 

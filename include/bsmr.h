@@ -56,7 +56,9 @@ extern "C" {
                               new declarations only); bsmr_attention_panels, its heads form, their
                               prepare / prepared / stats / limits calls and
                               bsmr_attention_panel_lists (the panel MFMA forward: new declarations
-                              only) */
+                              only); bsmr_attention_backward_panels, its heads form, their prepare /
+                              prepared / stats calls and bsmr_attention_pattern_transpose (the panel
+                              MFMA backward: new declarations only) */
 
 typedef enum {
     BSMR_OK = 0,
@@ -823,6 +825,77 @@ int bsmr_attention_panel_lists(uint32_t M, uint32_t N, const uint32_t* rowptr, c
                                const uint32_t* order, uint32_t norder, uint32_t* rows,
                                bsmr_attention_panel_step* steps, uint64_t* nsteps, bsmr_attention_panel_item* items,
                                uint64_t* nitems, bsmr_attention_panel_red* reds, uint64_t* nreds);
+
+/* -------------------- fused sparse attention backward on matrix instructions, per panel ---- */
+/* The gradients of bsmr_attention_backward, for fp16 / bf16 operands, on
+ * v_mfma_f32_16x16x32_{f16,bf16}. Definition, inputs (the six of
+ * bsmr_attention_backward, with O, GO, LSE and the three gradients fp32), NULL outputs (any, not all
+ * three: BSMR_ERR_INVALID), every element of a requested output written, pointer / alignment /
+ * scale / layout rules and their status codes, untouched outputs on every error: all
+ * bsmr_attention_backward's and bsmr_attention_backward_heads'.
+ * dtype is BSMR_F16 or BSMR_BF16 and D and Dv are each one of 32, 64, 128; anything else (BSMR_F32
+ * and 256 too) gives BSMR_ERR_UNSUPPORTED. 256 is left out on purpose: at D = Dv = 256 the columns
+ * side would hold K, V, GK and GV in 32 + 32 + 64 + 64 registers before an operand is in flight.
+ * Rows side (GQ): a wave per item of the forward's panel lists (the very lists of
+ * bsmr_attention_panels, built here if no forward built them): Q and GO of the panel's 16 rows in
+ * registers, every K and V row of the panel's column union loaded once per panel. Columns side (GK,
+ * GV): the same kind of lists of the transposed pattern, panels of 16 consecutive columns in
+ * ascending index and steps of 32 union rows: K and V of the panel in registers, every Q and GO row
+ * of the union loaded once per panel. p and g come out of the MFMA in fp32; x = p scale,
+ * w = 2^((x - LSE) log2e), dp = (w (g - delta)) scale are bsmr_attention_backward's fp32 steps; where
+ * the pattern does not store (i, j), w and dp are exactly +0 by a select after the products.
+ * Conventions (beyond bsmr_attention_backward's):
+ *   rounding: GO, w and dp are rounded once (nearest even) to the operand dtype before they enter an
+ *   MFMA; in fp16 a |GO| or |dp| above 65504 becomes inf there (bf16 has no such limit);
+ *   NaN / inf: one in a row that is staged for a second product reaches every destination of the
+ *   panels whose union holds that row (0 x NaN inside the MFMA is NaN) and no other destination:
+ *   K[j] the GQ rows of the row panels whose column union holds j; Q[i] or GO[i] the GK / GV rows
+ *   of the column panels whose row union holds i. Otherwise as bsmr_attention_backward (V[j]: the
+ *   GQ rows that store j and GK[j]; LSE[i]: GQ[i] and the GK / GV rows of the columns row i stores);
+ *   a row with LSE = -inf has w = 0 and adds nothing; a row or column without entries gets +0.
+ * At most five launches (delta, rows, rows reduce, columns, columns reduce), no atomics: a split
+ * panel's items go through partial slots added in item order by plain sums. The summation order is
+ * a function of the panel unions alone: results are bitwise reproducible, equal between a lazily
+ * built and a prepared plan and between a heads slice and the single-slice call; they are not the
+ * bits of bsmr_attention_backward. Plan-owned state of its own (delta, slices x M floats; scratch of
+ * slices x row_partials x 16 x D and slices x col_partials x 16 x (D + Dv) floats, growing, never
+ * shrinking): launches of one plan are ordered by the caller, and may interleave with every other
+ * family's. BSMR_ERR_NOT_PREPARED on a capturing stream until the prepare call ran; the capture
+ * stays intact. */
+int bsmr_attention_backward_panels(const bsmr_plan* plan, const void* dQ, const void* dK, const void* dV,
+                                   const float* dO, const float* dGO, const float* dLse, uint32_t D,
+                                   uint32_t Dv, int dtype, float scale, float* dGQ, float* dGK, float* dGV,
+                                   void* stream);
+int bsmr_attention_backward_panels_heads(const bsmr_plan* plan, uint32_t batches, uint32_t heads,
+                                         const bsmr_attention_operand* Q, const bsmr_attention_operand* K,
+                                         const bsmr_attention_operand* V, const bsmr_attention_operand* O,
+                                         const bsmr_attention_operand* GO, const float* dLse, uint32_t D,
+                                         uint32_t Dv, int dtype, float scale, const bsmr_attention_operand* GQ,
+                                         const bsmr_attention_operand* GK, const bsmr_attention_operand* GV,
+                                         void* stream);
+/* Build now what the first launch at (D, Dv) and that many slices would build: both sides' lists,
+ * delta and the scratches. Synchronous and idempotent. It builds the forward's panel lists when
+ * they do not exist (not the forward's scratch) and touches no other family's state;
+ * bsmr_plan_prepare_spmm and bsmr_plan_recolumn leave it alone. */
+int bsmr_plan_prepare_attention_backward_panels(const bsmr_plan* plan, uint32_t D, uint32_t Dv);
+int bsmr_plan_prepare_attention_backward_panels_heads(const bsmr_plan* plan, uint32_t D, uint32_t Dv, uint32_t slices);
+/* 1 when a launch would make no allocation, copy or synchronisation, else 0; no device call. */
+int bsmr_plan_attention_backward_panels_prepared(const bsmr_plan* plan, uint32_t D, uint32_t Dv);
+int bsmr_plan_attention_backward_panels_heads_prepared(const bsmr_plan* plan, uint32_t D, uint32_t Dv, uint32_t slices);
+typedef struct {
+    /* as bsmr_attention_panels_stats, per side: the rows side is the forward's lists */
+    uint32_t row_panels, row_items, row_steps, row_split_panels, row_partials, row_fill_permille;
+    uint32_t col_panels, col_items, col_steps, col_split_panels, col_partials, col_fill_permille;
+    uint64_t row_scratch_bytes, col_scratch_bytes, delta_bytes; /* plan-owned device memory */
+} bsmr_attention_backward_panels_stats;
+/* Zeros while the state is not built. */
+int bsmr_plan_attention_backward_panels_stats(const bsmr_plan* plan, bsmr_attention_backward_panels_stats* out);
+/* Host only: the CSR of the transposed pattern (trowptr: N + 1 entries, tcolidx: rowptr[M]; the
+ * rows of a column ascending). bsmr_attention_panel_lists(N, M, trowptr, tcolidx, NULL, 0, ...) is
+ * the columns side's lists. BSMR_ERR_INVALID for a null pointer, a rowptr not non-decreasing from 0
+ * or a column >= N. */
+int bsmr_attention_pattern_transpose(uint32_t M, uint32_t N, const uint32_t* rowptr, const uint32_t* colidx,
+                                     uint32_t* trowptr, uint32_t* tcolidx);
 
 /* Timing: run `iters` back-to-back SDDMMs on `stream`, timing each kernel with HIP events on
  * that stream (BSMR_ERR_UNSUPPORTED on a capturing stream). Outputs average ms per launch of the dense-tile kernel, the residual kernel and

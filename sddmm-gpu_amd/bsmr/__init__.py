@@ -190,6 +190,18 @@ class AttentionBackwardStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class AttentionBackwardPanelsStats(C.Structure):
+    """bsmr_attention_backward_panels_stats: both sides' panel lists of the MFMA attention backward
+    (the rows side is the forward's lists), how full their 16 x 32 masks are, and the plan-owned
+    scratch (zeros when not built)."""
+    _fields_ = [(f"{side}_{k}", C.c_uint32) for side in ("row", "col")
+                for k in ("panels", "items", "steps", "split_panels", "partials", "fill_permille")] + \
+               [("row_scratch_bytes", C.c_uint64), ("col_scratch_bytes", C.c_uint64), ("delta_bytes", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class AttentionOperand(C.Structure):
     """bsmr_attention_operand: one strided operand of the heads calls. Element [b][h][r][c] lies at
     ptr + (b batch + h head + r row + c) elements of the operand's dtype."""
@@ -253,6 +265,10 @@ EXPORTS = [
     "bsmr_plan_prepare_attention_panels_heads", "bsmr_plan_attention_panels_prepared",
     "bsmr_plan_attention_panels_heads_prepared", "bsmr_plan_attention_panels_stats",
     "bsmr_attention_panels_limits", "bsmr_attention_panel_lists",
+    "bsmr_attention_backward_panels", "bsmr_attention_backward_panels_heads",
+    "bsmr_plan_prepare_attention_backward_panels", "bsmr_plan_prepare_attention_backward_panels_heads",
+    "bsmr_plan_attention_backward_panels_prepared", "bsmr_plan_attention_backward_panels_heads_prepared",
+    "bsmr_plan_attention_backward_panels_stats", "bsmr_attention_pattern_transpose",
 ]
 
 # include/bsmr.h BSMR_ATTENTION_MAX_BATCHES, BSMR_ATTENTION_MAX_HEADS
@@ -411,6 +427,20 @@ def lib():
     u64p = C.POINTER(C.c_uint64)
     L.bsmr_attention_panel_lists.argtypes = [C.c_uint32, C.c_uint32, vp, vp, vp, C.c_uint32, vp, vp, u64p, vp, u64p, vp, u64p]
     L.bsmr_attention_panel_lists.restype = C.c_int
+    L.bsmr_attention_backward_panels.argtypes = L.bsmr_attention_backward.argtypes
+    L.bsmr_attention_backward_panels.restype = C.c_int
+    L.bsmr_attention_backward_panels_heads.argtypes = L.bsmr_attention_backward_heads.argtypes
+    L.bsmr_attention_backward_panels_heads.restype = C.c_int
+    for f in ("bsmr_plan_prepare_attention_backward_panels", "bsmr_plan_attention_backward_panels_prepared"):
+        getattr(L, f).argtypes = [vp, C.c_uint32, C.c_uint32]
+        getattr(L, f).restype = C.c_int
+    for f in ("bsmr_plan_prepare_attention_backward_panels_heads", "bsmr_plan_attention_backward_panels_heads_prepared"):
+        getattr(L, f).argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32]
+        getattr(L, f).restype = C.c_int
+    L.bsmr_plan_attention_backward_panels_stats.argtypes = [vp, C.POINTER(AttentionBackwardPanelsStats)]
+    L.bsmr_plan_attention_backward_panels_stats.restype = C.c_int
+    L.bsmr_attention_pattern_transpose.argtypes = [C.c_uint32, C.c_uint32, vp, vp, vp, vp]
+    L.bsmr_attention_pattern_transpose.restype = C.c_int
     L.bsmr_plan_check.argtypes = [vp, C.c_uint32, C.c_int, C.c_int]
     L.bsmr_plan_check.restype = C.c_int
     L.bsmr_check_rphm_arrays.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32] + [_u32p] * 2 + \
@@ -836,6 +866,47 @@ class Plan:
         _check(lib().bsmr_plan_attention_panels_stats(self.h, C.byref(s)), "bsmr_plan_attention_panels_stats")
         return s.as_dict()
 
+    def attention_backward_panels(self, dQ, dK, dV, dO, dGO, dLse, D, Dv, dGQ=0, dGK=0, dGV=0, scale=1.0, stream=0,
+                                  dtype=F16):
+        """bsmr_attention_backward_panels: Plan.attention_backward's GQ, GK and GV for fp16 / bf16
+        operands and D, Dv in {32, 64, 128}, on matrix instructions per 16-row panel (GQ) and per
+        16-column panel (GK, GV). Any output may be 0 (skipped); not all three. Opt-in."""
+        _check(lib().bsmr_attention_backward_panels(self.h, dQ, dK, dV, dO, dGO, dLse, D, Dv, dtype, scale,
+                                                    dGQ or None, dGK or None, dGV or None, stream or None),
+               "bsmr_attention_backward_panels")
+
+    def attention_backward_panels_heads(self, batches, heads, Q, K, V, O, GO, dLse, D, Dv, GQ=None, GK=None, GV=None,
+                                        scale=1.0, stream=0, dtype=F16):
+        """bsmr_attention_backward_panels_heads: attention_backward_panels over batches x heads slices
+        in one call; operands as in attention_backward_heads."""
+        ops = [AttentionOperand.of(x) for x in (Q, K, V, O, GO, GQ, GK, GV)]
+        ref = [None if o is None else C.byref(o) for o in ops]
+        _check(lib().bsmr_attention_backward_panels_heads(self.h, batches, heads, *ref[:5], dLse or None, D, Dv, dtype,
+                                                          scale, *ref[5:], stream or None),
+               "bsmr_attention_backward_panels_heads")
+
+    def prepare_attention_backward_panels(self, D, Dv):
+        """bsmr_plan_prepare_attention_backward_panels: both sides' panel lists, delta and scratch
+        for (D, Dv) now, so that the first attention_backward_panels launch can be captured."""
+        _check(lib().bsmr_plan_prepare_attention_backward_panels(self.h, D, Dv),
+               "bsmr_plan_prepare_attention_backward_panels")
+
+    def prepare_attention_backward_panels_heads(self, D, Dv, slices):
+        _check(lib().bsmr_plan_prepare_attention_backward_panels_heads(self.h, D, Dv, slices),
+               "bsmr_plan_prepare_attention_backward_panels_heads")
+
+    def attention_backward_panels_prepared(self, D, Dv):
+        return bool(lib().bsmr_plan_attention_backward_panels_prepared(self.h, D, Dv))
+
+    def attention_backward_panels_heads_prepared(self, D, Dv, slices):
+        return bool(lib().bsmr_plan_attention_backward_panels_heads_prepared(self.h, D, Dv, slices))
+
+    def attention_backward_panels_stats(self):
+        s = AttentionBackwardPanelsStats()
+        _check(lib().bsmr_plan_attention_backward_panels_stats(self.h, C.byref(s)),
+               "bsmr_plan_attention_backward_panels_stats")
+        return s.as_dict()
+
     def sddmm_backward(self, dG, dA, dB, K, dGA, dGB, stream=0, dtype=F32):
         """The gradients of P = sddmm(A, B) from dG = dL/dP (fp32, nnz): dGA (M x K fp32) =
         S(G) B and dGB (N x K fp32) = S(G)^T A. Either output may be 0: that side is skipped."""
@@ -980,6 +1051,18 @@ def attention_panel_lists(M, N, rowptr, colidx, order=()):
     _check(lib().bsmr_attention_panel_lists(*args, rows.ctypes.data, steps.ctypes.data, C.byref(n[0]), items.ctypes.data,
                                             C.byref(n[1]), reds.ctypes.data, C.byref(n[2])), "bsmr_attention_panel_lists")
     return rows, steps[:, :32], steps[:, 32:], items, reds
+
+
+def attention_pattern_transpose(M, N, rowptr, colidx):
+    """bsmr_attention_pattern_transpose (host only): (N, M, trowptr, tcolidx), the pattern of S^T;
+    attention_panel_lists(*that) is the columns side of Plan.attention_backward_panels."""
+    rp, ci = np.ascontiguousarray(rowptr, np.uint32), np.ascontiguousarray(colidx, np.uint32)
+    if len(rp) != M + 1 or len(ci) != int(rp[-1]):
+        raise ValueError("attention_pattern_transpose: rowptr needs M + 1 entries and colidx rowptr[M]")
+    trp, tci = np.zeros(N + 1, np.uint32), np.zeros(max(len(ci), 1), np.uint32)
+    _check(lib().bsmr_attention_pattern_transpose(M, N, rp.ctypes.data, ci.ctypes.data, trp.ctypes.data, tci.ctypes.data),
+           "bsmr_attention_pattern_transpose")
+    return N, M, trp, tci[:len(ci)]
 
 
 def attention_backward_limits():

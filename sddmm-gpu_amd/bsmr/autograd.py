@@ -312,8 +312,9 @@ class _AttentionFusedBwd(torch.autograd.Function):
     LSE; the backward is one Plan.attention_backward call."""
 
     @staticmethod
-    def forward(ctx, Q, K, V, plan, scale, want_lse, panels=False):
+    def forward(ctx, Q, K, V, plan, scale, want_lse, panels=False, bwd_panels=False):
         D, Dv, dtype = _validate_fused(plan, Q, K, V)
+        ctx.bwd_panels = bwd_panels
         O = torch.empty((plan.M, Dv), dtype=torch.float32, device=Q.device)
         lse = torch.empty(max(plan.M, 1), dtype=torch.float32, device=Q.device)
         (plan.attention_panels if panels else plan.attention)(
@@ -333,16 +334,16 @@ class _AttentionFusedBwd(torch.autograd.Function):
         plan = ctx.plan
         D, Dv, dtype = ctx.dims
         if not any(ctx.needs_input_grad[:3]):
-            return None, None, None, None, None, None, None
+            return None, None, None, None, None, None, None, None
         dO = grad.contiguous().float()
         out = [torch.empty(shape, dtype=torch.float32, device=Q.device) if need else None
                for need, shape in zip(ctx.needs_input_grad[:3], ((plan.M, D), (plan.N, D), (plan.N, Dv)))]
         ptr = [0 if t is None else t.data_ptr() for t in out]
-        plan.attention_backward(Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), dO.data_ptr(),
-                                _launchable(lse).data_ptr(), D, Dv, ptr[0], ptr[1], ptr[2], ctx.scale,
-                                stream=_stream(), dtype=dtype)
+        (plan.attention_backward_panels if ctx.bwd_panels else plan.attention_backward)(
+            Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), dO.data_ptr(), _launchable(lse).data_ptr(), D, Dv,
+            ptr[0], ptr[1], ptr[2], ctx.scale, stream=_stream(), dtype=dtype)
         gQ, gK, gV = (None if t is None else t.to(X.dtype) for t, X in zip(out, (Q, K, V)))
-        return gQ, gK, gV, None, None, None, None
+        return gQ, gK, gV, None, None, None, None, None
 
 
 def _validate_forward(who, forward, Q, D, Dv):
@@ -354,6 +355,14 @@ def _validate_forward(who, forward, Q, D, Dv):
         raise ValueError(f"{who}: forward = \"panels\" takes float16 / bfloat16 and D, Dv in 32, 64, 128, 256; got "
                          f"{Q.dtype}, D = {D}, Dv = {Dv}")
     return forward == "panels"
+
+
+def _validate_backward_panels(who, Q, D, Dv):
+    """backward = "panels" (Plan.attention_backward_panels): float16 / bfloat16 and D, Dv in {32, 64,
+    128}; ValueError before any launch otherwise."""
+    if Q.dtype == torch.float32 or D not in (32, 64, 128) or Dv not in (32, 64, 128):
+        raise ValueError(f"{who}: backward = \"panels\" takes float16 / bfloat16 and D, Dv in 32, 64, 128; got "
+                         f"{Q.dtype}, D = {D}, Dv = {Dv}")
 
 
 def attention_fused(plan, Q, K, V, scale=None, return_lse=False, backward="recompute", forward="gather"):
@@ -380,9 +389,14 @@ def attention_fused(plan, Q, K, V, scale=None, return_lse=False, backward="recom
     forward="panels": the forward is Plan.attention_panels (float16 / bfloat16, D and Dv in {32, 64,
     128, 256}; matrix instructions per 16-row panel, for patterns whose panel rows share columns)
     instead of Plan.attention; either backward takes it, the fused one from this forward's O and
-    LSE. The default "gather" is the path as it was; nothing chooses between them automatically."""
-    if backward not in ("recompute", "fused"):
-        raise ValueError(f"attention_fused: backward = {backward!r} must be \"recompute\" or \"fused\"")
+    LSE. The default "gather" is the path as it was; nothing chooses between them automatically.
+
+    backward="panels": what backward="fused" saves, and the backward is one
+    Plan.attention_backward_panels call (float16 / bfloat16, D and Dv in {32, 64, 128}; matrix
+    instructions per 16-row and per 16-column panel; GO, the weights and the score gradients are
+    rounded once to the operand dtype). ValueError before any launch for float32 or another D / Dv."""
+    if backward not in ("recompute", "fused", "panels"):
+        raise ValueError(f"attention_fused: backward = {backward!r} must be \"recompute\", \"fused\" or \"panels\"")
     if scale is None:
         if not isinstance(Q, torch.Tensor) or Q.dim() != 2 or Q.shape[1] == 0:
             raise ValueError("attention_fused: Q must be an (M, D) tensor with D > 0")
@@ -390,8 +404,11 @@ def attention_fused(plan, Q, K, V, scale=None, return_lse=False, backward="recom
     scale = _valid_scale("attention_fused", scale)
     D, Dv, _ = _validate_fused(plan, Q, K, V)
     panels = _validate_forward("attention_fused", forward, Q, D, Dv)
-    fn = _AttentionFusedBwd if backward == "fused" else _AttentionFused
-    return fn.apply(Q, K, V, plan, scale, bool(return_lse), panels)
+    if backward == "panels":
+        _validate_backward_panels("attention_fused", Q, D, Dv)
+    if backward == "recompute":
+        return _AttentionFused.apply(Q, K, V, plan, scale, bool(return_lse), panels)
+    return _AttentionFusedBwd.apply(Q, K, V, plan, scale, bool(return_lse), panels, backward == "panels")
 
 
 def _validate_heads(plan, Q, K, V):
@@ -450,8 +467,9 @@ class _AttentionFusedHeads(torch.autograd.Function):
     is one Plan.attention_backward_heads call."""
 
     @staticmethod
-    def forward(ctx, Q, K, V, plan, scale, want_lse, checked, panels=False):
+    def forward(ctx, Q, K, V, plan, scale, want_lse, checked, panels=False, bwd_panels=False):
         lead, D, Dv, dtype = checked  # (_validate_heads, run once by attention_fused_heads)
+        ctx.bwd_panels = bwd_panels
         B, H = (1,) * (2 - len(lead)) + lead
         O = _dense_like(Q, lead + (plan.M, Dv))
         lse = torch.empty(lead + (plan.M,), dtype=torch.float32, device=Q.device)
@@ -469,18 +487,18 @@ class _AttentionFusedHeads(torch.autograd.Function):
         plan = ctx.plan
         B, H, D, Dv, dtype = ctx.dims
         if not any(ctx.needs_input_grad[:3]):
-            return None, None, None, None, None, None, None, None
+            return None, None, None, None, None, None, None, None, None
         dO = grad if grad.dtype == torch.float32 else grad.float()
         if dO.stride(-1) != 1 or attention_layout_check(dO, B, H, plan.M, Dv, 4, False) is not None:
             dO = dO.contiguous()
         out = [_dense_like(X, X.shape) if need else None for need, X in zip(ctx.needs_input_grad[:3], (Q, K, V))]
-        plan.attention_backward_heads(B, H, Q, K, V, O, dO, lse.data_ptr(), D, Dv, out[0], out[1], out[2], ctx.scale,
-                                      stream=_stream(), dtype=dtype)
+        (plan.attention_backward_panels_heads if ctx.bwd_panels else plan.attention_backward_heads)(
+            B, H, Q, K, V, O, dO, lse.data_ptr(), D, Dv, out[0], out[1], out[2], ctx.scale, stream=_stream(), dtype=dtype)
         gQ, gK, gV = (None if t is None else t.to(X.dtype) for t, X in zip(out, (Q, K, V)))
-        return gQ, gK, gV, None, None, None, None, None
+        return gQ, gK, gV, None, None, None, None, None, None
 
 
-def attention_fused_heads(plan, Q, K, V, scale=None, return_lse=False, forward="gather"):
+def attention_fused_heads(plan, Q, K, V, scale=None, return_lse=False, forward="gather", backward="fused"):
     """attention_fused(..., backward="fused") over heads and an optional batch of one sparsity
     pattern: Q (H, M, D) or (B, H, M, D), K and V the same with N rows (V of width Dv). Returns O
     (..., M, Dv) float32 and, with return_lse=True, LSE (..., M) float32, non-differentiable.
@@ -499,7 +517,11 @@ def attention_fused_heads(plan, Q, K, V, scale=None, return_lse=False, forward="
     input's dtype; for an expanded input they are dense in standard order and torch's expand
     backward sums them. Slice (b, h) of every result equals, bit for bit, attention_fused(...,
     backward="fused") on contiguous copies of that slice. forward="panels" as in attention_fused:
-    one Plan.attention_panels_heads call instead of Plan.attention_heads."""
+    one Plan.attention_panels_heads call instead of Plan.attention_heads. backward="fused" (the
+    default) is the backward above; backward="panels" is one Plan.attention_backward_panels_heads call
+    instead, under attention_fused's rules for it; any other value raises ValueError."""
+    if backward not in ("fused", "panels"):
+        raise ValueError(f"attention_fused_heads: backward = {backward!r} must be \"fused\" or \"panels\"")
     if scale is None:
         if not isinstance(Q, torch.Tensor) or Q.dim() not in (3, 4) or Q.shape[-1] == 0:
             raise ValueError("attention_fused_heads: Q must be an (H, M, D) or (B, H, M, D) tensor with D > 0")
@@ -507,4 +529,6 @@ def attention_fused_heads(plan, Q, K, V, scale=None, return_lse=False, forward="
     scale = _valid_scale("attention_fused_heads", scale)
     checked = _validate_heads(plan, Q, K, V)
     panels = _validate_forward("attention_fused_heads", forward, Q, checked[1], checked[2])
-    return _AttentionFusedHeads.apply(Q, K, V, plan, scale, bool(return_lse), checked, panels)
+    if backward == "panels":
+        _validate_backward_panels("attention_fused_heads", Q, checked[1], checked[2])
+    return _AttentionFusedHeads.apply(Q, K, V, plan, scale, bool(return_lse), checked, panels, backward == "panels")

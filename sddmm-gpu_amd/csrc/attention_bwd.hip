@@ -539,24 +539,8 @@ int backward_launch(const char* who, const char* prep, const bsmr_plan* plan, u3
     cs.P1 = colScratch ? colScratch + static_cast<size_t>(colPartials) * D : nullptr;
     cs.sliceScratch = static_cast<u64>(colPartials) * (static_cast<u64>(D) + Dv);
 
-    if (p.M) {
-        const u32 epl = 16u / esz, perBlock = 4u * (64u / r.lanes);
-        const u32 grid = static_cast<u32>((static_cast<size_t>(p.M) + perBlock - 1) / perBlock);
-        DeltaArgs d{};
-        d.GO = r.GO;
-        d.O = attn_op_bytes(x.O, batches, heads, p.M, 4u);
-        d.delta = const_cast<float*>(r.delta);
-        d.heads = heads;
-        d.slices = slices;
-        d.M = p.M;
-        d.Dv = Dv;
-        d.L = r.lanes;
-        if (epl == 4)
-            hipLaunchKernelGGL(k_attention_bwd_delta<4>, dim3(grid, heads, batches), dim3(256), 0, s, d);
-        else
-            hipLaunchKernelGGL(k_attention_bwd_delta<8>, dim3(grid, heads, batches), dim3(256), 0, s, d);
-        BSMR_HIP(hipGetLastError());
-    }
+    BSMR_CHECK(attn_bwd_launch_delta(r.GO, attn_op_bytes(x.O, batches, heads, p.M, 4u), const_cast<float*>(r.delta), batches,
+                                     heads, p.M, D, Dv, esz, s));
     if (x.GQ) {
         const BwdFn fn = pick_side(dtype, true, rowBytes);
         if (r.nSegs) {
@@ -589,6 +573,31 @@ int backward_launch(const char* who, const char* prep, const bsmr_plan* plan, u3
 }
 
 }  // namespace
+
+// (shared with the panel backward, attention_bwd_panels.hip: one delta kernel, one launch rule)
+int attn_bwd_launch_delta(const AttnOpBytes& GO, const AttnOpBytes& O, float* delta, u32 batches, u32 heads, u32 M, u32 D,
+                          u32 Dv, u32 esz, hipStream_t s) {
+    if (!M) return BSMR_OK;
+    const u32 lanes = attn_lanes(std::max(D, Dv) * esz);
+    const u32 epl = 16u / esz, perBlock = 4u * (64u / lanes);
+    const u32 grid = static_cast<u32>((static_cast<size_t>(M) + perBlock - 1) / perBlock);
+    DeltaArgs d{};
+    d.GO = GO;
+    d.O = O;
+    d.delta = delta;
+    d.heads = heads;
+    d.slices = batches * heads;
+    d.M = M;
+    d.Dv = Dv;
+    d.L = lanes;
+    if (epl == 4)
+        hipLaunchKernelGGL(k_attention_bwd_delta<4>, dim3(grid, heads, batches), dim3(256), 0, s, d);
+    else
+        hipLaunchKernelGGL(k_attention_bwd_delta<8>, dim3(grid, heads, batches), dim3(256), 0, s, d);
+    BSMR_HIP(hipGetLastError());
+    return BSMR_OK;
+}
+
 }  // namespace bsmr
 
 using namespace bsmr;

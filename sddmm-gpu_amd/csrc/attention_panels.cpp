@@ -111,4 +111,38 @@ int attention_panel_lists(uint32_t M, uint32_t N, const uint32_t* rowptr, const 
     return 0;
 }
 
+int attention_pattern_transpose(uint32_t M, uint32_t N, const uint32_t* rowptr, const uint32_t* colidx,
+                                std::vector<uint32_t>& trowptr, std::vector<uint32_t>& tcolidx, std::string& err) {
+    trowptr.assign(static_cast<size_t>(N) + 1, 0u);
+    tcolidx.clear();
+    if (!rowptr || rowptr[0] != 0) {
+        err = "rowptr is null or rowptr[0] != 0";
+        return 1;
+    }
+    for (uint32_t r = 0; r < M; ++r)
+        if (rowptr[r + 1] < rowptr[r]) {
+            err = "rowptr is not non-decreasing at row " + std::to_string(r);
+            return 1;
+        }
+    const uint32_t nnz = rowptr[M];
+    if (nnz && !colidx) {
+        err = "null colidx";
+        return 1;
+    }
+    for (uint32_t e = 0; e < nnz; ++e) {
+        if (colidx[e] >= N) {
+            err = "column " + std::to_string(colidx[e]) + " is not below N";
+            return 1;
+        }
+        ++trowptr[colidx[e] + 1];
+    }
+    for (uint32_t j = 0; j < N; ++j) trowptr[j + 1] += trowptr[j];
+    // rows in ascending order: a column's rows come out ascending
+    tcolidx.resize(nnz);
+    std::vector<uint32_t> next(trowptr.begin(), trowptr.end() - 1);
+    for (uint32_t r = 0; r < M; ++r)
+        for (uint32_t e = rowptr[r]; e < rowptr[r + 1]; ++e) tcolidx[next[colidx[e]]++] = r;
+    return 0;
+}
+
 }  // namespace bsmr

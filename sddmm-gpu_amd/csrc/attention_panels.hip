@@ -57,19 +57,12 @@
 #include "attention_common.hpp"
 #include "attention_layout.hpp"
 #include "attention_panels.hpp"
+#include "panel_mfma.hpp"
 #include "plan.hpp"
 #include "seg_walk.hpp"  // exp2_hw
 
 namespace bsmr {
 namespace {
-
-constexpr u32 PANEL_WAVES = 4;  // waves (items) per workgroup
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 h16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 b16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 b16x8 __attribute__((ext_vector_type(8)));
 
 struct PanelArgs {
     const PanelItem* items;
@@ -87,40 +80,12 @@ struct PanelArgs {
 __device__ __forceinline__ float shift_of(float m) { return m == -INFINITY ? 0.f : m; }
 __device__ __forceinline__ float inverse_of(float s) { return s == 0.f ? 0.f : 1.0f / s; }
 
-template <int DT>
-__device__ __forceinline__ f32x4 mfma32(const uint4& a, const uint4& b, const f32x4 c) {
-    if constexpr (DT == BSMR_F16)
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h16x8, a), __builtin_bit_cast(h16x8, b), c, 0, 0, 0);
-    else
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(b16x8, a), __builtin_bit_cast(b16x8, b), c, 0, 0, 0);
-}
-
-// two weights rounded to the operand type (nearest even), lo in the low half
-template <int DT>
-__device__ __forceinline__ u32 pack2(float lo, float hi) {
-    if constexpr (DT == BSMR_F16) {
-        const h16x2 h = {static_cast<_Float16>(lo), static_cast<_Float16>(hi)};
-        return __builtin_bit_cast(u32, h);
-    } else {
-        const b16x2 h = {static_cast<__bf16>(lo), static_cast<__bf16>(hi)};
-        return __builtin_bit_cast(u32, h);
-    }
-}
-
-__device__ __forceinline__ uint4 load16(const char* p) { return *reinterpret_cast<const uint4*>(p); }
-
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 template <int DT, int D, int DV>
 __global__ __launch_bounds__(PANEL_WAVES * 64) __attribute__((amdgpu_waves_per_eu(2)))
 void k_attention_panels(const PanelArgs a) {
     constexpr int KS = D / 32;                // k-steps of a score tile
     constexpr int NP = DV / 32;               // pairs of output tiles
-    constexpr u32 VROW = 2u * DV + 16u;       // bytes between staged V rows
+    constexpr u32 VROW = staged_row_bytes(DV);  // bytes between staged V rows
     constexpr u32 CPR = DV / 8;               // 16-byte chunks per V row
     constexpr int VLOADS = DV / 16;           // chunks per lane and step (32 rows)
     constexpr int VBATCH = VLOADS < 8 ? VLOADS : 8;
@@ -216,24 +181,15 @@ void k_attention_panels(const PanelArgs a) {
             ts += t[j];
         }
         l = l * f + ts;
-        const uint4 pb = make_uint4(pack2<DT>(t[0], t[1]), pack2<DT>(t[2], t[3]), pack2<DT>(t[4], t[5]), pack2<DT>(t[6], t[7]));
+        const uint4 pb = pack8<DT>(t);
 #pragma unroll
         for (int n = 0; n < 2 * NP; ++n) acc[n] *= f;
 
         wave_lds_sync();
 #pragma unroll
         for (int n = 0; n < NP; ++n) {
-            u32 w[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const u32 cc = (j < 4 ? 4u * g + j : 16u + 4u * g + (j - 4));
-                w[j] = *reinterpret_cast<const u32*>(vl + cc * VROW + (32u * n + 2u * r) * 2u);
-            }
             uint4 even, odd;
-            even.x = __builtin_amdgcn_perm(w[1], w[0], 0x05040100u), odd.x = __builtin_amdgcn_perm(w[1], w[0], 0x07060302u);
-            even.y = __builtin_amdgcn_perm(w[3], w[2], 0x05040100u), odd.y = __builtin_amdgcn_perm(w[3], w[2], 0x07060302u);
-            even.z = __builtin_amdgcn_perm(w[5], w[4], 0x05040100u), odd.z = __builtin_amdgcn_perm(w[5], w[4], 0x07060302u);
-            even.w = __builtin_amdgcn_perm(w[7], w[6], 0x05040100u), odd.w = __builtin_amdgcn_perm(w[7], w[6], 0x07060302u);
+            staged_pair<VROW>(vl, n, r, g, even, odd);
             acc[2 * n] = mfma32<DT>(even, pb, acc[2 * n]);
             acc[2 * n + 1] = mfma32<DT>(odd, pb, acc[2 * n + 1]);
         }
@@ -351,43 +307,12 @@ bool panels_ready(const Plan::AttentionPanelsState& S, u32 Dv, u32 slices) {
     return S.built && S.scratch.size() >= panels_scratch_floats(S, Dv, slices);
 }
 
-// build the lists (once) and size the per-slice scratch for (Dv, slices): it grows and never
-// shrinks; layout_mu held. Synchronous on the plan's stream.
+// build the lists (once, attn_panels_build_lists) and size the per-slice scratch for (Dv, slices): it
+// grows and never shrinks; layout_mu held. Synchronous on the plan's stream.
 int build_panels(const Plan& p, u32 Dv, u32 slices, const char* who) {
-    Plan::AttentionPanelsState& S = p.attention_panels;
-    const hipStream_t s = p.stream;
-    if (!S.built) {
-        std::vector<u32> hrp, hci, hrows;
-        BSMR_CHECK(p.rowptr.download(hrp, s));
-        BSMR_CHECK(p.colidx.download(hci, s));
-        BSMR_CHECK(p.rows.download(hrows, s));
-        hrows.resize(std::min<size_t>(hrows.size(), p.R));
-        PanelLists L;
-        std::string err;
-        // (the rows the plan's order does not name, its empty ones, get trailing panels of 0 steps; the
-        // lists would compute them from their entries all the same)
-        if (const int st = attention_panel_lists(p.M, p.N, hrp.data(), hci.data(), hrows.data(), static_cast<u32>(hrows.size()), L, err)) {
-            set_error(std::string(who) + ": " + err);
-            return st == 2 ? BSMR_ERR_UNSUPPORTED : BSMR_ERR_INVALID;  // 2: past the lists' capacity
-        }
-        if (L.nItems > (1ull << 31)) {
-            set_error(std::string(who) + ": more than 2^31 items");
-            return BSMR_ERR_UNSUPPORTED;
-        }
-        BSMR_CHECK(S.rows.upload(L.rows.data(), L.rows.size(), s));
-        BSMR_CHECK(S.steps.upload(L.steps.data(), L.steps.size(), s));
-        BSMR_CHECK(S.items.upload(L.items.data(), L.items.size(), s));
-        BSMR_CHECK(S.reds.upload(L.reds.data(), L.reds.size(), s));
-        BSMR_HIP(hipStreamSynchronize(s));
-        S.nItems = static_cast<u32>(L.nItems);
-        S.nSteps = static_cast<u32>(L.nSteps);
-        S.nReds = static_cast<u32>(L.reds.size());
-        S.panels = L.panels;
-        S.splitPanels = L.splitPanels;
-        S.partials = L.partials;
-        S.built = true;
-    }
-    return S.scratch.grow(panels_scratch_floats(S, Dv, slices));
+    BSMR_CHECK(attn_panels_build_lists(p, who));
+    const Plan::AttentionPanelsState& S = p.attention_panels;
+    return p.attention_panels.scratch.grow(panels_scratch_floats(S, Dv, slices));
 }
 
 // the launches of bsmr_attention_panels and bsmr_attention_panels_heads, arguments already validated
@@ -458,6 +383,46 @@ int panels_prepare_args(const char* who, const bsmr_plan* plan, u32 D, u32 Dv, u
 }
 
 }  // namespace
+
+// the panel lists of the plan's rows (once): the panel backward's rows side launches over the same
+// lists and builds them through this when no forward has; layout_mu held
+int attn_panels_build_lists(const Plan& p, const char* who) {
+    Plan::AttentionPanelsState& S = p.attention_panels;
+    const hipStream_t s = p.stream;
+    if (!S.built) {
+        std::vector<u32> hrp, hci, hrows;
+        BSMR_CHECK(p.rowptr.download(hrp, s));
+        BSMR_CHECK(p.colidx.download(hci, s));
+        BSMR_CHECK(p.rows.download(hrows, s));
+        hrows.resize(std::min<size_t>(hrows.size(), p.R));
+        PanelLists L;
+        std::string err;
+        // (the rows the plan's order does not name, its empty ones, get trailing panels of 0 steps; the
+        // lists would compute them from their entries all the same)
+        if (const int st = attention_panel_lists(p.M, p.N, hrp.data(), hci.data(), hrows.data(), static_cast<u32>(hrows.size()), L, err)) {
+            set_error(std::string(who) + ": " + err);
+            return st == 2 ? BSMR_ERR_UNSUPPORTED : BSMR_ERR_INVALID;  // 2: past the lists' capacity
+        }
+        if (L.nItems > (1ull << 31)) {
+            set_error(std::string(who) + ": more than 2^31 items");
+            return BSMR_ERR_UNSUPPORTED;
+        }
+        BSMR_CHECK(S.rows.upload(L.rows.data(), L.rows.size(), s));
+        BSMR_CHECK(S.steps.upload(L.steps.data(), L.steps.size(), s));
+        BSMR_CHECK(S.items.upload(L.items.data(), L.items.size(), s));
+        BSMR_CHECK(S.reds.upload(L.reds.data(), L.reds.size(), s));
+        BSMR_HIP(hipStreamSynchronize(s));
+        S.nItems = static_cast<u32>(L.nItems);
+        S.nSteps = static_cast<u32>(L.nSteps);
+        S.nReds = static_cast<u32>(L.reds.size());
+        S.panels = L.panels;
+        S.splitPanels = L.splitPanels;
+        S.partials = L.partials;
+        S.built = true;
+    }
+    return BSMR_OK;
+}
+
 }  // namespace bsmr
 
 using namespace bsmr;

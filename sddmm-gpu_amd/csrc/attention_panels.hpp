@@ -59,6 +59,13 @@ struct PanelLists {
 int attention_panel_lists(uint32_t M, uint32_t N, const uint32_t* rowptr, const uint32_t* colidx, const uint32_t* order,
                           uint32_t norder, PanelLists& out, std::string& err);
 
+// The pattern of S^T as a CSR of N rows (trowptr: N + 1 entries; tcolidx: row j holds the rows that
+// store column j, ascending): the panel backward's columns side is attention_panel_lists on it with
+// M and N swapped and an empty order, so a column panel is 16 consecutive columns. 0, or 1 with
+// `err` set for a rowptr not ascending from 0 or a column >= N.
+int attention_pattern_transpose(uint32_t M, uint32_t N, const uint32_t* rowptr, const uint32_t* colidx,
+                                std::vector<uint32_t>& trowptr, std::vector<uint32_t>& tcolidx, std::string& err);
+
 // 1000 nnz / (16 x 32 x steps): how full the steps' masks are (0 without steps)
 inline uint32_t panel_fill_permille(uint64_t nnz, uint64_t steps) {
     return steps ? static_cast<uint32_t>(1000u * nnz / (PANEL_ROWS * PANEL_STEP_COLS * steps)) : 0u;

@@ -572,6 +572,23 @@ extern "C" int bsmr_attention_panel_lists(uint32_t M, uint32_t N, const uint32_t
     return BSMR_OK;
 }
 
+extern "C" int bsmr_attention_pattern_transpose(uint32_t M, uint32_t N, const uint32_t* rowptr, const uint32_t* colidx,
+                                                uint32_t* trowptr, uint32_t* tcolidx) {
+    if (!rowptr || !trowptr || (M && rowptr[M] && !tcolidx)) {
+        set_error("bsmr_attention_pattern_transpose: null argument");
+        return BSMR_ERR_INVALID;
+    }
+    std::vector<uint32_t> trp, tci;
+    std::string err;
+    if (attention_pattern_transpose(M, N, rowptr, colidx, trp, tci, err)) {
+        set_error("bsmr_attention_pattern_transpose: " + err);
+        return BSMR_ERR_INVALID;
+    }
+    std::copy(trp.begin(), trp.end(), trowptr);
+    std::copy(tci.begin(), tci.end(), tcolidx);
+    return BSMR_OK;
+}
+
 extern "C" void bsmr_attention_panels_limits(uint32_t* step_cols, uint32_t* item_steps) {
     if (step_cols) *step_cols = PANEL_STEP_COLS;
     if (item_steps) *item_steps = PANEL_ITEM_STEPS;

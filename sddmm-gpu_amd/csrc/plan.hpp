@@ -329,6 +329,27 @@ struct Plan {
     };
     mutable AttentionBwdState attention_bwd;
 
+    // fused sparse attention backward on matrix instructions (attention_bwd_panels.hip;
+    // bsmr_attention_backward_panels). The rows side runs over AttentionPanelsState's rows / steps /
+    // items / reds (built through attn_panels_build_lists when no forward has built them; never a
+    // second copy); the columns side over the same kind of lists of the transposed pattern: panels
+    // of 16 consecutive columns in ascending index, steps of 32 union rows. Per slice: M floats of
+    // delta, rowPartials x 16 x D floats of the split row panels, and colPartials x 16 x D followed
+    // by colPartials x 16 x Dv of the split column panels. Built on first use or by
+    // bsmr_plan_prepare_attention_backward_panels, under layout_mu; the buffers hold what the
+    // largest (D, Dv, slices) so far needs and never shrink. It reads no state of the gather
+    // forward, the gather backward or SpMM, and neither bsmr_plan_prepare_spmm nor build_columns
+    // touches it
+    struct AttentionBwdPanelsState {
+        bool built = false;
+        u32 colItems = 0, colReds = 0, colSteps = 0, colPanels = 0, colSplit = 0, colPartials = 0;
+        DevBuf<PanelStep> csteps;
+        DevBuf<PanelItem> citems;
+        DevBuf<PanelRed> creds;
+        DevBuf<float> delta, rowScratch, colScratch;
+    };
+    mutable AttentionBwdPanelsState attention_bwd_panels;
+
     int build_rows(const u32* h_rowptr, const u32* h_col);
     int build_columns();
     ~Plan() {

@@ -66,6 +66,12 @@ form can be taken from another build in the same session, for A/B runs.
 
     python3 tools/attention_bench.py --forward panels [--cases C2,C5,C3] [--dtype f16|bf16] [--d 64]
 
+With --backward panels [--cases C2,C5,C3] [--dtype f16|bf16] [--d 64|128] the tool times one
+Plan.attention_backward_panels against one Plan.attention_backward on the same
+plan and tensors by the same protocol and prints both sides' panel stats (fill_permille, items, split
+panels), graph_us of both, their ratio, the byte floor counted as section 18 counts it, and the
+largest difference of each gradient.
+
 With --forward panels the tool times one Plan.attention_panels (the panel form on matrix
 instructions) against one Plan.attention (the gather form) on the same plan
 and the same fp16 / bf16 tensors, D = Dv = --d, by the same protocol (graphs of `steps`, median of
@@ -96,6 +102,7 @@ def main():
     ap.add_argument("--batches", type=int, default=0)
     ap.add_argument("--dtype", default="f32", choices=["f32", "f16", "bf16"])
     ap.add_argument("--forward", default="gather", choices=["gather", "panels"])
+    ap.add_argument("--backward", default="gather", choices=["gather", "panels"])
     ap.add_argument("--layout", default="bmhd", choices=["bmhd", "bhmd"])
     ap.add_argument("--baseline-only", action="store_true")
     ap.add_argument("--order-probe", action="store_true")
@@ -103,8 +110,10 @@ def main():
     args = ap.parse_args()
     if args.forward == "panels" and args.dtype == "f32":
         raise SystemExit("--forward panels takes --dtype f16 or bf16")
-    if args.forward != "panels" and args.dtype == "bf16":
-        raise SystemExit("--dtype bf16 is for --forward panels only")
+    if args.backward == "panels" and (args.dtype == "f32" or args.d not in (32, 64, 128)):
+        raise SystemExit("--backward panels takes --dtype f16 or bf16 and --d 32, 64 or 128")
+    if "panels" not in (args.forward, args.backward) and args.dtype == "bf16":
+        raise SystemExit("--dtype bf16 is for --forward panels and --backward panels only")
     if args.package:
         sys.path.insert(0, os.path.abspath(args.package))
     import numpy as np
@@ -155,6 +164,9 @@ def main():
 
     D = args.d
     scale = D ** -0.5
+    if args.backward == "panels":
+        panels_bwd_bench(args, torch, dev, graph_of, alternate)
+        return
     if args.forward == "panels":
         panels_bench(args, torch, dev, graph_of, alternate)
         return
@@ -343,6 +355,48 @@ def panels_bench(args, torch, dev, graph_of, alternate):
                 "graph_us": graph_us, "panels_over_gather": round(graph_us["panels"] / graph_us["gather"], 3),
                 "floor_us": round(floor, 3), "floor_fraction": round(floor / graph_us["panels"], 3),
                 "max_abs_diff": (out["panels"][0] - out["gather"][0]).abs().max().item()}
+        print(json.dumps(line), flush=True)
+
+
+def panels_bwd_bench(args, torch, dev, graph_of, alternate):
+    """The --backward panels mode (module docstring)."""
+    from bsmr import BF16, F16, Plan, make_data, synth
+
+    D = args.d
+    scale = D ** -0.5
+    tdt, dtype = (torch.bfloat16, BF16) if args.dtype == "bf16" else (torch.float16, F16)
+    p = lambda t: t.data_ptr()  # noqa: E731
+    patterns = {"C2": synth.nips_like, "C3": synth.cop20k_like, "C5": lambda: synth.dlmc_like("block")}
+    for case in args.cases.split(","):
+        if case not in patterns:
+            raise SystemExit(f"unknown case {case}")
+        M, N, rp, ci = patterns[case]()
+        plan = Plan(M, N, rp, ci, alpha=0.3, delta=0.3)
+        plan.prepare_attention_panels(D, D)
+        plan.prepare_attention_backward(D, D)
+        plan.prepare_attention_backward_panels(D, D)
+        data = lambda rows: (torch.from_numpy(make_data(rows * D)).to(dev) - 1.0).reshape(rows, D)  # noqa: E731
+        Q, K, V, GO = data(M).to(tdt), data(N).to(tdt), data(N).to(tdt), data(M)
+        O, L = torch.zeros(M, D, device=dev), torch.zeros(M, device=dev)
+        s0 = torch.cuda.current_stream().cuda_stream
+        plan.attention_panels(p(Q), p(K), p(V), D, D, p(O), p(L), scale, stream=s0, dtype=dtype)
+        torch.cuda.synchronize()
+        out = {k: [torch.zeros(r, D, device=dev) for r in (M, N, N)] for k in ("gather", "panels")}
+        call = {"gather": plan.attention_backward, "panels": plan.attention_backward_panels}
+        ours = {k: (lambda s, k=k: call[k](p(Q), p(K), p(V), p(O), p(GO), p(L), D, D, *(p(t) for t in out[k]), scale,
+                                           stream=s, dtype=dtype)) for k in call}
+        graphs = {k: graph_of(f) for k, f in ours.items()}
+        graph_us = alternate({k: g.replay for k, g in graphs.items()})
+        st = plan.attention_backward_panels_stats()
+        # as section 18 counts: every operand once, per step its list record and the 32 rows it brings in
+        rows_side = 2 * D * M + 4 * D * M + 8 * M + 4 * D * M + st["row_steps"] * (192 + 2 * 2 * D * 32)
+        cols_side = 2 * 2 * D * N + 2 * 4 * D * N + st["col_steps"] * (192 + (2 * D + 4 * D + 8) * 32)
+        floor = (8 * D * M + 4 * M + rows_side + cols_side) / HBM_BYTES_PER_S * 1e6
+        line = {"case": case, "mode": "backward_panels", "M": M, "N": N, "nnz": len(ci), "D": D, "dtype": args.dtype,
+                "steps": args.steps, "rounds": args.rounds, "attention_backward_panels_stats": st, "graph_us": graph_us,
+                "panels_over_gather": round(graph_us["panels"] / graph_us["gather"], 3), "floor_us": round(floor, 3),
+                "floor_fraction": round(floor / graph_us["panels"], 3),
+                "max_abs_diff": {n: (a - b).abs().max().item() for n, a, b in zip(("GQ", "GK", "GV"), out["panels"], out["gather"])}}
         print(json.dumps(line), flush=True)
 
 

@@ -58,7 +58,9 @@ extern "C" {
                               bsmr_attention_panel_lists (the panel MFMA forward: new declarations
                               only); bsmr_attention_backward_panels, its heads form, their prepare /
                               prepared / stats calls and bsmr_attention_pattern_transpose (the panel
-                              MFMA backward: new declarations only) */
+                              MFMA backward: new declarations only); bsmr_attention_panels_kv8, its
+                              heads form and the bsmr_kv_dtype enum: the panel MFMA forward over e4m3 K / V,
+                              new declarations only */
 
 typedef enum {
     BSMR_OK = 0,
@@ -825,6 +827,39 @@ int bsmr_attention_panel_lists(uint32_t M, uint32_t N, const uint32_t* rowptr, c
                                const uint32_t* order, uint32_t norder, uint32_t* rows,
                                bsmr_attention_panel_step* steps, uint64_t* nsteps, bsmr_attention_panel_item* items,
                                uint64_t* nitems, bsmr_attention_panel_red* reds, uint64_t* nreds);
+
+/* ------------------------------ the panel forward over an fp8 (e4m3) K / V cache ---- */
+/* bsmr_attention_panels for a quantised K / V cache (forward only, there is no
+ * backward of this path): Q in `dtype` (BSMR_F16 or BSMR_BF16), K8 (N x D) and V8 (N x Dv) one
+ * byte per element in the OCP e4m3 format (torch.float8_e4m3fn; NaN 0x7F / 0xFF, no inf; not the
+ * fnuz format), with one positive finite scale each:
+ *   O = v_scale softmax_row(scale k_scale S .* (Q K8^T)) V8,  LSE of that softmax.
+ * The bytes are widened to `dtype` in registers, exactly, right before the matrix instructions: the
+ * result is that of bsmr_attention_panels on the widened tensors with scale x k_scale, times
+ * v_scale, within the bounds of §20, from half the K / V bytes. The score scale is the exact
+ * double product scale x k_scale, held to bsmr_attention's scale rule and rounded once; v_scale
+ * multiplies 1 / l once (a rounded product) before the product with the accumulator.
+ * D and Dv are each one of 64, 128, 256. BSMR_ERR_UNSUPPORTED: another dtype (BSMR_F32 too), D, Dv
+ * or kv_dtype. BSMR_ERR_INVALID: k_scale or v_scale not finite or not > 0, scale x k_scale (or its
+ * product with log2(e)) not finite, and bsmr_attention_panels' pointer rules (dK8 and dV8 16-byte
+ * aligned). The plan state is bsmr_attention_panels': bsmr_plan_prepare_attention_panels(_heads)
+ * prepares this call too, and an unprepared call on a capturing stream is BSMR_ERR_NOT_PREPARED.
+ * One k_scale and one v_scale hold for the whole call (per-tensor scaling): per-head or per-row
+ * scales and the e5m2 format are out of scope.
+ * NaN: a NaN byte of a K row reaches exactly the rows that store the column; one of a V row the
+ * rows of the panels whose column union holds the column (bsmr_attention_panels' rule). */
+typedef enum { BSMR_KV_F8_E4M3 = 0 } bsmr_kv_dtype;
+int bsmr_attention_panels_kv8(const bsmr_plan* plan, const void* dQ, const void* dK8, const void* dV8, uint32_t D,
+                              uint32_t Dv, int dtype, int kv_dtype, float scale, float k_scale, float v_scale, float* dO,
+                              float* dLse, void* stream);
+/* The same over batches x heads slices in one call, as bsmr_attention_panels_heads: K8 and V8 follow
+ * the layout rules with elements of one byte (strides in bytes, multiples of 16; 16-byte aligned
+ * pointers); every slice equals the single-slice call bit for bit. */
+int bsmr_attention_panels_kv8_heads(const bsmr_plan* plan, uint32_t batches, uint32_t heads,
+                                    const bsmr_attention_operand* Q, const bsmr_attention_operand* K8,
+                                    const bsmr_attention_operand* V8, uint32_t D, uint32_t Dv, int dtype, int kv_dtype,
+                                    float scale, float k_scale, float v_scale, const bsmr_attention_operand* O,
+                                    float* dLse, void* stream);
 
 /* -------------------- fused sparse attention backward on matrix instructions, per panel ---- */
 /* The gradients of bsmr_attention_backward, for fp16 / bf16 operands, on

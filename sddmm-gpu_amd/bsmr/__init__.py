@@ -231,6 +231,7 @@ SOFTMAX_WAVE = 0x100
 SOFTMAX_BLOCK = 0x200
 
 ABI_VERSION = 13  # include/bsmr.h BSMR_ABI_VERSION
+KV_F8_E4M3 = 0  # bsmr_kv_dtype: the K / V format of Plan.attention_panels_kv8
 
 # every symbol include/bsmr.h declares (tests check the library exports all of them)
 EXPORTS = [
@@ -269,6 +270,7 @@ EXPORTS = [
     "bsmr_plan_prepare_attention_backward_panels", "bsmr_plan_prepare_attention_backward_panels_heads",
     "bsmr_plan_attention_backward_panels_prepared", "bsmr_plan_attention_backward_panels_heads_prepared",
     "bsmr_plan_attention_backward_panels_stats", "bsmr_attention_pattern_transpose",
+    "bsmr_attention_panels_kv8", "bsmr_attention_panels_kv8_heads",
 ]
 
 # include/bsmr.h BSMR_ATTENTION_MAX_BATCHES, BSMR_ATTENTION_MAX_HEADS
@@ -424,6 +426,12 @@ def lib():
     L.bsmr_plan_attention_panels_stats.restype = C.c_int
     L.bsmr_attention_panels_limits.argtypes = [C.POINTER(C.c_uint32)] * 2
     L.bsmr_attention_panels_limits.restype = None
+    L.bsmr_attention_panels_kv8.argtypes = [vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_float, C.c_float,
+                                            C.c_float, vp, vp, vp]
+    L.bsmr_attention_panels_kv8.restype = C.c_int
+    L.bsmr_attention_panels_kv8_heads.argtypes = [vp, C.c_uint32, C.c_uint32, op, op, op, C.c_uint32, C.c_uint32, C.c_int,
+                                                  C.c_int, C.c_float, C.c_float, C.c_float, op, vp, vp]
+    L.bsmr_attention_panels_kv8_heads.restype = C.c_int
     u64p = C.POINTER(C.c_uint64)
     L.bsmr_attention_panel_lists.argtypes = [C.c_uint32, C.c_uint32, vp, vp, vp, C.c_uint32, vp, vp, u64p, vp, u64p, vp, u64p]
     L.bsmr_attention_panel_lists.restype = C.c_int
@@ -845,6 +853,26 @@ class Plan:
         ref = [None if o is None else C.byref(o) for o in ops]
         _check(lib().bsmr_attention_panels_heads(self.h, batches, heads, ref[0], ref[1], ref[2], D, Dv, dtype, scale,
                                                  ref[3], dLse or None, stream or None), "bsmr_attention_panels_heads")
+
+    def attention_panels_kv8(self, dQ, dK8, dV8, D, Dv, dO, dLse=0, scale=1.0, k_scale=1.0, v_scale=1.0, stream=0,
+                             dtype=F16):
+        """bsmr_attention_panels_kv8: attention_panels over an fp8 K / V cache. dQ (M x D) fp16 / bf16;
+        dK8 (N x D) and dV8 (N x Dv) OCP e4m3 bytes (torch.float8_e4m3fn) with one scale each:
+        O = v_scale softmax(scale k_scale S .* (Q K8^T)) V8. D, Dv in {64, 128, 256}; forward only;
+        prepare_attention_panels prepares it."""
+        _check(lib().bsmr_attention_panels_kv8(self.h, dQ, dK8, dV8, D, Dv, dtype, KV_F8_E4M3, scale, k_scale, v_scale, dO,
+                                               dLse or None, stream or None), "bsmr_attention_panels_kv8")
+
+    def attention_panels_kv8_heads(self, batches, heads, Q, K8, V8, D, Dv, O, dLse=0, scale=1.0, k_scale=1.0, v_scale=1.0,
+                                   stream=0, dtype=F16):
+        """bsmr_attention_panels_kv8_heads: attention_panels_kv8 over batches x heads slices in one
+        call; operands as in attention_heads (K8 and V8 with strides in bytes), one k_scale and one
+        v_scale for all slices."""
+        ops = [AttentionOperand.of(x) for x in (Q, K8, V8, O)]
+        ref = [None if o is None else C.byref(o) for o in ops]
+        _check(lib().bsmr_attention_panels_kv8_heads(self.h, batches, heads, ref[0], ref[1], ref[2], D, Dv, dtype,
+                                                     KV_F8_E4M3, scale, k_scale, v_scale, ref[3], dLse or None,
+                                                     stream or None), "bsmr_attention_panels_kv8_heads")
 
     def prepare_attention_panels(self, D, Dv):
         """bsmr_plan_prepare_attention_panels: the panel lists and the scratch of the split panels

@@ -17,6 +17,9 @@ and, over the same plan, the row softmax, the SpMM and their composition into sp
                                      (B, H, M, D) operands with any strides (views of a
                                      (B, M, H D) projection, an expanded K / V) in one
                                      Plan.attention_heads call and one Plan.attention_backward_heads call
+    quantize_kv(K, V)                (K8, V8, k_scale, v_scale): per-tensor e4m3 quantisation (torch ops)
+    attention_fused_kv8(plan, Q, K8, V8, k_scale, v_scale)   the panel forward over that fp8 cache
+                                     (Plan.attention_panels_kv8_heads); inference only, no backward
 
 Every direction is the library's HIP kernels on torch.cuda.current_stream(); torch only owns the
 tensors. Importing this module imports torch (`import bsmr` alone does not).
@@ -532,3 +535,76 @@ def attention_fused_heads(plan, Q, K, V, scale=None, return_lse=False, forward="
     if backward == "panels":
         _validate_backward_panels("attention_fused_heads", Q, checked[1], checked[2])
     return _AttentionFusedHeads.apply(Q, K, V, plan, scale, bool(return_lse), checked, panels, backward == "panels")
+
+
+E4M3_MAX = 448.0  # the largest finite torch.float8_e4m3fn value
+
+
+def quantize_kv(K, V):
+    """(K8, V8, k_scale, v_scale): K and V as torch.float8_e4m3fn with one scale per tensor,
+    scale = amax / 448 (1.0 for a tensor of zeros), so that X is about X8 * scale and the largest
+    magnitude maps to +-448. The scales are Python floats that float32 holds exactly. Torch ops only:
+    CPU and device tensors alike; shapes and strides are kept as torch's elementwise ops keep them."""
+    out = []
+    for X in (K, V):
+        amax = X.detach().abs().max().float() if X.numel() else torch.zeros(())
+        s = float(amax / E4M3_MAX) if float(amax) > 0.0 else 1.0
+        out.append(((X.detach().float() / s).clamp(-E4M3_MAX, E4M3_MAX).to(torch.float8_e4m3fn), s))
+    return out[0][0], out[1][0], out[0][1], out[1][1]
+
+
+def attention_fused_kv8(plan, Q, K8, V8, k_scale, v_scale, scale=None, return_lse=False):
+    """O = v_scale softmax(scale k_scale S .* (Q K8^T)) V8 in float32 from one
+    Plan.attention_panels_kv8_heads call, and with return_lse=True also LSE; both non-differentiable.
+    Q is (M, D), (H, M, D) or (B, H, M, D) float16 / bfloat16; K8 and V8 are torch.float8_e4m3fn with
+    N rows and the same leading dimensions (quantize_kv makes them), D and Dv in {64, 128, 256}.
+    Strided views are taken as attention_fused_heads takes them (a transposed view of a (B, M, H D)
+    projection, one K8 / V8 expanded over the heads), under the same layout rules with one-byte
+    elements for K8 and V8. k_scale and v_scale are per tensor: one pair for every slice.
+
+    This path is inference only: no backward exists for it, so a Q that requires grad while grad
+    mode is on raises ValueError (wrap the call in torch.no_grad(), or use attention_fused_heads on
+    widened tensors to train). ValueError, before any launch, also for K8 / V8 of another dtype, a Q
+    that is not float16 / bfloat16, wrong shapes, scales that are not finite and > 0 or a layout the
+    library refuses."""
+    who = "attention_fused_kv8"
+    for name, X in (("Q", Q), ("K8", K8), ("V8", V8)):
+        if not isinstance(X, torch.Tensor) or not X.is_cuda:
+            raise ValueError(f"{who}: {name} must be a device tensor")
+    if Q.dtype not in (torch.float16, torch.bfloat16):
+        raise ValueError(f"{who}: Q must be float16 or bfloat16, got {Q.dtype}")
+    if K8.dtype != torch.float8_e4m3fn or V8.dtype != torch.float8_e4m3fn:
+        raise ValueError(f"{who}: K8 and V8 must be torch.float8_e4m3fn, got {K8.dtype} and {V8.dtype}")
+    if torch.is_grad_enabled() and Q.requires_grad:
+        raise ValueError(f"{who}: Q requires grad, but this path has no backward (inference only): call it under "
+                         "torch.no_grad() or detach Q")
+    if Q.dim() not in (2, 3, 4) or not (Q.dim() == K8.dim() == V8.dim()):
+        raise ValueError(f"{who}: Q, K8 and V8 must all be (rows, W), (H, rows, W) or (B, H, rows, W)")
+    flat = Q.dim() == 2
+    if flat:
+        Q, K8, V8 = Q.unsqueeze(0), K8.unsqueeze(0), V8.unsqueeze(0)
+    lead, D, Dv = tuple(Q.shape[:-2]), Q.shape[-1], V8.shape[-1]
+    for name, X, rows, W in (("Q", Q, plan.M, D), ("K8", K8, plan.N, D), ("V8", V8, plan.N, Dv)):
+        if tuple(X.shape) != lead + (rows, W):
+            raise ValueError(f"{who}: {name} must be {lead + (rows, W)}, got {tuple(X.shape)}")
+    if D not in (64, 128, 256) or Dv not in (64, 128, 256):
+        raise ValueError(f"{who}: D = {D} and Dv = {Dv} must each be one of 64, 128, 256")
+    lim = attention_heads_limits()
+    B, H = (1,) * (2 - len(lead)) + lead
+    if not (1 <= B <= lim["max_batches"] and 1 <= H <= lim["max_heads"]):
+        raise ValueError(f"{who}: batch = {B} and heads = {H} must be 1 .. {lim['max_batches']} and 1 .. {lim['max_heads']}")
+    for name, X, rows, W in (("Q", Q, plan.M, D), ("K8", K8, plan.N, D), ("V8", V8, plan.N, Dv)):
+        if X.stride(-1) != 1 or min(X.stride()) < 0:
+            raise ValueError(f"{who}: {name} must have a contiguous last dimension, got strides {tuple(X.stride())}")
+        bad = attention_layout_check(X, B, H, rows, W, X.element_size(), False)
+        if bad is not None:
+            raise ValueError(f"{who}: {name}: {bad}")
+    scale = _valid_scale(who, D ** -0.5 if scale is None else scale)
+    k_scale, v_scale = _valid_scale(who, k_scale), _valid_scale(who, v_scale)
+    O = _dense_like(Q, lead + (plan.M, Dv))
+    lse = torch.empty(lead + (plan.M,), dtype=torch.float32, device=Q.device)
+    plan.attention_panels_kv8_heads(B, H, Q.detach(), K8, V8, D, Dv, O, lse.data_ptr(), scale, k_scale, v_scale,
+                                    stream=_stream(), dtype=_DTYPES[Q.dtype])
+    if flat:
+        O, lse = O[0], lse[0]
+    return (O, lse) if return_lse else O

@@ -57,28 +57,13 @@
 #include "attention_common.hpp"
 #include "attention_layout.hpp"
 #include "attention_panels.hpp"
+#include "attention_panels_args.hpp"
 #include "panel_mfma.hpp"
 #include "plan.hpp"
 #include "seg_walk.hpp"  // exp2_hw
 
 namespace bsmr {
 namespace {
-
-struct PanelArgs {
-    const PanelItem* items;
-    const PanelStep* steps;
-    const u32* rows;
-    AttnOpBytes Q, K, V, O;  // strides in bytes
-    float* lse;              // slices x M, or null
-    float* pacc;             // slices x partials x 16 x Dv
-    float* pml;              // behind them: slices x partials x 16 x (m, l)
-    u32 partials, heads, M, nItems;
-    float c, scale;  // scale log2(e), rounded once from double; scale
-};
-
-// attention.hip's conventions
-__device__ __forceinline__ float shift_of(float m) { return m == -INFINITY ? 0.f : m; }
-__device__ __forceinline__ float inverse_of(float s) { return s == 0.f ? 0.f : 1.0f / s; }
 
 template <int DT, int D, int DV>
 __global__ __launch_bounds__(PANEL_WAVES * 64) __attribute__((amdgpu_waves_per_eu(2)))
@@ -259,12 +244,10 @@ __global__ __launch_bounds__(256) void k_attention_panels_reduce(const PanelArgs
         s.z = i ? s.z + fz : fz;
         s.w = i ? s.w + fw : fw;
     }
-    const float inv = inverse_of(ls);
+    const float inv = inverse_of(ls) * a.vscale;  // (vscale 1 but for e4m3 K / V: an exact product)
     reinterpret_cast<float4*>(O + static_cast<size_t>(row) * a.O.row)[q] = make_float4(s.x * inv, s.y * inv, s.z * inv, s.w * inv);
     if (q == 0 && a.lse) a.lse[slice * a.M + row] = m * a.scale + logf(ls);
 }
-
-using PanelFn = void (*)(const PanelArgs);
 
 template <int DT, int D>
 PanelFn pick_dv(u32 Dv) {
@@ -315,10 +298,12 @@ int build_panels(const Plan& p, u32 Dv, u32 slices, const char* who) {
     return p.attention_panels.scratch.grow(panels_scratch_floats(S, Dv, slices));
 }
 
-// the launches of bsmr_attention_panels and bsmr_attention_panels_heads, arguments already validated
-int panels_launch(const char* who, const char* prep, const bsmr_plan* plan, u32 batches, u32 heads,
-                  const bsmr_attention_operand& Q, const bsmr_attention_operand& K, const bsmr_attention_operand& V, u32 D,
-                  u32 Dv, int dtype, float scale, float c, const bsmr_attention_operand& O, float* dLse, void* stream) {
+}  // namespace
+
+int attn_panels_launch(const char* who, const char* prep, const bsmr_plan* plan, PanelFn fn, u32 batches, u32 heads,
+                       const bsmr_attention_operand& Q, const bsmr_attention_operand& K, const bsmr_attention_operand& V,
+                       u32 kvBytes, u32 D, u32 Dv, int dtype, float scale, float c, float vscale,
+                       const bsmr_attention_operand& O, float* dLse, void* stream) {
     const Plan& p = plan->p;
     const hipStream_t s = static_cast<hipStream_t>(stream);
     const Plan::AttentionPanelsState& S = p.attention_panels;
@@ -349,15 +334,15 @@ int panels_launch(const char* who, const char* prep, const bsmr_plan* plan, u32 
     }
     a.pml = a.pacc ? a.pacc + static_cast<size_t>(slices) * a.partials * PANEL_ROWS * Dv : nullptr;
     a.Q = attn_op_bytes(&Q, batches, heads, p.M, 2u);
-    a.K = attn_op_bytes(&K, batches, heads, p.N, 2u);
-    a.V = attn_op_bytes(&V, batches, heads, p.N, 2u);
+    a.K = attn_op_bytes(&K, batches, heads, p.N, kvBytes);
+    a.V = attn_op_bytes(&V, batches, heads, p.N, kvBytes);
     a.O = attn_op_bytes(&O, batches, heads, p.M, 4u);
     a.lse = dLse;
     a.heads = heads;
     a.M = p.M;
     a.c = c;
     a.scale = scale;
-    const PanelFn fn = dtype == BSMR_F16 ? pick_d<BSMR_F16>(D, Dv) : pick_d<BSMR_BF16>(D, Dv);
+    a.vscale = vscale;
     if (a.nItems) {
         const u32 grid = (a.nItems + PANEL_WAVES - 1) / PANEL_WAVES;
         hipLaunchKernelGGL(fn, dim3(grid, heads, batches), dim3(PANEL_WAVES * 64), 0, s, a);
@@ -371,6 +356,11 @@ int panels_launch(const char* who, const char* prep, const bsmr_plan* plan, u32 
     }
     return BSMR_OK;
 }
+
+namespace {
+
+// the 16-bit form's kernel; the dims are validated
+PanelFn panels_kernel(u32 D, u32 Dv, int dtype) { return dtype == BSMR_F16 ? pick_d<BSMR_F16>(D, Dv) : pick_d<BSMR_BF16>(D, Dv); }
 
 // the prepare calls carry no dtype
 int panels_prepare_args(const char* who, const bsmr_plan* plan, u32 D, u32 Dv, u32 slices) {
@@ -447,9 +437,10 @@ extern "C" int bsmr_attention_panels(const bsmr_plan* plan, const void* dQ, cons
     BSMR_CHECK(attn_validate_scale(who, scale, &c));
     BSMR_CHECK(panels_validate_dims(who, D, Dv, dtype));
     const Plan& p = plan->p;
-    return panels_launch(who, "bsmr_plan_prepare_attention_panels", plan, 1, 1, attention_dense_operand(dQ, 1, p.M, D),
-                         attention_dense_operand(dK, 1, p.N, D), attention_dense_operand(dV, 1, p.N, Dv), D, Dv, dtype, scale,
-                         c, attention_dense_operand(dO, 1, p.M, Dv), dLse, stream);
+    return attn_panels_launch(who, "bsmr_plan_prepare_attention_panels", plan, panels_kernel(D, Dv, dtype), 1, 1,
+                              attention_dense_operand(dQ, 1, p.M, D), attention_dense_operand(dK, 1, p.N, D),
+                              attention_dense_operand(dV, 1, p.N, Dv), 2u, D, Dv, dtype, scale, c, 1.0f,
+                              attention_dense_operand(dO, 1, p.M, Dv), dLse, stream);
 }
 
 extern "C" int bsmr_attention_panels_heads(const bsmr_plan* plan, uint32_t batches, uint32_t heads,
@@ -473,8 +464,8 @@ extern "C" int bsmr_attention_panels_heads(const bsmr_plan* plan, uint32_t batch
     BSMR_CHECK(attn_check_operand(who, "K", K, batches, heads, p.N, D, 2u, false));
     BSMR_CHECK(attn_check_operand(who, "V", V, batches, heads, p.N, Dv, 2u, false));
     BSMR_CHECK(attn_check_operand(who, "O", O, batches, heads, p.M, Dv, 4u, true));
-    return panels_launch(who, "bsmr_plan_prepare_attention_panels_heads", plan, batches, heads, *Q, *K, *V, D, Dv, dtype,
-                         scale, c, *O, dLse, stream);
+    return attn_panels_launch(who, "bsmr_plan_prepare_attention_panels_heads", plan, panels_kernel(D, Dv, dtype), batches,
+                              heads, *Q, *K, *V, 2u, D, Dv, dtype, scale, c, 1.0f, *O, dLse, stream);
 }
 
 extern "C" int bsmr_plan_prepare_attention_panels_heads(const bsmr_plan* plan, uint32_t D, uint32_t Dv, uint32_t slices) {

@@ -1,0 +1,43 @@
+// attention_panels_args.hpp — what the forms of the panel attention forward share: the kernels'
+// argument record, the softmax conventions and the one launch routine (attention_panels.hip, the
+// 16-bit K / V form and the reduce; attention_panels_kv8.hip, the e4m3 K / V form).
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+
+#include "attention_common.hpp"
+#include "attention_panels.hpp"
+
+namespace bsmr {
+
+struct PanelArgs {
+    const PanelItem* items;
+    const PanelStep* steps;
+    const u32* rows;
+    AttnOpBytes Q, K, V, O;  // strides in bytes
+    float* lse;              // slices x M, or null
+    float* pacc;             // slices x partials x 16 x Dv
+    float* pml;              // behind them: slices x partials x 16 x (m, l)
+    u32 partials, heads, M, nItems;
+    float c, scale;  // scale log2(e), rounded once from double; scale
+    float vscale;    // multiplies 1 / l once, rounded, before the product with acc (1: the 16-bit form)
+};
+
+using PanelFn = void (*)(const PanelArgs);
+
+// attention.hip's conventions
+__device__ __forceinline__ float shift_of(float m) { return m == -INFINITY ? 0.f : m; }
+__device__ __forceinline__ float inverse_of(float s) { return s == 0.f ? 0.f : 1.0f / s; }
+
+// The launches of a panel forward, arguments already validated: `fn` over the plan's items, then
+// k_attention_panels_reduce over its split panels. K and V hold elements of kvBytes bytes; the
+// lists and the scratch are built first unless `stream` is capturing (BSMR_ERR_NOT_PREPARED, naming
+// `prep`). Defined in attention_panels.hip
+int attn_panels_launch(const char* who, const char* prep, const bsmr_plan* plan, PanelFn fn, u32 batches, u32 heads,
+                       const bsmr_attention_operand& Q, const bsmr_attention_operand& K, const bsmr_attention_operand& V,
+                       u32 kvBytes, u32 D, u32 Dv, int dtype, float scale, float c, float vscale,
+                       const bsmr_attention_operand& O, float* dLse, void* stream);
+
+}  // namespace bsmr

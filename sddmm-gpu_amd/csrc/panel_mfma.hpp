@@ -1,7 +1,7 @@
 // panel_mfma.hpp — what the panel kernels of the fused sparse attention share on the device
 // (attention_panels.hip, the forward; attention_bwd_panels.hip, the backward): the 16 x 16 x 32
-// matrix instruction on fp16 / bf16 operands, the rounding pack, the wave's own LDS ordering and
-// the transposing read of a staged tile. Lane l of a wave is (r, g) = (l & 15, l >> 4) everywhere:
+// matrix instruction on fp16 / bf16 operands, the rounding pack, the exact widening of e4m3 bytes
+// (attention_panels_kv8.hip), the wave's own LDS ordering and the transposing read of a staged tile. Lane l of a wave is (r, g) = (l & 15, l >> 4) everywhere:
 //   A operand  lane (i, g) holds A[i][8 g, +8)        (16 x 32)
 //   B operand  lane (n, g) holds B[8 g, +8)[n]        (32 x 16)
 //   result     lane (n, g) holds C[4 g + j][n], j = 0 .. 3
@@ -47,6 +47,23 @@ __device__ __forceinline__ u32 pack2(float lo, float hi) {
 template <int DT>
 __device__ __forceinline__ uint4 pack8(const float* t) {
     return make_uint4(pack2<DT>(t[0], t[1]), pack2<DT>(t[2], t[3]), pack2<DT>(t[4], t[5]), pack2<DT>(t[6], t[7]));
+}
+
+// Two OCP e4m3 bytes (the low or the high half of w) widened to the operand type by gfx950's packed
+// convert with scale 1: exact, since an e4m3 value (3 mantissa bits, 2^-9 .. 2^8) is a normal
+// number of fp16 and of bf16; a NaN byte (0x7F, 0xFF) stays a NaN. The lower byte lands in the low half
+template <int DT, bool HI>
+__device__ __forceinline__ u32 widen2(u32 w) {
+    if constexpr (DT == BSMR_F16)
+        return __builtin_bit_cast(u32, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w, 1.0f, HI));
+    else
+        return __builtin_bit_cast(u32, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, HI));
+}
+
+// eight consecutive e4m3 bytes (two words) as an operand of mfma32, in byte order
+template <int DT>
+__device__ __forceinline__ uint4 widen8(u32 lo, u32 hi) {
+    return make_uint4(widen2<DT, false>(lo), widen2<DT, true>(lo), widen2<DT, false>(hi), widen2<DT, true>(hi));
 }
 
 __device__ __forceinline__ uint4 load16(const char* p) { return *reinterpret_cast<const uint4*>(p); }

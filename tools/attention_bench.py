@@ -79,6 +79,14 @@ and the same fp16 / bf16 tensors, D = Dv = --d, by the same protocol (graphs of 
 attention_panels_stats (fill_permille, steps, items, split panels), graph_us of both, their ratio,
 the largest |O_panels - O_gather|, and floor_us: Q, O and LSE once, the step records, and the K and
 V rows of every panel's column union once per panel (32 rows per step, padding included).
+
+    python3 tools/attention_bench.py --forward panels --kv8 [--cases C2,C5,C3] [--dtype f16|bf16] [--d 64|128|256]
+
+With --forward panels --kv8 the two sides are one Plan.attention_panels_kv8 (K and V as e4m3 bytes,
+DESIGN.md section 20) and one Plan.attention_panels on the same plan, the same Q and the same K and
+V quantised by bsmr.autograd.quantize_kv and widened again (scale x k_scale as its scale), by the
+same protocol. Per case: graph_us of both, kv8_over_panels16, floor_us of both with section 18's
+count (one byte per K / V element for kv8) and the largest |O_kv8 - v_scale O_panels16|.
 """
 import argparse
 import json
@@ -103,6 +111,7 @@ def main():
     ap.add_argument("--dtype", default="f32", choices=["f32", "f16", "bf16"])
     ap.add_argument("--forward", default="gather", choices=["gather", "panels"])
     ap.add_argument("--backward", default="gather", choices=["gather", "panels"])
+    ap.add_argument("--kv8", action="store_true")
     ap.add_argument("--layout", default="bmhd", choices=["bmhd", "bhmd"])
     ap.add_argument("--baseline-only", action="store_true")
     ap.add_argument("--order-probe", action="store_true")
@@ -110,6 +119,8 @@ def main():
     args = ap.parse_args()
     if args.forward == "panels" and args.dtype == "f32":
         raise SystemExit("--forward panels takes --dtype f16 or bf16")
+    if args.kv8 and (args.forward != "panels" or args.d not in (64, 128, 256)):
+        raise SystemExit("--kv8 goes with --forward panels and --d 64, 128 or 256")
     if args.backward == "panels" and (args.dtype == "f32" or args.d not in (32, 64, 128)):
         raise SystemExit("--backward panels takes --dtype f16 or bf16 and --d 32, 64 or 128")
     if "panels" not in (args.forward, args.backward) and args.dtype == "bf16":
@@ -341,6 +352,9 @@ def panels_bench(args, torch, dev, graph_of, alternate):
         plan.prepare_attention_panels(D, D)
         data = lambda rows: (torch.from_numpy(make_data(rows * D)).to(dev) - 1.0).reshape(rows, D).to(tdt)  # noqa: E731
         Q, K, V = data(M), data(N), data(N)
+        if args.kv8:
+            kv8_case(args, torch, plan, case, Q, K, V, scale, dtype, graph_of, alternate)
+            continue
         out = {k: (torch.zeros(M, D, device=dev), torch.zeros(M, device=dev)) for k in ("gather", "panels")}
         ours = {"gather": lambda s: plan.attention(p(Q), p(K), p(V), D, D, p(out["gather"][0]), p(out["gather"][1]), scale,
                                                    stream=s, dtype=dtype),
@@ -356,6 +370,33 @@ def panels_bench(args, torch, dev, graph_of, alternate):
                 "floor_us": round(floor, 3), "floor_fraction": round(floor / graph_us["panels"], 3),
                 "max_abs_diff": (out["panels"][0] - out["gather"][0]).abs().max().item()}
         print(json.dumps(line), flush=True)
+
+
+def kv8_case(args, torch, plan, case, Q, K, V, scale, dtype, graph_of, alternate):
+    """One case of --forward panels --kv8 (module docstring)."""
+    from bsmr.autograd import quantize_kv
+
+    D, M = args.d, plan.M
+    p = lambda t: t.data_ptr()  # noqa: E731
+    K8, V8, ks, vs = quantize_kv(K, V)
+    Kw, Vw = K8.to(Q.dtype), V8.to(Q.dtype)  # exact: what the kv8 kernel widens to in registers
+    out = {k: (torch.zeros(M, D, device=Q.device), torch.zeros(M, device=Q.device)) for k in ("panels16", "kv8")}
+    ours = {"panels16": lambda s: plan.attention_panels(p(Q), p(Kw), p(Vw), D, D, p(out["panels16"][0]), p(out["panels16"][1]),
+                                                        scale * ks, stream=s, dtype=dtype),
+            "kv8": lambda s: plan.attention_panels_kv8(p(Q), p(K8), p(V8), D, D, p(out["kv8"][0]), p(out["kv8"][1]), scale, ks,
+                                                       vs, stream=s, dtype=dtype)}
+    graphs = {k: graph_of(f) for k, f in ours.items()}
+    graph_us = alternate({k: g.replay for k, g in graphs.items()})
+    st = plan.attention_panels_stats()
+    floor = {k: (2 * D * M + 4 * D * M + 4 * M + 192 * st["steps"] + 2 * esz * D * 32 * st["steps"]) / HBM_BYTES_PER_S * 1e6
+             for k, esz in (("panels16", 2), ("kv8", 1))}
+    line = {"case": case, "mode": "panels_kv8", "M": M, "N": plan.N, "D": D, "dtype": args.dtype, "steps": args.steps,
+            "rounds": args.rounds, "attention_panels_stats": st, "k_scale": ks, "v_scale": vs, "graph_us": graph_us,
+            "kv8_over_panels16": round(graph_us["kv8"] / graph_us["panels16"], 3),
+            "floor_us": {k: round(v, 3) for k, v in floor.items()},
+            "floor_fraction": {k: round(floor[k] / graph_us[k], 3) for k in floor},
+            "max_abs_diff": (out["kv8"][0] - vs * out["panels16"][0]).abs().max().item()}
+    print(json.dumps(line), flush=True)
 
 
 def panels_bwd_bench(args, torch, dev, graph_of, alternate):

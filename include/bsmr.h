@@ -60,7 +60,10 @@ extern "C" {
                               prepared / stats calls and bsmr_attention_pattern_transpose (the panel
                               MFMA backward: new declarations only); bsmr_attention_panels_kv8, its
                               heads form and the bsmr_kv_dtype enum: the panel MFMA forward over e4m3 K / V,
-                              new declarations only */
+                              new declarations only; bsmr_spmm_panels, bsmr_spmm_t_panels,
+                              bsmr_plan_prepare_spmm_panels, bsmr_plan_spmm_panels_prepared,
+                              bsmr_plan_spmm_panels_stats and bsmr_spmm_panel_positions (the panel
+                              MFMA SpMM, the SDDMM gradients: new declarations only) */
 
 typedef enum {
     BSMR_OK = 0,
@@ -931,6 +934,60 @@ int bsmr_plan_attention_backward_panels_stats(const bsmr_plan* plan, bsmr_attent
  * or a column >= N. */
 int bsmr_attention_pattern_transpose(uint32_t M, uint32_t N, const uint32_t* rowptr, const uint32_t* colidx,
                                      uint32_t* trowptr, uint32_t* tcolidx);
+
+/* ------------------------------------ SpMM on matrix instructions, per panel ---- */
+/* bsmr_spmm / bsmr_spmm_t for fp16 / bf16 dense operands on v_mfma_f32_16x16x32_{f16,bf16}
+ * (DESIGN.md §21): Y = S(V) B per 16-row panel of the plan's row order (the very lists of
+ * bsmr_attention_panels) and Y = S(V)^T A per panel of 16 consecutive columns (the lists of
+ * bsmr_attention_backward_panels' columns side); each is built here when no attention call built
+ * it. Every dense row of a panel's union is loaded once per panel (once per slice of 256 columns
+ * for K = 512 and 1024). The contract is bsmr_spmm's: V is nnz fp32 values at CSR positions, the
+ * operand layouts are unchanged (the dense operand and dY 16-byte aligned), every element of Y is
+ * written and an empty destination is exactly 0, outputs are untouched on every error, no atomics,
+ * results are bitwise reproducible and equal between a lazily built and a prepared plan, an
+ * unprepared call on a capturing stream gives BSMR_ERR_NOT_PREPARED and leaves the capture intact,
+ * the scratch is plan-owned and grows only, launches of one side go in order on one stream and the
+ * two sides are independent. What differs:
+ *   dtype is BSMR_F16 or BSMR_BF16 and K one of 32, 64, 128, 256, 512, 1024; anything else
+ *   (BSMR_F32 too) gives BSMR_ERR_UNSUPPORTED;
+ *   at most two launches per call (the items, then the reduce of the split panels);
+ *   the summation order is the panel's union order: the bits are not those of bsmr_spmm;
+ *   V is not rounded to the operand type: it enters the MFMA as two fp16 pieces under a running
+ *   power-of-two scale per destination, or as three bf16 pieces whose sum is the value, so that
+ *   Y(2^k V) = 2^k Y(V) bit for bit while nothing leaves fp32's normal range (bound: §21);
+ *   NaN / inf: a non-finite V[e] makes exactly its own destination row non-finite (all of it); a
+ *   NaN or inf in a dense row reaches every destination of the panels whose union holds that row
+ *   (0 x NaN inside the MFMA is NaN) and no destination of another panel. */
+int bsmr_spmm_panels(const bsmr_plan* plan, const float* dV, const void* dB, uint32_t K, int dtype, float* dY,
+                     void* stream);
+int bsmr_spmm_t_panels(const bsmr_plan* plan, const float* dV, const void* dA, uint32_t K, int dtype, float* dY,
+                       void* stream);
+/* Build now what the first launch of the named sides at K would build (sides & 1: rows, & 2:
+ * columns): the side's panel lists when no attention call built them, its entry positions and the
+ * scratch of its split panels. Synchronous and idempotent; a larger K grows the scratch. */
+int bsmr_plan_prepare_spmm_panels(const bsmr_plan* plan, uint32_t K, int sides);
+/* 1 when a launch of the named sides at K would make no allocation, copy or synchronisation, else 0
+ * (also 0 on bad arguments); no device call. */
+int bsmr_plan_spmm_panels_prepared(const bsmr_plan* plan, uint32_t K, int sides);
+typedef struct {
+    /* as bsmr_attention_panels_stats, of the side's lists */
+    uint32_t panels, items, steps, split_panels, partials, fill_permille;
+} bsmr_spmm_panels_stats;
+/* side 1 (rows) or 2 (columns); zeros while the side is not built. */
+int bsmr_plan_spmm_panels_stats(const bsmr_plan* plan, int side, bsmr_spmm_panels_stats* out);
+/* Host only (no plan, no device): where in V the entry behind every set mask bit of panel lists
+ * lies. side 1: the lists are bsmr_attention_panel_lists(M, N, rowptr, colidx, order, ...) and
+ * `rows` its launch order; side 2: they are the lists of bsmr_attention_pattern_transpose's pattern
+ * (`rows` is ignored) and a position is the entry's index in the CSR of S, carried through the
+ * transpose. A CSR row's columns need not be sorted. pos (rowptr[M] entries) is ordered step by
+ * step, panel row by panel row, mask bit by mask bit, and base holds 16 entries per step: the entry
+ * of (step s, panel row r, slot c) is V[pos[base[16 s + r] + popcount(masks[r] & ((1 << c) - 1))]].
+ * Every position appears exactly once. BSMR_ERR_INVALID for a null pointer, a side other than 1 or
+ * 2, a rowptr not non-decreasing from 0, a column >= N, an item, row or step out of range, or lists
+ * that are not those of this pattern (a mask bit without its entry, an entry without its bit). */
+int bsmr_spmm_panel_positions(uint32_t M, uint32_t N, const uint32_t* rowptr, const uint32_t* colidx, int side,
+                              const uint32_t* rows, const bsmr_attention_panel_step* steps, uint64_t nsteps,
+                              const bsmr_attention_panel_item* items, uint64_t nitems, uint32_t* base, uint32_t* pos);
 
 /* Timing: run `iters` back-to-back SDDMMs on `stream`, timing each kernel with HIP events on
  * that stream (BSMR_ERR_UNSUPPORTED on a capturing stream). Outputs average ms per launch of the dense-tile kernel, the residual kernel and

@@ -179,6 +179,14 @@ class AttentionPanelsStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class SpmmPanelsStats(C.Structure):
+    """bsmr_spmm_panels_stats: one side's panel lists of the MFMA SpMM (zeros when not built)."""
+    _fields_ = [(k, C.c_uint32) for k in ("panels", "items", "steps", "split_panels", "partials", "fill_permille")]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class AttentionBackwardStats(C.Structure):
     """bsmr_attention_backward_stats: the fused attention backward's row and column segment lists
     and plan-owned scratch (zeros when not built) and the library's constant chunks."""
@@ -271,6 +279,8 @@ EXPORTS = [
     "bsmr_plan_attention_backward_panels_prepared", "bsmr_plan_attention_backward_panels_heads_prepared",
     "bsmr_plan_attention_backward_panels_stats", "bsmr_attention_pattern_transpose",
     "bsmr_attention_panels_kv8", "bsmr_attention_panels_kv8_heads",
+    "bsmr_spmm_panels", "bsmr_spmm_t_panels", "bsmr_plan_prepare_spmm_panels", "bsmr_plan_spmm_panels_prepared",
+    "bsmr_plan_spmm_panels_stats", "bsmr_spmm_panel_positions",
 ]
 
 # include/bsmr.h BSMR_ATTENTION_MAX_BATCHES, BSMR_ATTENTION_MAX_HEADS
@@ -435,6 +445,16 @@ def lib():
     u64p = C.POINTER(C.c_uint64)
     L.bsmr_attention_panel_lists.argtypes = [C.c_uint32, C.c_uint32, vp, vp, vp, C.c_uint32, vp, vp, u64p, vp, u64p, vp, u64p]
     L.bsmr_attention_panel_lists.restype = C.c_int
+    for f in ("bsmr_spmm_panels", "bsmr_spmm_t_panels"):
+        getattr(L, f).argtypes = [vp, vp, vp, C.c_uint32, C.c_int, vp, vp]
+        getattr(L, f).restype = C.c_int
+    for f in ("bsmr_plan_prepare_spmm_panels", "bsmr_plan_spmm_panels_prepared"):
+        getattr(L, f).argtypes = [vp, C.c_uint32, C.c_int]
+        getattr(L, f).restype = C.c_int
+    L.bsmr_plan_spmm_panels_stats.argtypes = [vp, C.c_int, C.POINTER(SpmmPanelsStats)]
+    L.bsmr_plan_spmm_panels_stats.restype = C.c_int
+    L.bsmr_spmm_panel_positions.argtypes = [C.c_uint32, C.c_uint32, vp, vp, C.c_int, vp, vp, C.c_uint64, vp, C.c_uint64, vp, vp]
+    L.bsmr_spmm_panel_positions.restype = C.c_int
     L.bsmr_attention_backward_panels.argtypes = L.bsmr_attention_backward.argtypes
     L.bsmr_attention_backward_panels.restype = C.c_int
     L.bsmr_attention_backward_panels_heads.argtypes = L.bsmr_attention_backward_heads.argtypes
@@ -732,6 +752,29 @@ class Plan:
         _check(lib().bsmr_plan_spmm_stats(self.h, side, C.byref(s)), "bsmr_plan_spmm_stats")
         return s.as_dict()
 
+    def spmm_panels(self, dV, dB, K, dY, stream=0, dtype=F16):
+        """bsmr_spmm_panels: spmm's Y for fp16 / bf16 B and K in 32 .. 1024 (powers of two), per
+        16-row panel on matrix instructions; V enters in pieces, never rounded."""
+        _check(lib().bsmr_spmm_panels(self.h, dV, dB, K, dtype, dY, stream or None), "bsmr_spmm_panels")
+
+    def spmm_t_panels(self, dV, dA, K, dY, stream=0, dtype=F16):
+        """bsmr_spmm_t_panels: spmm_t's Y the same way, per panel of 16 consecutive columns."""
+        _check(lib().bsmr_spmm_t_panels(self.h, dV, dA, K, dtype, dY, stream or None), "bsmr_spmm_t_panels")
+
+    def prepare_spmm_panels(self, K, sides=3):
+        """bsmr_plan_prepare_spmm_panels: build now the panel lists, the entry positions and the
+        scratch of spmm_panels (sides & 1) and spmm_t_panels (sides & 2) at K, so that their first
+        launch can be captured."""
+        _check(lib().bsmr_plan_prepare_spmm_panels(self.h, K, sides), "bsmr_plan_prepare_spmm_panels")
+
+    def spmm_panels_prepared(self, K, sides=3):
+        return bool(lib().bsmr_plan_spmm_panels_prepared(self.h, K, sides))
+
+    def spmm_panels_stats(self, side):
+        s = SpmmPanelsStats()
+        _check(lib().bsmr_plan_spmm_panels_stats(self.h, side, C.byref(s)), "bsmr_plan_spmm_panels_stats")
+        return s.as_dict()
+
     def softmax(self, dP, dW, scale=1.0, stream=0):
         """bsmr_softmax: per row of S, W = softmax(scale * P) over the row's stored entries (dP,
         dW: device pointers to nnz fp32 in CSR order; dW == dP works in place). The maximum is
@@ -935,13 +978,17 @@ class Plan:
                "bsmr_plan_attention_backward_panels_stats")
         return s.as_dict()
 
-    def sddmm_backward(self, dG, dA, dB, K, dGA, dGB, stream=0, dtype=F32):
+    def sddmm_backward(self, dG, dA, dB, K, dGA, dGB, stream=0, dtype=F32, backward="gather"):
         """The gradients of P = sddmm(A, B) from dG = dL/dP (fp32, nnz): dGA (M x K fp32) =
-        S(G) B and dGB (N x K fp32) = S(G)^T A. Either output may be 0: that side is skipped."""
+        S(G) B and dGB (N x K fp32) = S(G)^T A. Either output may be 0: that side is skipped.
+        backward: "gather" (spmm / spmm_t) or "panels" (spmm_panels / spmm_t_panels)."""
+        if backward not in ("gather", "panels"):
+            raise ValueError(f'sddmm_backward: backward must be "gather" or "panels", got {backward!r}')
+        rows, cols = (self.spmm_panels, self.spmm_t_panels) if backward == "panels" else (self.spmm, self.spmm_t)
         if dGA:
-            self.spmm(dG, dB, K, dGA, stream=stream, dtype=dtype)
+            rows(dG, dB, K, dGA, stream=stream, dtype=dtype)
         if dGB:
-            self.spmm_t(dG, dA, K, dGB, stream=stream, dtype=dtype)
+            cols(dG, dA, K, dGB, stream=stream, dtype=dtype)
 
     def shard(self, K, rank, world, dtype=F32):
         """Panel range [p0, p1) of `rank` (bsmr_plan_shard_dtype)."""
@@ -1091,6 +1138,26 @@ def attention_pattern_transpose(M, N, rowptr, colidx):
     _check(lib().bsmr_attention_pattern_transpose(M, N, rp.ctypes.data, ci.ctypes.data, trp.ctypes.data, tci.ctypes.data),
            "bsmr_attention_pattern_transpose")
     return N, M, trp, tci[:len(ci)]
+
+
+def spmm_panel_positions(M, N, rowptr, colidx, side, lists):
+    """bsmr_spmm_panel_positions (host only): (base, pos) of the panel SpMM over `lists`, the tuple
+    attention_panel_lists returns for the pattern (side 1) or for attention_pattern_transpose of it
+    (side 2). base (steps, 16) and pos (nnz,) uint32: the entry of (step s, panel row r, slot c) is
+    V[pos[base[s, r] + popcount(masks[s, r] & ((1 << c) - 1))]]."""
+    rp, ci = np.ascontiguousarray(rowptr, np.uint32), np.ascontiguousarray(colidx, np.uint32)
+    if len(rp) != M + 1 or len(ci) != int(rp[-1]):
+        raise ValueError("spmm_panel_positions: rowptr needs M + 1 entries and colidx rowptr[M]")
+    rows, cols, masks, items, _ = lists
+    rows, items = np.ascontiguousarray(rows, np.uint32), np.ascontiguousarray(items, np.uint32)
+    steps = np.ascontiguousarray(np.concatenate([cols, masks], axis=1), np.uint32)
+    if side == 1 and len(rows) != M:
+        raise ValueError("spmm_panel_positions: side 1 needs the M rows of the launch order")
+    base, pos = np.zeros((len(steps), 16), np.uint32), np.zeros(max(len(ci), 1), np.uint32)
+    _check(lib().bsmr_spmm_panel_positions(M, N, rp.ctypes.data, ci.ctypes.data, side, rows.ctypes.data, steps.ctypes.data,
+                                           len(steps), items.ctypes.data, len(items), base.ctypes.data, pos.ctypes.data),
+           "bsmr_spmm_panel_positions")
+    return base, pos[:len(ci)]
 
 
 def attention_backward_limits():

@@ -29,6 +29,17 @@ import torch
 from . import BF16, F16, F32, attention_heads_limits, attention_layout_check, attention_limits
 
 _DTYPES = {torch.float32: F32, torch.float16: F16, torch.bfloat16: BF16}
+_PANEL_K = (32, 64, 128, 256, 512, 1024)  # include/bsmr.h, bsmr_spmm_panels
+
+
+def _validate_panels(who, arg, value, K, dtype):
+    """The SpMM form named by `arg`: "gather" (Plan.spmm / spmm_t) or "panels" (Plan.spmm_panels /
+    spmm_t_panels: float16 / bfloat16 and K in _PANEL_K); True for "panels"."""
+    if value not in ("gather", "panels"):
+        raise ValueError(f'{who}: {arg} must be "gather" or "panels", got {value!r}')
+    if value == "panels" and (dtype == F32 or K not in _PANEL_K):
+        raise ValueError(f'{who}: {arg}="panels" needs float16 or bfloat16 operands and K one of {_PANEL_K}, got K = {K}')
+    return value == "panels"
 
 
 def _stream():
@@ -66,11 +77,11 @@ def _validate(plan, A, B):
 
 class _Sddmm(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, A, B, plan):
+    def forward(ctx, A, B, plan, backward="gather"):
         K, dtype = _validate(plan, A, B)
         P = torch.empty(max(plan.nnz, 1), dtype=torch.float32, device=A.device)
         plan.sddmm(A.data_ptr(), B.data_ptr(), K, P.data_ptr(), stream=_stream(), dtype=dtype)
-        ctx.plan, ctx.K, ctx.dtype = plan, K, dtype
+        ctx.plan, ctx.K, ctx.dtype, ctx.backward_form = plan, K, dtype, backward
         ctx.save_for_backward(A, B)
         return P[:plan.nnz]
 
@@ -89,18 +100,21 @@ class _Sddmm(torch.autograd.Function):
         plan.sddmm_backward(G.data_ptr(), A.data_ptr(), B.data_ptr(), K,
                             gA.data_ptr() if gA is not None else 0,
                             gB.data_ptr() if gB is not None else 0,
-                            stream=_stream(), dtype=ctx.dtype)
-        return (None if gA is None else gA.to(A.dtype), None if gB is None else gB.to(B.dtype), None)
+                            stream=_stream(), dtype=ctx.dtype, backward=ctx.backward_form)
+        return (None if gA is None else gA.to(A.dtype), None if gB is None else gB.to(B.dtype), None, None)
 
 
-def sddmm(plan, A, B):
+def sddmm(plan, A, B, backward="gather"):
     """P (nnz,) float32 = the plan's sampled A @ B.T, differentiable in A and B. A: (M, K), B:
     (N, K) (the header's column-major K x N), contiguous device tensors of one dtype out of
     float32, float16 and bfloat16; K a positive multiple of 16 (float32) or 32 (float16 /
     bfloat16: what the forward launch takes). Shape, dtype, device, contiguity and K errors raise
-    ValueError before any launch and before any gather list is built."""
-    _validate(plan, A, B)
-    return _Sddmm.apply(A, B, plan)
+    ValueError before any launch and before any gather list is built. backward="panels" computes
+    both gradients per 16-destination panel on matrix instructions (Plan.spmm_panels /
+    spmm_t_panels: float16 / bfloat16 and K in 32, 64, 128, 256, 512, 1024, else ValueError)."""
+    K, dtype = _validate(plan, A, B)
+    _validate_panels("sddmm", "backward", backward, K, dtype)
+    return _Sddmm.apply(A, B, plan, backward)
 
 
 def _valid_scale(who, scale):
@@ -190,10 +204,11 @@ def _validate_spmm(plan, V, X):
 
 class _Spmm(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, V, X, plan):
+    def forward(ctx, V, X, plan, kernel="gather"):
         K, dtype = _validate_spmm(plan, V, X)
         Y = torch.empty((plan.M, K), dtype=torch.float32, device=X.device)
-        plan.spmm(_launchable(V).data_ptr(), X.data_ptr(), K, Y.data_ptr(), stream=_stream(), dtype=dtype)
+        launch = plan.spmm_panels if kernel == "panels" else plan.spmm
+        launch(_launchable(V).data_ptr(), X.data_ptr(), K, Y.data_ptr(), stream=_stream(), dtype=dtype)
         ctx.plan, ctx.K = plan, K
         ctx.save_for_backward(V, X)
         return Y
@@ -213,17 +228,21 @@ class _Spmm(torch.autograd.Function):
             gX = torch.empty((plan.N, K), dtype=torch.float32, device=X.device)
             plan.spmm_t(_launchable(V).data_ptr(), dY.data_ptr(), K, gX.data_ptr(), stream=_stream())
             gX = gX.to(X.dtype)
-        return gV, gX, None
+        return gV, gX, None, None
 
 
-def spmm(plan, V, X):
+def spmm(plan, V, X, kernel="gather"):
     """Y (M, K) float32 = S(V) X, the plan's pattern with values V times the dense X (Plan.spmm),
     differentiable in both: dV = the plan's sampled dY @ X.T (Plan.sddmm, in fp32: a float16 /
     bfloat16 X is cast up to float32 once for it), dX = S(V)^T dY (Plan.spmm_t, returned in X's
     dtype). V: (nnz,) float32 in CSR order; X: (N, K) float32, float16 or bfloat16, K a positive
-    multiple of 16; contiguous tensors of one device. Errors raise ValueError before any launch."""
-    _validate_spmm(plan, V, X)
-    return _Spmm.apply(V, X, plan)
+    multiple of 16; contiguous tensors of one device. Errors raise ValueError before any launch.
+    kernel="panels" runs the forward on matrix instructions (Plan.spmm_panels: float16 / bfloat16 X
+    and K in 32, 64, 128, 256, 512, 1024, else ValueError); dX multiplies by the float32 dY and
+    stays on Plan.spmm_t."""
+    K, dtype = _validate_spmm(plan, V, X)
+    _validate_panels("spmm", "kernel", kernel, K, dtype)
+    return _Spmm.apply(V, X, plan, kernel)
 
 
 def attention(plan, Q, K, V, scale=None):

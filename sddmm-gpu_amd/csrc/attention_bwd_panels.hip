@@ -447,39 +447,8 @@ bool bwdp_ready(const Plan& p, u32 D, u32 Dv, u32 slices) {
 // held. Synchronous on the plan's stream.
 int build_bwdp(const Plan& p, u32 D, u32 Dv, u32 slices, const char* who) {
     Plan::AttentionBwdPanelsState& B = p.attention_bwd_panels;
-    const hipStream_t s = p.stream;
     BSMR_CHECK(attn_panels_build_lists(p, who));
-    if (!B.built) {
-        std::vector<u32> hrp, hci, trp, tci;
-        BSMR_CHECK(p.rowptr.download(hrp, s));
-        BSMR_CHECK(p.colidx.download(hci, s));
-        PanelLists L;
-        std::string err;
-        if (attention_pattern_transpose(p.M, p.N, hrp.data(), hci.data(), trp, tci, err)) {
-            set_error(std::string(who) + ": " + err);
-            return BSMR_ERR_INVALID;
-        }
-        // M and N swap roles; no order: a column panel is 16 consecutive columns
-        if (const int st = attention_panel_lists(p.N, p.M, trp.data(), tci.data(), nullptr, 0, L, err)) {
-            set_error(std::string(who) + ": " + err);
-            return st == 2 ? BSMR_ERR_UNSUPPORTED : BSMR_ERR_INVALID;
-        }
-        if (L.nItems > (1ull << 31)) {
-            set_error(std::string(who) + ": more than 2^31 items");
-            return BSMR_ERR_UNSUPPORTED;
-        }
-        BSMR_CHECK(B.csteps.upload(L.steps.data(), L.steps.size(), s));
-        BSMR_CHECK(B.citems.upload(L.items.data(), L.items.size(), s));
-        BSMR_CHECK(B.creds.upload(L.reds.data(), L.reds.size(), s));
-        BSMR_HIP(hipStreamSynchronize(s));
-        B.colItems = static_cast<u32>(L.nItems);
-        B.colSteps = static_cast<u32>(L.nSteps);
-        B.colReds = static_cast<u32>(L.reds.size());
-        B.colPanels = L.panels;
-        B.colSplit = L.splitPanels;
-        B.colPartials = L.partials;
-        B.built = true;
-    }
+    BSMR_CHECK(attn_bwd_panels_build_col_lists(p, who));
     BSMR_CHECK(B.delta.grow(attn_sat_mul(slices, p.M)));
     BSMR_CHECK(B.rowScratch.grow(bwdp_row_floats(p, D, slices)));
     BSMR_CHECK(B.colScratch.grow(bwdp_col_floats(p, D, Dv, slices)));
@@ -581,6 +550,46 @@ int bwdp_prepare_args(const char* who, const bsmr_plan* plan, u32 D, u32 Dv, u32
 }
 
 }  // namespace
+
+// the column panels' lists (once): attention_panel_lists on the transposed pattern, M and N in each
+// other's role and no order, so a column panel is 16 consecutive columns. The panel SpMM's columns
+// side (spmm_panels.hip) runs over these very lists and builds them through this when no backward has
+int attn_bwd_panels_build_col_lists(const Plan& p, const char* who) {
+    Plan::AttentionBwdPanelsState& B = p.attention_bwd_panels;
+    const hipStream_t s = p.stream;
+    if (!B.built) {
+        std::vector<u32> hrp, hci, trp, tci;
+        BSMR_CHECK(p.rowptr.download(hrp, s));
+        BSMR_CHECK(p.colidx.download(hci, s));
+        PanelLists L;
+        std::string err;
+        if (attention_pattern_transpose(p.M, p.N, hrp.data(), hci.data(), trp, tci, err)) {
+            set_error(std::string(who) + ": " + err);
+            return BSMR_ERR_INVALID;
+        }
+        if (const int st = attention_panel_lists(p.N, p.M, trp.data(), tci.data(), nullptr, 0, L, err)) {
+            set_error(std::string(who) + ": " + err);
+            return st == 2 ? BSMR_ERR_UNSUPPORTED : BSMR_ERR_INVALID;
+        }
+        if (L.nItems > (1ull << 31)) {
+            set_error(std::string(who) + ": more than 2^31 items");
+            return BSMR_ERR_UNSUPPORTED;
+        }
+        BSMR_CHECK(B.csteps.upload(L.steps.data(), L.steps.size(), s));
+        BSMR_CHECK(B.citems.upload(L.items.data(), L.items.size(), s));
+        BSMR_CHECK(B.creds.upload(L.reds.data(), L.reds.size(), s));
+        BSMR_HIP(hipStreamSynchronize(s));
+        B.colItems = static_cast<u32>(L.nItems);
+        B.colSteps = static_cast<u32>(L.nSteps);
+        B.colReds = static_cast<u32>(L.reds.size());
+        B.colPanels = L.panels;
+        B.colSplit = L.splitPanels;
+        B.colPartials = L.partials;
+        B.built = true;
+    }
+    return BSMR_OK;
+}
+
 }  // namespace bsmr
 
 using namespace bsmr;

@@ -7,6 +7,7 @@
 
 #include "common.hpp"
 #include "plan.hpp"
+#include "spmm_panels.hpp"
 
 using namespace bsmr;
 
@@ -586,6 +587,37 @@ extern "C" int bsmr_attention_pattern_transpose(uint32_t M, uint32_t N, const ui
     }
     std::copy(trp.begin(), trp.end(), trowptr);
     std::copy(tci.begin(), tci.end(), tcolidx);
+    return BSMR_OK;
+}
+
+extern "C" int bsmr_spmm_panel_positions(uint32_t M, uint32_t N, const uint32_t* rowptr, const uint32_t* colidx, int side,
+                                         const uint32_t* rows, const bsmr_attention_panel_step* steps, uint64_t nsteps,
+                                         const bsmr_attention_panel_item* items, uint64_t nitems, uint32_t* base,
+                                         uint32_t* pos) {
+    const char* who = "bsmr_spmm_panel_positions";
+    if (!rowptr || (side != 1 && side != 2) || (nsteps && !base) || (M && rowptr[M] && !pos)) {
+        set_error(std::string(who) + ": null argument or side not 1 (rows) / 2 (columns)");
+        return BSMR_ERR_INVALID;
+    }
+    const PanelStep* st = reinterpret_cast<const PanelStep*>(steps);
+    const PanelItem* it = reinterpret_cast<const PanelItem*>(items);
+    std::vector<uint32_t> b, p, trp, tci, tpos, iota;
+    std::string err;
+    int bad;
+    if (side == 1) {
+        bad = spmm_panel_positions(M, N, rowptr, colidx, nullptr, rows, st, nsteps, it, nitems, b, p, err);
+    } else {
+        bad = spmm_pattern_transpose_pos(M, N, rowptr, colidx, trp, tci, tpos, err);
+        iota.resize(N);
+        for (uint32_t j = 0; j < N; ++j) iota[j] = j;
+        if (!bad) bad = spmm_panel_positions(N, M, trp.data(), tci.data(), tpos.data(), iota.data(), st, nsteps, it, nitems, b, p, err);
+    }
+    if (bad) {
+        set_error(std::string(who) + ": " + err);
+        return BSMR_ERR_INVALID;
+    }
+    std::copy(b.begin(), b.end(), base);
+    std::copy(p.begin(), p.end(), pos);
     return BSMR_OK;
 }
 

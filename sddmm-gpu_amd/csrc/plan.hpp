@@ -350,6 +350,22 @@ struct Plan {
     };
     mutable AttentionBwdPanelsState attention_bwd_panels;
 
+    // SpMM on matrix instructions, per panel (spmm_panels.hip; bsmr_spmm_panels / bsmr_spmm_t_panels).
+    // The rows side runs over AttentionPanelsState's rows / steps / items / reds, the columns side
+    // over AttentionBwdPanelsState's csteps / citems / creds (each built through its owner's builder
+    // when no attention call has; never a second copy). Its own, per side: where in V the entry of
+    // every set mask bit lies (spmm_panels.hpp: base, 16 per step; pos, one per entry) and the
+    // partial slots of the split panels: partials x 16 x scratchK floats followed by partials x 16
+    // running exponents. Built on first use or by bsmr_plan_prepare_spmm_panels, under layout_mu;
+    // the scratch grows and never shrinks; build_columns keeps all of it
+    struct SpmmPanelsSide {
+        bool built = false;
+        u32 scratchK = 0;
+        DevBuf<u32> base, pos;
+        DevBuf<float> scratch;
+    };
+    mutable SpmmPanelsSide spmm_panels[2];  // [0] rows (bsmr_spmm_panels), [1] columns (bsmr_spmm_t_panels)
+
     int build_rows(const u32* h_rowptr, const u32* h_col);
     int build_columns();
     ~Plan() {

@@ -14,6 +14,13 @@ Per case (C2: nips-like, K = 128, fp32; C3: cop20k-like, K = 256, fp16) and prod
     its transpose) built outside the timed region, stream-timed. Where torch lacks the product for
     the dtype the line carries the error text instead of a substitute;
   * floor_us: (8 nnz + 4 K dsts + rowBytes x distinct sources) / 8 TB/s, the byte floor.
+--panels [--cases C2/128/f16,C3/256/f16,C5/64/f16,C5/128/f16,C3/256/bf16] times the panel form
+(Plan.spmm_panels / spmm_t_panels) against the gather form on one plan, the same
+tensors and the same graph replays in alternation; per case and side it prints spmm_panels_stats
+(fill_permille, steps, items, split panels), graph_us of both forms, their ratio, the largest
+|Y_panels - Y_gather| and floor_us with each panel's union counted once: V, its positions and Y once,
+the step records and 32 dense rows per step, once per slice of 256 columns. C5 is the 2,048 x 2,048
+mask of 16 x 16 blocks.
 --sweep adds the chunk sweep {128, 256, 512, 1024} on C2 side 2 (the skewed side), one plan per
 chunk, replayed in alternation.
 """
@@ -31,7 +38,8 @@ HBM_BYTES_PER_S = 8e12
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--cases", default="C2,C3")
+    ap.add_argument("--cases", default=None)
+    ap.add_argument("--panels", action="store_true")
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--sweep", action="store_true")
@@ -39,7 +47,9 @@ def main():
     import numpy as np
     import torch
 
-    from bsmr import F16, F32, Plan, make_data, synth
+    from bsmr import BF16, F16, F32, Plan, make_data, synth
+
+    args.cases = args.cases or ("C2/128/f16,C3/256/f16,C5/64/f16,C5/128/f16,C3/256/bf16" if args.panels else "C2,C3")
 
     assert torch.cuda.is_available(), "spmm_bench needs a GPU"
     dev = torch.device("cuda", 0)
@@ -84,7 +94,35 @@ def main():
                 fn(gs.cuda_stream)
         return run
 
-    for case in args.cases.split(","):
+    patterns = {"C2": synth.nips_like, "C3": synth.cop20k_like, "C5": lambda: synth.dlmc_like("block")}
+    for spec in args.cases.split(",") if args.panels else ():
+        case, K, dtype = spec.split("/")
+        (M, N, rp, ci), K = patterns[case](), int(K)
+        dt, tdt = (F16, torch.float16) if dtype == "f16" else (BF16, torch.bfloat16)
+        nnz = len(ci)
+        plan = Plan(M, N, rp, ci, alpha=0.3, delta=0.3)
+        plan.prepare_spmm(K, 3)
+        plan.prepare_spmm_panels(K, 3)
+        X = {1: torch.from_numpy(make_data(N * K)).to(dev).to(tdt).reshape(N, K),
+             2: torch.from_numpy(make_data(M * K)).to(dev).to(tdt).reshape(M, K)}
+        dV = torch.from_numpy(make_data(nnz) - np.float32(0.5)).to(dev)
+        line = {"case": case, "mode": "panels", "M": M, "N": N, "nnz": nnz, "K": K, "dtype": dtype, "steps": args.steps,
+                "rounds": args.rounds}
+        for side, name in ((1, "dA"), (2, "dB")):
+            forms = {"gather": plan.spmm if side == 1 else plan.spmm_t, "panels": plan.spmm_panels if side == 1 else plan.spmm_t_panels}
+            out = {k: torch.zeros((M if side == 1 else N, K), dtype=torch.float32, device=dev) for k in forms}
+            graphs = {k: graph_of(lambda s, f=f, k=k: f(dV.data_ptr(), X[side].data_ptr(), K, out[k].data_ptr(), stream=s, dtype=dt))
+                      for k, f in forms.items()}
+            graph_us, rounds = alternate({k: g.replay for k, g in graphs.items()})
+            st = plan.spmm_panels_stats(side)
+            slices = max(1, K // 256)
+            floor = (8 * nnz + 4 * K * (M if side == 1 else N) + slices * st["steps"] * (256 + 32 * 2 * K // slices)) / HBM_BYTES_PER_S * 1e6
+            line[name] = {"spmm_panels_stats": st, "graph_us": graph_us, "panels_over_gather": round(graph_us["panels"] / graph_us["gather"], 3),
+                          "floor_us": round(floor, 3), "floor_fraction": round(floor / graph_us["panels"], 3),
+                          "max_abs_diff": (out["panels"] - out["gather"]).abs().max().item(), "max_abs": out["gather"].abs().max().item(),
+                          "graph_us_rounds": rounds}
+        print(json.dumps(line), flush=True)
+    for case in () if args.panels else args.cases.split(","):
         if case == "C2":
             (M, N, rp, ci), K, dt, tdt = synth.nips_like(), 128, F32, torch.float32
         elif case == "C3":

@@ -51,6 +51,7 @@
 #include "attention_common.hpp"
 #include "attention_layout.hpp"
 #include "attention_panels.hpp"
+#include "panel_host.hpp"
 #include "panel_mfma.hpp"
 #include "plan.hpp"
 #include "seg_walk.hpp"  // exp2_hw
@@ -98,18 +99,6 @@ __device__ __forceinline__ uint4 load8_rounded(const char* p) {
     return make_uint4(pack2<DT>(lo.x, lo.y), pack2<DT>(lo.z, lo.w), pack2<DT>(hi.x, hi.y), pack2<DT>(hi.z, hi.w));
 }
 
-// acc[2 n][j] and acc[2 n + 1][j] are elements 32 n + 8 g + 2 j and + 2 j + 1 of the lane's row: o
-// points at element 8 g
-template <int NP>
-__device__ __forceinline__ void store_acc(float* o, const f32x4* acc) {
-#pragma unroll
-    for (int n = 0; n < NP; ++n) {
-        const f32x4 e = acc[2 * n], d = acc[2 * n + 1];
-        *reinterpret_cast<float4*>(o + 32 * n) = make_float4(e[0], d[0], e[1], d[1]);
-        *reinterpret_cast<float4*>(o + 32 * n + 4) = make_float4(e[2], d[2], e[3], d[3]);
-    }
-}
-
 template <int DT, int D, int DV>
 __global__ __launch_bounds__(PANEL_WAVES * 64) __attribute__((amdgpu_waves_per_eu(2)))
 void k_attention_bwd_panels_rows(const BwdPanelArgs a) {
@@ -137,9 +126,7 @@ void k_attention_bwd_panels_rows(const BwdPanelArgs a) {
     const bool live = it.row0 + r < a.M;  // (a row of a short last panel is neither loaded nor stored)
     const u32 row = live ? a.rows[it.row0 + r] : 0u;
     uint4 q[KS], go[VS];
-#pragma unroll
-    for (int s = 0; s < KS; ++s)
-        q[s] = live ? load16(Qs + static_cast<size_t>(row) * a.Q.row + (32u * s + 8u * g) * 2u) : make_uint4(0, 0, 0, 0);
+    panel_row_operand(q, Qs + static_cast<size_t>(row) * a.Q.row, live, g);
 #pragma unroll
     for (int s = 0; s < VS; ++s)
         go[s] = live ? load8_rounded<DT>(GOs + static_cast<size_t>(row) * a.GO.row + (32u * s + 8u * g) * 4u)
@@ -204,8 +191,8 @@ void k_attention_bwd_panels_rows(const BwdPanelArgs a) {
         float w, dp[8];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            panel_weight(s0[j], g0[j], lse, dl, a.scale, (mask >> (4u * g + j)) & 1u, w, dp[j]);
-            panel_weight(s1[j], g1[j], lse, dl, a.scale, (mask >> (16u + 4u * g + j)) & 1u, w, dp[4 + j]);
+            panel_weight(s0[j], g0[j], lse, dl, a.scale, (mask >> panel_slot(g, j)) & 1u, w, dp[j]);
+            panel_weight(s1[j], g1[j], lse, dl, a.scale, (mask >> panel_slot(g, 4 + j)) & 1u, w, dp[4 + j]);
         }
         const uint4 pb = pack8<DT>(dp);
 
@@ -418,27 +405,16 @@ BwdPanelFn pick_d(bool rows, u32 D, u32 Dv) {
     }
 }
 
-bool bwdp_dim(u32 d) { return d == 32 || d == 64 || d == 128; }
-
-// fp16 / bf16 and the compile-time forms; else BSMR_ERR_UNSUPPORTED with the message set
-int bwdp_validate_dims(const char* who, u32 D, u32 Dv, int dtype) {
-    if ((dtype != BSMR_F16 && dtype != BSMR_BF16) || !bwdp_dim(D) || !bwdp_dim(Dv)) {
-        set_error(std::string(who) + ": dtype must be BSMR_F16 or BSMR_BF16 and D and Dv each one of 32, 64, 128");
-        return BSMR_ERR_UNSUPPORTED;
-    }
-    return BSMR_OK;
-}
-
 size_t bwdp_row_floats(const Plan& p, u32 D, u32 slices) {
-    return attn_sat_mul(attn_sat_mul(slices, p.attention_panels.partials, PANEL_ROWS), D);
+    return attn_sat_mul(attn_sat_mul(slices, p.panel_rows.partials, PANEL_ROWS), D);
 }
 size_t bwdp_col_floats(const Plan& p, u32 D, u32 Dv, u32 slices) {
-    return attn_sat_mul(attn_sat_mul(slices, p.attention_bwd_panels.colPartials, PANEL_ROWS), static_cast<size_t>(D) + Dv);
+    return attn_sat_mul(attn_sat_mul(slices, p.panel_cols.partials, PANEL_ROWS), static_cast<size_t>(D) + Dv);
 }
 
 bool bwdp_ready(const Plan& p, u32 D, u32 Dv, u32 slices) {
     const Plan::AttentionBwdPanelsState& B = p.attention_bwd_panels;
-    return B.built && p.attention_panels.built && B.delta.size() >= attn_sat_mul(slices, p.M) &&
+    return p.panel_cols.built && p.panel_rows.built && B.delta.size() >= attn_sat_mul(slices, p.M) &&
            B.rowScratch.size() >= bwdp_row_floats(p, D, slices) && B.colScratch.size() >= bwdp_col_floats(p, D, Dv, slices);
 }
 
@@ -471,34 +447,30 @@ int bwdp_launch(const char* who, const char* prep, const bsmr_plan* plan, u32 ba
     float* delta = nullptr;
     {
         std::lock_guard<std::mutex> g(p.layout_mu);
-        if (!bwdp_ready(p, D, Dv, slices)) {
-            const LaunchSite at{s, who, prep, D, dtype};
-            const int st = lazy_build_guard(at);
-            if (st == BSMR_ERR_NOT_PREPARED)
-                set_error(std::string(who) + ": stream is capturing and the panel backward's lists (or their scratch for D = " +
-                          std::to_string(D) + ", Dv = " + std::to_string(Dv) +
-                          (slices > 1 ? ", " + std::to_string(slices) + " slices" : std::string()) +
-                          ") are not built; call " + prep + " first");
-            BSMR_CHECK(st);
-            BSMR_CHECK(build_bwdp(p, D, Dv, slices, prep));
-        }
-        const Plan::AttentionPanelsState& F = p.attention_panels;
+        BSMR_CHECK(panel_build_missing(
+            LaunchSite{s, who, prep, D, dtype}, [&] { return bwdp_ready(p, D, Dv, slices); },
+            [&] {
+                return "the panel backward's lists (or their scratch for D = " + std::to_string(D) + ", Dv = " + std::to_string(Dv) +
+                       panel_slices_clause(slices) + ")";
+            },
+            [&] { return build_bwdp(p, D, Dv, slices, prep); }));
+        const Plan::PanelListState &R = p.panel_rows, &C = p.panel_cols;
         const Plan::AttentionBwdPanelsState& B = p.attention_bwd_panels;
-        r.items = F.items.data();
-        r.steps = F.steps.data();
-        r.rows = F.rows.data();
-        r.nItems = F.nItems;
-        r.partials = F.partials;
+        r.items = R.items.data();
+        r.steps = R.steps.data();
+        r.rows = R.rows.data();
+        r.nItems = R.nItems;
+        r.partials = R.partials;
         r.P0 = B.rowScratch.data();
-        rreds = F.reds.data();
-        rowReds = F.nReds;
-        cs.items = B.citems.data();
-        cs.steps = B.csteps.data();
-        cs.nItems = B.colItems;
-        cs.partials = B.colPartials;
+        rreds = R.reds.data();
+        rowReds = R.nReds;
+        cs.items = C.items.data();
+        cs.steps = C.steps.data();
+        cs.nItems = C.nItems;
+        cs.partials = C.partials;
         cs.P0 = B.colScratch.data();
-        creds = B.creds.data();
-        colReds = B.colReds;
+        creds = C.reds.data();
+        colReds = C.nReds;
         delta = B.delta.data();
     }
     cs.P1 = cs.P0 ? cs.P0 + static_cast<size_t>(slices) * cs.partials * PANEL_ROWS * D : nullptr;
@@ -519,34 +491,14 @@ int bwdp_launch(const char* who, const char* prep, const bsmr_plan* plan, u32 ba
 
     BSMR_CHECK(attn_bwd_launch_delta(r.GO, attn_op_bytes(x.O, batches, heads, p.M, 4u), delta, batches, heads, p.M, D, Dv, 2u, s));
     const bool f16 = dtype == BSMR_F16;
-    auto side = [&](const BwdPanelArgs& a, bool rows, const PanelRed* reds, u32 nReds, u32 q4) -> int {
-        if (a.nItems) {
-            const BwdPanelFn fn = f16 ? pick_d<BSMR_F16>(rows, D, Dv) : pick_d<BSMR_BF16>(rows, D, Dv);
-            hipLaunchKernelGGL(fn, dim3((a.nItems + PANEL_WAVES - 1) / PANEL_WAVES, heads, batches), dim3(PANEL_WAVES * 64), 0,
-                               s, a);
-            BSMR_HIP(hipGetLastError());
-        }
-        if (nReds) {
-            const size_t threads = static_cast<size_t>(nReds) * PANEL_ROWS * q4;
-            hipLaunchKernelGGL(k_attention_bwd_panels_reduce, dim3(static_cast<u32>((threads + 255) / 256), heads, batches),
-                               dim3(256), 0, s, a, reds, nReds, D, Dv);
-            BSMR_HIP(hipGetLastError());
-        }
-        return BSMR_OK;
+    auto side = [&](const BwdPanelArgs& a, bool rows, const PanelRed* reds, u32 nReds, u32 q4) {
+        const dim3 outer(1, heads, batches);
+        return panel_launch(s, f16 ? pick_d<BSMR_F16>(rows, D, Dv) : pick_d<BSMR_BF16>(rows, D, Dv), a, a.nItems, outer,
+                            k_attention_bwd_panels_reduce, reds, nReds, q4, outer, D, Dv);
     };
     if (x.GQ) BSMR_CHECK(side(r, true, rreds, rowReds, D / 4u));
     if (x.GK || x.GV) BSMR_CHECK(side(cs, false, creds, colReds, (x.GK ? D / 4u : 0u) + (x.GV ? Dv / 4u : 0u)));
     return BSMR_OK;
-}
-
-// the prepare calls carry no dtype
-int bwdp_prepare_args(const char* who, const bsmr_plan* plan, u32 D, u32 Dv, u32 slices) {
-    if (!plan) {
-        set_error(std::string(who) + ": null plan");
-        return BSMR_ERR_INVALID;
-    }
-    BSMR_CHECK(attn_check_slices(who, slices));
-    return bwdp_validate_dims(who, D, Dv, BSMR_F16);
 }
 
 }  // namespace
@@ -555,39 +507,20 @@ int bwdp_prepare_args(const char* who, const bsmr_plan* plan, u32 D, u32 Dv, u32
 // other's role and no order, so a column panel is 16 consecutive columns. The panel SpMM's columns
 // side (spmm_panels.hip) runs over these very lists and builds them through this when no backward has
 int attn_bwd_panels_build_col_lists(const Plan& p, const char* who) {
-    Plan::AttentionBwdPanelsState& B = p.attention_bwd_panels;
+    if (p.panel_cols.built) return BSMR_OK;
     const hipStream_t s = p.stream;
-    if (!B.built) {
-        std::vector<u32> hrp, hci, trp, tci;
-        BSMR_CHECK(p.rowptr.download(hrp, s));
-        BSMR_CHECK(p.colidx.download(hci, s));
-        PanelLists L;
-        std::string err;
-        if (attention_pattern_transpose(p.M, p.N, hrp.data(), hci.data(), trp, tci, err)) {
-            set_error(std::string(who) + ": " + err);
-            return BSMR_ERR_INVALID;
-        }
-        if (const int st = attention_panel_lists(p.N, p.M, trp.data(), tci.data(), nullptr, 0, L, err)) {
-            set_error(std::string(who) + ": " + err);
-            return st == 2 ? BSMR_ERR_UNSUPPORTED : BSMR_ERR_INVALID;
-        }
-        if (L.nItems > (1ull << 31)) {
-            set_error(std::string(who) + ": more than 2^31 items");
-            return BSMR_ERR_UNSUPPORTED;
-        }
-        BSMR_CHECK(B.csteps.upload(L.steps.data(), L.steps.size(), s));
-        BSMR_CHECK(B.citems.upload(L.items.data(), L.items.size(), s));
-        BSMR_CHECK(B.creds.upload(L.reds.data(), L.reds.size(), s));
-        BSMR_HIP(hipStreamSynchronize(s));
-        B.colItems = static_cast<u32>(L.nItems);
-        B.colSteps = static_cast<u32>(L.nSteps);
-        B.colReds = static_cast<u32>(L.reds.size());
-        B.colPanels = L.panels;
-        B.colSplit = L.splitPanels;
-        B.colPartials = L.partials;
-        B.built = true;
+    std::vector<u32> hrp, hci, trp, tci;
+    BSMR_CHECK(p.rowptr.download(hrp, s));
+    BSMR_CHECK(p.colidx.download(hci, s));
+    PanelLists L;
+    std::string err;
+    if (attention_pattern_transpose(p.M, p.N, hrp.data(), hci.data(), trp, tci, err)) {
+        set_error(std::string(who) + ": " + err);
+        return BSMR_ERR_INVALID;
     }
-    return BSMR_OK;
+    const int st = attention_panel_lists(p.N, p.M, trp.data(), tci.data(), nullptr, 0, L, err);
+    L.rows.clear();  // (the identity: a column is its position, and the kernels take a null order)
+    return panel_lists_upload(p, p.panel_cols, st, err, L, who);
 }
 
 }  // namespace bsmr
@@ -618,7 +551,7 @@ extern "C" int bsmr_attention_backward_panels(const bsmr_plan* plan, const void*
     }
     float c;
     BSMR_CHECK(attn_validate_scale(who, scale, &c));
-    BSMR_CHECK(bwdp_validate_dims(who, D, Dv, dtype));
+    BSMR_CHECK(panel_validate_dims(who, D, Dv, dtype, false));
     const Plan& p = plan->p;
     const bsmr_attention_operand q = attention_dense_operand(dQ, 1, p.M, D), k = attention_dense_operand(dK, 1, p.N, D),
                                  v = attention_dense_operand(dV, 1, p.N, Dv), o = attention_dense_operand(dO, 1, p.M, Dv),
@@ -650,7 +583,7 @@ extern "C" int bsmr_attention_backward_panels_heads(const bsmr_plan* plan, uint3
     }
     float c;
     BSMR_CHECK(attn_validate_scale(who, scale, &c));
-    BSMR_CHECK(bwdp_validate_dims(who, D, Dv, dtype));
+    BSMR_CHECK(panel_validate_dims(who, D, Dv, dtype, false));
     const Plan& p = plan->p;
     BSMR_CHECK(attn_check_operand(who, "Q", Q, batches, heads, p.M, D, 2u, false));
     BSMR_CHECK(attn_check_operand(who, "K", K, batches, heads, p.N, D, 2u, false));
@@ -668,21 +601,21 @@ extern "C" int bsmr_attention_backward_panels_heads(const bsmr_plan* plan, uint3
 extern "C" int bsmr_plan_prepare_attention_backward_panels_heads(const bsmr_plan* plan, uint32_t D, uint32_t Dv,
                                                                  uint32_t slices) {
     const char* who = "bsmr_plan_prepare_attention_backward_panels_heads";
-    BSMR_CHECK(bwdp_prepare_args(who, plan, D, Dv, slices));
+    BSMR_CHECK(panel_prepare_args(who, plan, D, Dv, slices, false));
     std::lock_guard<std::mutex> g(plan->p.layout_mu);
     return build_bwdp(plan->p, D, Dv, slices, who);
 }
 
 extern "C" int bsmr_plan_prepare_attention_backward_panels(const bsmr_plan* plan, uint32_t D, uint32_t Dv) {
     const char* who = "bsmr_plan_prepare_attention_backward_panels";
-    BSMR_CHECK(bwdp_prepare_args(who, plan, D, Dv, 1));
+    BSMR_CHECK(panel_prepare_args(who, plan, D, Dv, 1, false));
     std::lock_guard<std::mutex> g(plan->p.layout_mu);
     return build_bwdp(plan->p, D, Dv, 1, who);
 }
 
 extern "C" int bsmr_plan_attention_backward_panels_heads_prepared(const bsmr_plan* plan, uint32_t D, uint32_t Dv,
                                                                   uint32_t slices) {
-    if (bwdp_prepare_args("bsmr_plan_attention_backward_panels_heads_prepared", plan, D, Dv, slices) != BSMR_OK) return 0;
+    if (panel_prepare_args("bsmr_plan_attention_backward_panels_heads_prepared", plan, D, Dv, slices, false) != BSMR_OK) return 0;
     std::lock_guard<std::mutex> g(plan->p.layout_mu);
     return bwdp_ready(plan->p, D, Dv, slices) ? 1 : 0;
 }
@@ -698,22 +631,13 @@ extern "C" int bsmr_plan_attention_backward_panels_stats(const bsmr_plan* plan, 
     }
     const Plan& p = plan->p;
     std::lock_guard<std::mutex> g(p.layout_mu);
-    const Plan::AttentionPanelsState& F = p.attention_panels;
     const Plan::AttentionBwdPanelsState& B = p.attention_bwd_panels;
     *out = bsmr_attention_backward_panels_stats{};
-    if (B.built && F.built) {
-        out->row_panels = F.panels;
-        out->row_items = F.nItems;
-        out->row_steps = F.nSteps;
-        out->row_split_panels = F.splitPanels;
-        out->row_partials = F.partials;
-        out->row_fill_permille = panel_fill_permille(p.nnz, F.nSteps);
-        out->col_panels = B.colPanels;
-        out->col_items = B.colItems;
-        out->col_steps = B.colSteps;
-        out->col_split_panels = B.colSplit;
-        out->col_partials = B.colPartials;
-        out->col_fill_permille = panel_fill_permille(p.nnz, B.colSteps);
+    if (p.panel_cols.built && p.panel_rows.built) {
+        panel_list_stats(p.panel_rows, p.nnz, out->row_panels, out->row_items, out->row_steps, out->row_split_panels,
+                         out->row_partials, out->row_fill_permille);
+        panel_list_stats(p.panel_cols, p.nnz, out->col_panels, out->col_items, out->col_steps, out->col_split_panels,
+                         out->col_partials, out->col_fill_permille);
         out->row_scratch_bytes = B.rowScratch.size() * sizeof(float);
         out->col_scratch_bytes = B.colScratch.size() * sizeof(float);
         out->delta_bytes = B.delta.size() * sizeof(float);

@@ -66,14 +66,6 @@ u32 attn_forward_chunk();
 // spmm_lists at side 1 over the plan's CSR in the plan's reordered row order, `chunk` entries per
 // segment; layout_mu held. Synchronous on the plan's stream. `who` names the caller in errors
 int attn_row_lists(const Plan& p, u32 chunk, const char* who, SpmmLists& L);
-// the panel lists of the plan's rows (Plan::AttentionPanelsState rows / steps / items / reds), built
-// once (attention_panels.hip): the panel backward's rows side runs over the forward's lists;
-// layout_mu held. Synchronous on the plan's stream
-int attn_panels_build_lists(const Plan& p, const char* who);
-// the panel lists of the plan's columns (Plan::AttentionBwdPanelsState csteps / citems / creds), built
-// once (attention_bwd_panels.hip): the panel SpMM's columns side runs over the panel backward's
-// lists; layout_mu held. Synchronous on the plan's stream
-int attn_bwd_panels_build_col_lists(const Plan& p, const char* who);
 // the launch of k_attention_bwd_delta (attention_bwd.hip): delta[slice][i] = dot(GO[i,:], O[i,:]) in
 // the lane order of the gather backward's g, for operands of `esz` bytes per element
 int attn_bwd_launch_delta(const AttnOpBytes& GO, const AttnOpBytes& O, float* delta, u32 batches, u32 heads, u32 M, u32 D,

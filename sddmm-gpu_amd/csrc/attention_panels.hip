@@ -7,8 +7,9 @@
 // (attention_panels.hpp): up to PANEL_ITEM_STEPS steps of 32 columns of one panel's column union,
 // and loads every K and V row of the union once for the panel's 16 rows. Both products run on
 // v_mfma_f32_16x16x32_{f16,bf16}, transposed, so that every per-row quantity of query row r lives
-// on the lanes l with (l & 15) == r and nothing is shuffled between the two products. With
-// r = l & 15 and g = l >> 4:
+// on the lanes l with (l & 15) == r and nothing is shuffled between the two products. The lane
+// mapping, the k-slot order and the stage layout with its bank arithmetic are panel_mfma.hpp's.
+// With r = l & 15 and g = l >> 4:
 //   Q        lane (r, g) keeps Q[row r][32 s + 8 g, +8) of every k-step s in registers (D / 32
 //            16-byte loads for the whole item; a row past a short panel's end is zeros);
 //   scores   per step and 16-column tile, S^T = K_tile Q^T: the A operand of lane (i, g) is the
@@ -25,15 +26,10 @@
 //            of its own eight columns per step (l = l f + sum t, in column order); the four lanes
 //            of a row are added in g order at the end;
 //   O        O^T += V^T P^T per 16 columns of Dv: the B operand is the lane's eight t rounded to
-//            the operand type (k-slot 8 g + j is step column 4 g + j for j < 4, 16 + 4 g + j - 4
-//            else), the A operand V[those eight columns][dv]. The step's 32 V rows are staged in
-//            LDS by 16-byte loads and stores, rows 2 Dv + 16 bytes apart; lane (i, g) reads the
-//            32-bit word of elements (32 n + 2 i, 32 n + 2 i + 1) of its eight rows and splits it
-//            with two byte permutes per row pair into the A operands of two MFMAs: the even
-//            elements of [32 n, +32) and the odd ones. One instruction's 64 reads fall on 64
-//            different banks: the word index is (4 g + j)(Dv / 2 + 4) + 16 n + i = 16 g + i + const
-//            (mod 64). Lane (r, g) then holds O[row r][32 n + 8 g, +8): the row's rescale by f,
-//            the final 1 / l and two 16-byte stores per pair sit on the lane that owns the row.
+//            the operand type (pack8), the A operand V[those eight columns][dv] out of the step's
+//            32 staged V rows (staged_pair). Lane (r, g) then holds O[row r][32 n + 8 g, +8): the
+//            row's rescale by f, the final 1 / l and two 16-byte stores per pair sit on the lane
+//            that owns the row.
 // An item that is its panel's only one stores acc / l and m scale + ln l; an item of a split
 // panel stores (m, l, acc) per row to plan-owned scratch and k_attention_panels_reduce combines
 // the items as k_attention_reduce does: M = max m_i, every partial scaled once by 2^((m_i - M) c)
@@ -58,6 +54,7 @@
 #include "attention_layout.hpp"
 #include "attention_panels.hpp"
 #include "attention_panels_args.hpp"
+#include "panel_host.hpp"
 #include "panel_mfma.hpp"
 #include "plan.hpp"
 #include "seg_walk.hpp"  // exp2_hw
@@ -93,9 +90,7 @@ void k_attention_panels(const PanelArgs a) {
     const bool live = it.row0 + r < a.M;  // (a row of a short last panel is neither loaded nor stored)
     const u32 row = live ? a.rows[it.row0 + r] : 0u;
     uint4 q[KS];
-#pragma unroll
-    for (int s = 0; s < KS; ++s)
-        q[s] = live ? load16(Qs + static_cast<size_t>(row) * a.Q.row + (32u * s + 8u * g) * 2u) : make_uint4(0, 0, 0, 0);
+    panel_row_operand(q, Qs + static_cast<size_t>(row) * a.Q.row, live, g);
 
     float m = -INFINITY, l = 0.f;
     f32x4 acc[2 * NP];
@@ -147,8 +142,8 @@ void k_attention_panels(const PanelArgs a) {
         float p[8];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            p[j] = (mask >> (4u * g + j)) & 1u ? s0[j] : -INFINITY;
-            p[4 + j] = (mask >> (16u + 4u * g + j)) & 1u ? s1[j] : -INFINITY;
+            p[j] = (mask >> panel_slot(g, j)) & 1u ? s0[j] : -INFINITY;
+            p[4 + j] = (mask >> panel_slot(g, 4 + j)) & 1u ? s1[j] : -INFINITY;
         }
         float ms = p[0];
 #pragma unroll
@@ -197,13 +192,7 @@ void k_attention_panels(const PanelArgs a) {
         if (g == 0 && a.lse) a.lse[slice * a.M + row] = m * a.scale + logf(lt);
     } else {
         const size_t slot = (slice * a.partials + it.part) * PANEL_ROWS + r;
-        float* o = a.pacc + slot * DV + 8u * g;
-#pragma unroll
-        for (int n = 0; n < NP; ++n) {
-            const f32x4 e = acc[2 * n], d = acc[2 * n + 1];
-            *reinterpret_cast<float4*>(o + 32 * n) = make_float4(e[0], d[0], e[1], d[1]);
-            *reinterpret_cast<float4*>(o + 32 * n + 4) = make_float4(e[2], d[2], e[3], d[3]);
-        }
+        store_acc<NP>(a.pacc + slot * DV + 8u * g, acc);
         if (g == 0) {
             a.pml[2u * slot] = m;
             a.pml[2u * slot + 1u] = lt;
@@ -271,34 +260,74 @@ PanelFn pick_d(u32 D, u32 Dv) {
     }
 }
 
-bool panel_dim(u32 d) { return d == 32 || d == 64 || d == 128 || d == 256; }
-
-// fp16 / bf16 and the compile-time forms; else BSMR_ERR_UNSUPPORTED with the message set
-int panels_validate_dims(const char* who, u32 D, u32 Dv, int dtype) {
-    if ((dtype != BSMR_F16 && dtype != BSMR_BF16) || !panel_dim(D) || !panel_dim(Dv)) {
-        set_error(std::string(who) + ": dtype must be BSMR_F16 or BSMR_BF16 and D and Dv each one of 32, 64, 128, 256");
-        return BSMR_ERR_UNSUPPORTED;
-    }
-    return BSMR_OK;
+size_t panels_scratch_floats(const Plan& p, u32 Dv, u32 slices) {
+    return attn_sat_mul(attn_sat_mul(slices, p.panel_rows.partials, PANEL_ROWS), Dv + 2u);
 }
 
-size_t panels_scratch_floats(const Plan::AttentionPanelsState& S, u32 Dv, u32 slices) {
-    return attn_sat_mul(attn_sat_mul(slices, S.partials, PANEL_ROWS), Dv + 2u);
-}
-
-bool panels_ready(const Plan::AttentionPanelsState& S, u32 Dv, u32 slices) {
-    return S.built && S.scratch.size() >= panels_scratch_floats(S, Dv, slices);
+bool panels_ready(const Plan& p, u32 Dv, u32 slices) {
+    return p.panel_rows.built && p.attention_panels.scratch.size() >= panels_scratch_floats(p, Dv, slices);
 }
 
 // build the lists (once, attn_panels_build_lists) and size the per-slice scratch for (Dv, slices): it
 // grows and never shrinks; layout_mu held. Synchronous on the plan's stream.
 int build_panels(const Plan& p, u32 Dv, u32 slices, const char* who) {
     BSMR_CHECK(attn_panels_build_lists(p, who));
-    const Plan::AttentionPanelsState& S = p.attention_panels;
-    return p.attention_panels.scratch.grow(panels_scratch_floats(S, Dv, slices));
+    return p.attention_panels.scratch.grow(panels_scratch_floats(p, Dv, slices));
 }
 
+// the 16-bit form's kernel; the dims are validated
+PanelFn panels_kernel(u32 D, u32 Dv, int dtype) { return dtype == BSMR_F16 ? pick_d<BSMR_F16>(D, Dv) : pick_d<BSMR_BF16>(D, Dv); }
+
 }  // namespace
+
+int panel_validate_dims(const char* who, u32 D, u32 Dv, int dtype, bool with256) {
+    auto dim = [&](u32 d) { return d == 32 || d == 64 || d == 128 || (with256 && d == 256); };
+    if ((dtype != BSMR_F16 && dtype != BSMR_BF16) || !dim(D) || !dim(Dv)) {
+        set_error(std::string(who) + ": dtype must be BSMR_F16 or BSMR_BF16 and D and Dv each one of 32, 64, 128" +
+                  (with256 ? ", 256" : ""));
+        return BSMR_ERR_UNSUPPORTED;
+    }
+    return BSMR_OK;
+}
+
+int panel_prepare_args(const char* who, const bsmr_plan* plan, u32 D, u32 Dv, u32 slices, bool with256) {
+    if (!plan) {
+        set_error(std::string(who) + ": null plan");
+        return BSMR_ERR_INVALID;
+    }
+    BSMR_CHECK(attn_check_slices(who, slices));
+    return panel_validate_dims(who, D, Dv, BSMR_F16, with256);
+}
+
+int attn_panels_check_dense(const char* who, const char* names, const bsmr_plan* plan, const void* dQ, const void* dK,
+                            const void* dV, const void* dO, const float* dLse) {
+    if (!plan) {
+        set_error(std::string(who) + ": null plan");
+        return BSMR_ERR_INVALID;
+    }
+    if (!dQ || !dK || !dV || !dO) {
+        set_error(std::string(who) + ": null device pointer");
+        return BSMR_ERR_INVALID;
+    }
+    if (!attn_aligned16(dQ) || !attn_aligned16(dK) || !attn_aligned16(dV) || !attn_aligned16(dO) ||
+        (reinterpret_cast<uintptr_t>(dLse) & 3u)) {
+        set_error(std::string(who) + ": " + names + " must be 16-byte aligned");
+        return BSMR_ERR_INVALID;
+    }
+    return BSMR_OK;
+}
+
+int attn_panels_check_heads(const char* who, const bsmr_plan* plan, const float* dLse) {
+    if (!plan) {
+        set_error(std::string(who) + ": null plan");
+        return BSMR_ERR_INVALID;
+    }
+    if (reinterpret_cast<uintptr_t>(dLse) & 3u) {
+        set_error(std::string(who) + ": dLse must be 4-byte aligned");
+        return BSMR_ERR_INVALID;
+    }
+    return BSMR_OK;
+}
 
 int attn_panels_launch(const char* who, const char* prep, const bsmr_plan* plan, PanelFn fn, u32 batches, u32 heads,
                        const bsmr_attention_operand& Q, const bsmr_attention_operand& K, const bsmr_attention_operand& V,
@@ -306,31 +335,25 @@ int attn_panels_launch(const char* who, const char* prep, const bsmr_plan* plan,
                        const bsmr_attention_operand& O, float* dLse, void* stream) {
     const Plan& p = plan->p;
     const hipStream_t s = static_cast<hipStream_t>(stream);
-    const Plan::AttentionPanelsState& S = p.attention_panels;
+    const Plan::PanelListState& L = p.panel_rows;
     const u32 slices = batches * heads;  // (both at most 65535)
     PanelArgs a{};
     const PanelRed* reds = nullptr;
     u32 nReds = 0;
     {
         std::lock_guard<std::mutex> g(p.layout_mu);
-        if (!panels_ready(S, Dv, slices)) {
-            const LaunchSite at{s, who, prep, D, dtype};
-            const int st = lazy_build_guard(at);
-            if (st == BSMR_ERR_NOT_PREPARED)
-                set_error(std::string(who) + ": stream is capturing and the panel lists (or their scratch for Dv = " +
-                          std::to_string(Dv) + (slices > 1 ? ", " + std::to_string(slices) + " slices" : std::string()) +
-                          ") are not built; call " + prep + " first");
-            BSMR_CHECK(st);
-            BSMR_CHECK(build_panels(p, Dv, slices, prep));
-        }
-        a.items = S.items.data();
-        a.steps = S.steps.data();
-        a.rows = S.rows.data();
-        a.nItems = S.nItems;
-        a.partials = S.partials;
-        a.pacc = S.scratch.data();
-        reds = S.reds.data();
-        nReds = S.nReds;
+        BSMR_CHECK(panel_build_missing(
+            LaunchSite{s, who, prep, D, dtype}, [&] { return panels_ready(p, Dv, slices); },
+            [&] { return "the panel lists (or their scratch for Dv = " + std::to_string(Dv) + panel_slices_clause(slices) + ")"; },
+            [&] { return build_panels(p, Dv, slices, prep); }));
+        a.items = L.items.data();
+        a.steps = L.steps.data();
+        a.rows = L.rows.data();
+        a.nItems = L.nItems;
+        a.partials = L.partials;
+        a.pacc = p.attention_panels.scratch.data();
+        reds = L.reds.data();
+        nReds = L.nReds;
     }
     a.pml = a.pacc ? a.pacc + static_cast<size_t>(slices) * a.partials * PANEL_ROWS * Dv : nullptr;
     a.Q = attn_op_bytes(&Q, batches, heads, p.M, 2u);
@@ -343,74 +366,50 @@ int attn_panels_launch(const char* who, const char* prep, const bsmr_plan* plan,
     a.c = c;
     a.scale = scale;
     a.vscale = vscale;
-    if (a.nItems) {
-        const u32 grid = (a.nItems + PANEL_WAVES - 1) / PANEL_WAVES;
-        hipLaunchKernelGGL(fn, dim3(grid, heads, batches), dim3(PANEL_WAVES * 64), 0, s, a);
-        BSMR_HIP(hipGetLastError());
-    }
-    if (nReds) {
-        const size_t threads = static_cast<size_t>(nReds) * PANEL_ROWS * (Dv / 4u);
-        const dim3 rgrid(static_cast<u32>((threads + 255) / 256), heads, batches);
-        hipLaunchKernelGGL(k_attention_panels_reduce, rgrid, dim3(256), 0, s, a, reds, nReds, Dv);
-        BSMR_HIP(hipGetLastError());
-    }
-    return BSMR_OK;
+    const dim3 outer(1, heads, batches);
+    return panel_launch(s, fn, a, a.nItems, outer, k_attention_panels_reduce, reds, nReds, Dv / 4u, outer, Dv);
 }
 
-namespace {
-
-// the 16-bit form's kernel; the dims are validated
-PanelFn panels_kernel(u32 D, u32 Dv, int dtype) { return dtype == BSMR_F16 ? pick_d<BSMR_F16>(D, Dv) : pick_d<BSMR_BF16>(D, Dv); }
-
-// the prepare calls carry no dtype
-int panels_prepare_args(const char* who, const bsmr_plan* plan, u32 D, u32 Dv, u32 slices) {
-    if (!plan) {
-        set_error(std::string(who) + ": null plan");
-        return BSMR_ERR_INVALID;
-    }
-    BSMR_CHECK(attn_check_slices(who, slices));
-    return panels_validate_dims(who, D, Dv, BSMR_F16);
-}
-
-}  // namespace
-
-// the panel lists of the plan's rows (once): the panel backward's rows side launches over the same
-// lists and builds them through this when no forward has; layout_mu held
-int attn_panels_build_lists(const Plan& p, const char* who) {
-    Plan::AttentionPanelsState& S = p.attention_panels;
+int panel_lists_upload(const Plan& p, Plan::PanelListState& S, int st, const std::string& err, const PanelLists& L,
+                       const char* who) {
     const hipStream_t s = p.stream;
-    if (!S.built) {
-        std::vector<u32> hrp, hci, hrows;
-        BSMR_CHECK(p.rowptr.download(hrp, s));
-        BSMR_CHECK(p.colidx.download(hci, s));
-        BSMR_CHECK(p.rows.download(hrows, s));
-        hrows.resize(std::min<size_t>(hrows.size(), p.R));
-        PanelLists L;
-        std::string err;
-        // (the rows the plan's order does not name, its empty ones, get trailing panels of 0 steps; the
-        // lists would compute them from their entries all the same)
-        if (const int st = attention_panel_lists(p.M, p.N, hrp.data(), hci.data(), hrows.data(), static_cast<u32>(hrows.size()), L, err)) {
-            set_error(std::string(who) + ": " + err);
-            return st == 2 ? BSMR_ERR_UNSUPPORTED : BSMR_ERR_INVALID;  // 2: past the lists' capacity
-        }
-        if (L.nItems > (1ull << 31)) {
-            set_error(std::string(who) + ": more than 2^31 items");
-            return BSMR_ERR_UNSUPPORTED;
-        }
-        BSMR_CHECK(S.rows.upload(L.rows.data(), L.rows.size(), s));
-        BSMR_CHECK(S.steps.upload(L.steps.data(), L.steps.size(), s));
-        BSMR_CHECK(S.items.upload(L.items.data(), L.items.size(), s));
-        BSMR_CHECK(S.reds.upload(L.reds.data(), L.reds.size(), s));
-        BSMR_HIP(hipStreamSynchronize(s));
-        S.nItems = static_cast<u32>(L.nItems);
-        S.nSteps = static_cast<u32>(L.nSteps);
-        S.nReds = static_cast<u32>(L.reds.size());
-        S.panels = L.panels;
-        S.splitPanels = L.splitPanels;
-        S.partials = L.partials;
-        S.built = true;
+    if (st) {
+        set_error(std::string(who) + ": " + err);
+        return st == 2 ? BSMR_ERR_UNSUPPORTED : BSMR_ERR_INVALID;  // 2: past the lists' capacity
     }
+    if (L.nItems > (1ull << 31)) {
+        set_error(std::string(who) + ": more than 2^31 items");
+        return BSMR_ERR_UNSUPPORTED;
+    }
+    BSMR_CHECK(S.rows.upload(L.rows.data(), L.rows.size(), s));
+    BSMR_CHECK(S.steps.upload(L.steps.data(), L.steps.size(), s));
+    BSMR_CHECK(S.items.upload(L.items.data(), L.items.size(), s));
+    BSMR_CHECK(S.reds.upload(L.reds.data(), L.reds.size(), s));
+    BSMR_HIP(hipStreamSynchronize(s));
+    S.nItems = static_cast<u32>(L.nItems);
+    S.nSteps = static_cast<u32>(L.nSteps);
+    S.nReds = static_cast<u32>(L.reds.size());
+    S.panels = L.panels;
+    S.splitPanels = L.splitPanels;
+    S.partials = L.partials;
+    S.built = true;
     return BSMR_OK;
+}
+
+int attn_panels_build_lists(const Plan& p, const char* who) {
+    if (p.panel_rows.built) return BSMR_OK;
+    const hipStream_t s = p.stream;
+    std::vector<u32> hrp, hci, hrows;
+    BSMR_CHECK(p.rowptr.download(hrp, s));
+    BSMR_CHECK(p.colidx.download(hci, s));
+    BSMR_CHECK(p.rows.download(hrows, s));
+    hrows.resize(std::min<size_t>(hrows.size(), p.R));
+    PanelLists L;
+    std::string err;
+    // (the rows the plan's order does not name, its empty ones, get trailing panels of 0 steps; the
+    // lists would compute them from their entries all the same)
+    const int st = attention_panel_lists(p.M, p.N, hrp.data(), hci.data(), hrows.data(), static_cast<u32>(hrows.size()), L, err);
+    return panel_lists_upload(p, p.panel_rows, st, err, L, who);
 }
 
 }  // namespace bsmr
@@ -420,22 +419,10 @@ using namespace bsmr;
 extern "C" int bsmr_attention_panels(const bsmr_plan* plan, const void* dQ, const void* dK, const void* dV, uint32_t D,
                                      uint32_t Dv, int dtype, float scale, float* dO, float* dLse, void* stream) {
     const char* who = "bsmr_attention_panels";
-    if (!plan) {
-        set_error("bsmr_attention_panels: null plan");
-        return BSMR_ERR_INVALID;
-    }
-    if (!dQ || !dK || !dV || !dO) {
-        set_error("bsmr_attention_panels: null device pointer");
-        return BSMR_ERR_INVALID;
-    }
-    if (!attn_aligned16(dQ) || !attn_aligned16(dK) || !attn_aligned16(dV) || !attn_aligned16(dO) ||
-        (reinterpret_cast<uintptr_t>(dLse) & 3u)) {
-        set_error("bsmr_attention_panels: dQ, dK, dV and dO must be 16-byte aligned");
-        return BSMR_ERR_INVALID;
-    }
+    BSMR_CHECK(attn_panels_check_dense(who, "dQ, dK, dV and dO", plan, dQ, dK, dV, dO, dLse));
     float c;
     BSMR_CHECK(attn_validate_scale(who, scale, &c));
-    BSMR_CHECK(panels_validate_dims(who, D, Dv, dtype));
+    BSMR_CHECK(panel_validate_dims(who, D, Dv, dtype, true));
     const Plan& p = plan->p;
     return attn_panels_launch(who, "bsmr_plan_prepare_attention_panels", plan, panels_kernel(D, Dv, dtype), 1, 1,
                               attention_dense_operand(dQ, 1, p.M, D), attention_dense_operand(dK, 1, p.N, D),
@@ -448,17 +435,10 @@ extern "C" int bsmr_attention_panels_heads(const bsmr_plan* plan, uint32_t batch
                                            const bsmr_attention_operand* V, uint32_t D, uint32_t Dv, int dtype, float scale,
                                            const bsmr_attention_operand* O, float* dLse, void* stream) {
     const char* who = "bsmr_attention_panels_heads";
-    if (!plan) {
-        set_error("bsmr_attention_panels_heads: null plan");
-        return BSMR_ERR_INVALID;
-    }
-    if (reinterpret_cast<uintptr_t>(dLse) & 3u) {
-        set_error("bsmr_attention_panels_heads: dLse must be 4-byte aligned");
-        return BSMR_ERR_INVALID;
-    }
+    BSMR_CHECK(attn_panels_check_heads(who, plan, dLse));
     float c;
     BSMR_CHECK(attn_validate_scale(who, scale, &c));
-    BSMR_CHECK(panels_validate_dims(who, D, Dv, dtype));
+    BSMR_CHECK(panel_validate_dims(who, D, Dv, dtype, true));
     const Plan& p = plan->p;
     BSMR_CHECK(attn_check_operand(who, "Q", Q, batches, heads, p.M, D, 2u, false));
     BSMR_CHECK(attn_check_operand(who, "K", K, batches, heads, p.N, D, 2u, false));
@@ -470,22 +450,22 @@ extern "C" int bsmr_attention_panels_heads(const bsmr_plan* plan, uint32_t batch
 
 extern "C" int bsmr_plan_prepare_attention_panels_heads(const bsmr_plan* plan, uint32_t D, uint32_t Dv, uint32_t slices) {
     const char* who = "bsmr_plan_prepare_attention_panels_heads";
-    BSMR_CHECK(panels_prepare_args(who, plan, D, Dv, slices));
+    BSMR_CHECK(panel_prepare_args(who, plan, D, Dv, slices, true));
     std::lock_guard<std::mutex> g(plan->p.layout_mu);
     return build_panels(plan->p, Dv, slices, who);
 }
 
 extern "C" int bsmr_plan_prepare_attention_panels(const bsmr_plan* plan, uint32_t D, uint32_t Dv) {
     const char* who = "bsmr_plan_prepare_attention_panels";
-    BSMR_CHECK(panels_prepare_args(who, plan, D, Dv, 1));
+    BSMR_CHECK(panel_prepare_args(who, plan, D, Dv, 1, true));
     std::lock_guard<std::mutex> g(plan->p.layout_mu);
     return build_panels(plan->p, Dv, 1, who);
 }
 
 extern "C" int bsmr_plan_attention_panels_heads_prepared(const bsmr_plan* plan, uint32_t D, uint32_t Dv, uint32_t slices) {
-    if (panels_prepare_args("bsmr_plan_attention_panels_heads_prepared", plan, D, Dv, slices) != BSMR_OK) return 0;
+    if (panel_prepare_args("bsmr_plan_attention_panels_heads_prepared", plan, D, Dv, slices, true) != BSMR_OK) return 0;
     std::lock_guard<std::mutex> g(plan->p.layout_mu);
-    return panels_ready(plan->p.attention_panels, Dv, slices) ? 1 : 0;
+    return panels_ready(plan->p, Dv, slices) ? 1 : 0;
 }
 
 extern "C" int bsmr_plan_attention_panels_prepared(const bsmr_plan* plan, uint32_t D, uint32_t Dv) {
@@ -499,17 +479,11 @@ extern "C" int bsmr_plan_attention_panels_stats(const bsmr_plan* plan, bsmr_atte
     }
     const Plan& p = plan->p;
     std::lock_guard<std::mutex> g(p.layout_mu);
-    const Plan::AttentionPanelsState& S = p.attention_panels;
     *out = bsmr_attention_panels_stats{};
     out->step_cols = PANEL_STEP_COLS;
     out->item_steps = PANEL_ITEM_STEPS;
-    if (S.built) {
-        out->panels = S.panels;
-        out->items = S.nItems;
-        out->steps = S.nSteps;
-        out->split_panels = S.splitPanels;
-        out->partials = S.partials;
-        out->fill_permille = panel_fill_permille(p.nnz, S.nSteps);
-    }
+    if (p.panel_rows.built)
+        panel_list_stats(p.panel_rows, p.nnz, out->panels, out->items, out->steps, out->split_panels, out->partials,
+                         out->fill_permille);
     return BSMR_OK;
 }

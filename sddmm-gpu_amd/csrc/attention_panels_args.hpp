@@ -31,6 +31,13 @@ using PanelFn = void (*)(const PanelArgs);
 __device__ __forceinline__ float shift_of(float m) { return m == -INFINITY ? 0.f : m; }
 __device__ __forceinline__ float inverse_of(float s) { return s == 0.f ? 0.f : 1.0f / s; }
 
+// The first checks of a dense entry point (a null plan, a null pointer, alignment; `names` is the
+// message's list of the four pointers) and of a heads entry point (a null plan, dLse's alignment);
+// else BSMR_ERR_INVALID with the message set. Defined in attention_panels.hip
+int attn_panels_check_dense(const char* who, const char* names, const bsmr_plan* plan, const void* dQ, const void* dK,
+                            const void* dV, const void* dO, const float* dLse);
+int attn_panels_check_heads(const char* who, const bsmr_plan* plan, const float* dLse);
+
 // The launches of a panel forward, arguments already validated: `fn` over the plan's items, then
 // k_attention_panels_reduce over its split panels. K and V hold elements of kvBytes bytes; the
 // lists and the scratch are built first unless `stream` is capturing (BSMR_ERR_NOT_PREPARED, naming

@@ -22,8 +22,8 @@
 //   V stage  the step's 32 V rows are staged as bytes by 16-byte loads and stores (chunk
 //            x = 64 u + lane is 16 bytes of row x / (Dv / 16): each row is fetched once per step),
 //            rows Dv + 16 bytes apart: 32 (Dv + 16) bytes per wave, against 32 (2 Dv + 16);
-//   V read   lane (i, g) reads the 32-bit word 16 n + i of its eight rows (k-slot order: step column
-//            4 g + j for j < 4, 16 + 4 g + j - 4 else): four consecutive output columns
+//   V read   lane (i, g) reads the 32-bit word 16 n + i of its eight rows (the k-slot order of
+//            panel_mfma.hpp): four consecutive output columns
 //            64 n + 4 i + b of each row. Per row pair two v_perm_b32 re-deal the two words into
 //            (row j, row j + 1) byte pairs, b = 0, 1 in one word and b = 2, 3 in the other, and the
 //            packed convert widens each pair into one register of the A operand of MFMA b: eight
@@ -73,10 +73,7 @@ template <int DT, u32 ROW>
 __device__ __forceinline__ void staged_quad(const char* tile, u32 n, u32 i, u32 g, uint4 (&op)[4]) {
     u32 w[8];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const u32 cc = (j < 4 ? 4u * g + j : 16u + 4u * g + (j - 4));
-        w[j] = *reinterpret_cast<const u32*>(tile + cc * ROW + (16u * n + i) * 4u);
-    }
+    for (int j = 0; j < 8; ++j) w[j] = *reinterpret_cast<const u32*>(tile + panel_slot(g, j) * ROW + (16u * n + i) * 4u);
     u32 lo[4], hi[4];  // per row pair: bytes (b0, b0', b1, b1') and (b2, b2', b3, b3')
 #pragma unroll
     for (int jj = 0; jj < 4; ++jj) {
@@ -172,8 +169,8 @@ void k_attention_panels_kv8(const PanelArgs a) {
         float p[8];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            p[j] = (mask >> (4u * g + j)) & 1u ? s0[j] : -INFINITY;
-            p[4 + j] = (mask >> (16u + 4u * g + j)) & 1u ? s1[j] : -INFINITY;
+            p[j] = (mask >> panel_slot(g, j)) & 1u ? s0[j] : -INFINITY;
+            p[4 + j] = (mask >> panel_slot(g, 4 + j)) & 1u ? s1[j] : -INFINITY;
         }
         float ms = p[0];
 #pragma unroll
@@ -292,19 +289,7 @@ extern "C" int bsmr_attention_panels_kv8(const bsmr_plan* plan, const void* dQ, 
                                          uint32_t Dv, int dtype, int kv_dtype, float scale, float k_scale, float v_scale,
                                          float* dO, float* dLse, void* stream) {
     const char* who = "bsmr_attention_panels_kv8";
-    if (!plan) {
-        set_error("bsmr_attention_panels_kv8: null plan");
-        return BSMR_ERR_INVALID;
-    }
-    if (!dQ || !dK8 || !dV8 || !dO) {
-        set_error("bsmr_attention_panels_kv8: null device pointer");
-        return BSMR_ERR_INVALID;
-    }
-    if (!attn_aligned16(dQ) || !attn_aligned16(dK8) || !attn_aligned16(dV8) || !attn_aligned16(dO) ||
-        (reinterpret_cast<uintptr_t>(dLse) & 3u)) {
-        set_error("bsmr_attention_panels_kv8: dQ, dK8, dV8 and dO must be 16-byte aligned");
-        return BSMR_ERR_INVALID;
-    }
+    BSMR_CHECK(attn_panels_check_dense(who, "dQ, dK8, dV8 and dO", plan, dQ, dK8, dV8, dO, dLse));
     float eff, c;
     PanelFn fn;
     BSMR_CHECK(kv8_validate(who, D, Dv, dtype, kv_dtype, scale, k_scale, v_scale, &eff, &c, &fn));
@@ -320,14 +305,7 @@ extern "C" int bsmr_attention_panels_kv8_heads(const bsmr_plan* plan, uint32_t b
                                                int kv_dtype, float scale, float k_scale, float v_scale,
                                                const bsmr_attention_operand* O, float* dLse, void* stream) {
     const char* who = "bsmr_attention_panels_kv8_heads";
-    if (!plan) {
-        set_error("bsmr_attention_panels_kv8_heads: null plan");
-        return BSMR_ERR_INVALID;
-    }
-    if (reinterpret_cast<uintptr_t>(dLse) & 3u) {
-        set_error("bsmr_attention_panels_kv8_heads: dLse must be 4-byte aligned");
-        return BSMR_ERR_INVALID;
-    }
+    BSMR_CHECK(attn_panels_check_heads(who, plan, dLse));
     float eff, c;
     PanelFn fn;
     BSMR_CHECK(kv8_validate(who, D, Dv, dtype, kv_dtype, scale, k_scale, v_scale, &eff, &c, &fn));

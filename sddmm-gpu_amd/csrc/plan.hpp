@@ -288,21 +288,33 @@ struct Plan {
     };
     mutable AttentionState attention;
 
-    // fused sparse attention forward on matrix instructions (attention_panels.hip;
-    // bsmr_attention_panels): the launch order of the rows, the panels' steps, the items and the
-    // split panels (attention_panels.hpp), and their partials: slices x partials x 16 rows of Dv
-    // accumulator floats followed by slices x partials x 16 (m, l) pairs; the scratch holds what
-    // the largest slices x (Dv + 2) so far needs and never shrinks. Built on first use or by
-    // bsmr_plan_prepare_attention_panels / _heads, under layout_mu; a state of its own, which no
-    // other path reads or writes, and which depends on S and the row order only, so build_columns
-    // keeps it
-    struct AttentionPanelsState {
+    // a panel list on the device (attention_panels.hpp): the launch order of the destinations (empty
+    // where it is the identity), the panels' steps, the items, the split panels and the list's
+    // counters. The plan holds two, each built once, under layout_mu, by whichever panel family needs
+    // it first (panel_host.hpp: attn_panels_build_lists, attn_bwd_panels_build_col_lists) and never
+    // copied: panel_rows, panels of 16 rows of the plan's launch order, steps of 32 union columns
+    // (the attention forward and its e4m3 form, the panel backward's rows side, the panel SpMM's rows
+    // side); panel_cols, the same kind of lists of the transposed pattern, panels of 16 consecutive
+    // columns in ascending index, steps of 32 union rows (the panel backward's and the panel SpMM's
+    // columns side). They depend on S and the row order only, so build_columns keeps them
+    struct PanelListState {
         bool built = false;
         u32 nItems = 0, nReds = 0, nSteps = 0, panels = 0, splitPanels = 0, partials = 0;
         DevBuf<u32> rows;
         DevBuf<PanelStep> steps;
         DevBuf<PanelItem> items;
         DevBuf<PanelRed> reds;
+    };
+    mutable PanelListState panel_rows, panel_cols;
+    PanelListState& panel_lists(int side) const { return side == 1 ? panel_rows : panel_cols; }  // 1 rows, 2 columns
+
+    // fused sparse attention forward on matrix instructions (attention_panels.hip;
+    // bsmr_attention_panels) over panel_rows: the partials of the split panels, slices x partials x
+    // 16 rows of Dv accumulator floats followed by slices x partials x 16 (m, l) pairs; the scratch
+    // holds what the largest slices x (Dv + 2) so far needs and never shrinks. Built on first use or
+    // by bsmr_plan_prepare_attention_panels / _heads, under layout_mu; no other path reads or
+    // writes it
+    struct AttentionPanelsState {
         DevBuf<float> scratch;
     };
     mutable AttentionPanelsState attention_panels;
@@ -330,34 +342,24 @@ struct Plan {
     mutable AttentionBwdState attention_bwd;
 
     // fused sparse attention backward on matrix instructions (attention_bwd_panels.hip;
-    // bsmr_attention_backward_panels). The rows side runs over AttentionPanelsState's rows / steps /
-    // items / reds (built through attn_panels_build_lists when no forward has built them; never a
-    // second copy); the columns side over the same kind of lists of the transposed pattern: panels
-    // of 16 consecutive columns in ascending index, steps of 32 union rows. Per slice: M floats of
-    // delta, rowPartials x 16 x D floats of the split row panels, and colPartials x 16 x D followed
-    // by colPartials x 16 x Dv of the split column panels. Built on first use or by
-    // bsmr_plan_prepare_attention_backward_panels, under layout_mu; the buffers hold what the
-    // largest (D, Dv, slices) so far needs and never shrink. It reads no state of the gather
+    // bsmr_attention_backward_panels): the rows side runs over panel_rows, the columns side over
+    // panel_cols. Per slice: M floats of delta, rowPartials x 16 x D floats of the split row panels,
+    // and colPartials x 16 x D followed by colPartials x 16 x Dv of the split column panels. Built on
+    // first use or by bsmr_plan_prepare_attention_backward_panels, under layout_mu; the buffers hold
+    // what the largest (D, Dv, slices) so far needs and never shrink. It reads no state of the gather
     // forward, the gather backward or SpMM, and neither bsmr_plan_prepare_spmm nor build_columns
     // touches it
     struct AttentionBwdPanelsState {
-        bool built = false;
-        u32 colItems = 0, colReds = 0, colSteps = 0, colPanels = 0, colSplit = 0, colPartials = 0;
-        DevBuf<PanelStep> csteps;
-        DevBuf<PanelItem> citems;
-        DevBuf<PanelRed> creds;
         DevBuf<float> delta, rowScratch, colScratch;
     };
     mutable AttentionBwdPanelsState attention_bwd_panels;
 
-    // SpMM on matrix instructions, per panel (spmm_panels.hip; bsmr_spmm_panels / bsmr_spmm_t_panels).
-    // The rows side runs over AttentionPanelsState's rows / steps / items / reds, the columns side
-    // over AttentionBwdPanelsState's csteps / citems / creds (each built through its owner's builder
-    // when no attention call has; never a second copy). Its own, per side: where in V the entry of
-    // every set mask bit lies (spmm_panels.hpp: base, 16 per step; pos, one per entry) and the
-    // partial slots of the split panels: partials x 16 x scratchK floats followed by partials x 16
-    // running exponents. Built on first use or by bsmr_plan_prepare_spmm_panels, under layout_mu;
-    // the scratch grows and never shrinks; build_columns keeps all of it
+    // SpMM on matrix instructions, per panel (spmm_panels.hip; bsmr_spmm_panels / bsmr_spmm_t_panels):
+    // the rows side runs over panel_rows, the columns side over panel_cols. Its own, per side: where
+    // in V the entry of every set mask bit lies (spmm_panels.hpp: base, 16 per step; pos, one per
+    // entry) and the partial slots of the split panels: partials x 16 x scratchK floats followed by
+    // partials x 16 running exponents. Built on first use or by bsmr_plan_prepare_spmm_panels, under
+    // layout_mu; the scratch grows and never shrinks; build_columns keeps all of it
     struct SpmmPanelsSide {
         bool built = false;
         u32 scratchK = 0;

@@ -8,8 +8,8 @@
 // steps of 32 sources of one panel's union, every dense row of the union loaded once for the
 // panel's 16 destinations. It is the second product of attention_panels.hip with its lane mapping
 // (r = l & 15, g = l >> 4; panel_mfma.hpp), Y^T += X^T W^T per 16 columns of K:
-//   weights  lane (r, g) owns destination r's eight weights of a step, step slots 4 g + j (j < 4)
-//            and 16 + 4 g + j - 4: the entry of slot c is V[pos[base[r] + popcount(mask_r below c)]]
+//   weights  lane (r, g) owns destination r's eight weights of a step, step slots panel_slot(g, j)
+//            (the k-slot order): the entry of slot c is V[pos[base[r] + popcount(mask_r below c)]]
 //            (spmm_panels.hpp); a lane whose mask bit is clear issues no load and holds 0. Positions
 //            and values of step s + 1 are requested before the MFMAs of step s;
 //   pieces   an fp32 weight does not fit a 16-bit operand, and rounding it would lose a gradient of
@@ -48,6 +48,7 @@
 
 #include "attention_common.hpp"
 #include "attention_panels.hpp"
+#include "panel_host.hpp"
 #include "panel_mfma.hpp"
 #include "plan.hpp"
 #include "spmm_panels.hpp"
@@ -70,9 +71,6 @@ struct SpmmPanelArgs {
     int* pm;          // behind them: partials x 16 running exponents (fp16)
     u32 nItems, D, K;
 };
-
-// step slot of a lane's j-th weight (the k-slot order of pack8 and staged_pair)
-__device__ __forceinline__ u32 slot_of(u32 g, int j) { return j < 4 ? 4u * g + j : 16u + 4u * g + (j - 4); }
 
 template <int DT, int KS>
 __global__ __launch_bounds__(PANEL_WAVES * 64) __attribute__((amdgpu_waves_per_eu(2)))
@@ -110,7 +108,7 @@ void k_spmm_panels(const SpmmPanelArgs a) {
         const u32 mask = sp->masks[r], b = bp[r];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            const u32 c = slot_of(g, j);
+            const u32 c = panel_slot(g, j);
             p[j] = 0xFFFFFFFFu;
             if ((mask >> c) & 1u) p[j] = a.pos[b + __builtin_popcount(mask & ((1u << c) - 1u))];
         }
@@ -289,30 +287,11 @@ int spmm_panels_validate(const char* who, u32 K, int dtype) {
     return BSMR_OK;
 }
 
-// what a side launches over: the panel lists of its owner (plan.hpp)
-struct SideLists {
-    const PanelItem* items;
-    const PanelStep* steps;
-    const u32* rows;
-    const PanelRed* reds;
-    u32 nItems, nSteps, nReds, panels, splitPanels, partials;
-};
-
-SideLists side_lists(const Plan& p, int side) {
-    if (side == 1) {
-        const Plan::AttentionPanelsState& F = p.attention_panels;
-        return {F.items.data(), F.steps.data(), F.rows.data(), F.reds.data(), F.nItems, F.nSteps, F.nReds, F.panels, F.splitPanels, F.partials};
-    }
-    const Plan::AttentionBwdPanelsState& B = p.attention_bwd_panels;
-    return {B.citems.data(), B.csteps.data(), nullptr, B.creds.data(), B.colItems, B.colSteps, B.colReds, B.colPanels, B.colSplit, B.colPartials};
-}
-
-bool lists_built(const Plan& p, int side) { return side == 1 ? p.attention_panels.built : p.attention_bwd_panels.built; }
-
 // a side's lists, positions and scratch cover a launch at K (layout_mu held)
 bool side_ready(const Plan& p, int side, u32 K) {
     const Plan::SpmmPanelsSide& S = p.spmm_panels[side - 1];
-    return S.built && lists_built(p, side) && (side_lists(p, side).partials == 0 || S.scratchK >= K);
+    const Plan::PanelListState& L = p.panel_lists(side);
+    return S.built && L.built && (L.partials == 0 || S.scratchK >= K);
 }
 
 // the side's lists (through their owner's builder), its positions (once) and its scratch for K:
@@ -321,6 +300,7 @@ int build_side(const Plan& p, int side, u32 K, const char* who) {
     Plan::SpmmPanelsSide& S = p.spmm_panels[side - 1];
     const hipStream_t s = p.stream;
     BSMR_CHECK(side == 1 ? attn_panels_build_lists(p, who) : attn_bwd_panels_build_col_lists(p, who));
+    const Plan::PanelListState& L = p.panel_lists(side);
     if (!S.built) {
         // the lists as the device holds them: what the kernel walks is what the positions follow
         std::vector<u32> hrp, hci, hrows, trp, tci, tpos, base, pos;
@@ -328,17 +308,15 @@ int build_side(const Plan& p, int side, u32 K, const char* who) {
         std::vector<PanelItem> items;
         BSMR_CHECK(p.rowptr.download(hrp, s));
         BSMR_CHECK(p.colidx.download(hci, s));
+        BSMR_CHECK(L.steps.download(steps, s));
+        BSMR_CHECK(L.items.download(items, s));
         std::string err;
         int st;
         if (side == 1) {
-            BSMR_CHECK(p.attention_panels.rows.download(hrows, s));
-            BSMR_CHECK(p.attention_panels.steps.download(steps, s));
-            BSMR_CHECK(p.attention_panels.items.download(items, s));
+            BSMR_CHECK(L.rows.download(hrows, s));
             st = spmm_panel_positions(p.M, p.N, hrp.data(), hci.data(), nullptr, hrows.data(), steps.data(), steps.size(),
                                       items.data(), items.size(), base, pos, err);
         } else {
-            BSMR_CHECK(p.attention_bwd_panels.csteps.download(steps, s));
-            BSMR_CHECK(p.attention_bwd_panels.citems.download(items, s));
             st = spmm_pattern_transpose_pos(p.M, p.N, hrp.data(), hci.data(), trp, tci, tpos, err);
             hrows.resize(p.N);
             for (u32 j = 0; j < p.N; ++j) hrows[j] = j;
@@ -355,9 +333,8 @@ int build_side(const Plan& p, int side, u32 K, const char* who) {
         BSMR_HIP(hipStreamSynchronize(s));
         S.built = true;
     }
-    const u32 partials = side_lists(p, side).partials;
-    if (partials != 0 && S.scratchK < K) {
-        BSMR_CHECK(S.scratch.grow(attn_sat_mul(attn_sat_mul(partials, PANEL_ROWS), static_cast<size_t>(K) + 1u)));
+    if (L.partials != 0 && S.scratchK < K) {
+        BSMR_CHECK(S.scratch.grow(attn_sat_mul(attn_sat_mul(L.partials, PANEL_ROWS), static_cast<size_t>(K) + 1u)));
         S.scratchK = K;
     }
     return BSMR_OK;
@@ -381,50 +358,37 @@ int launch_side(const bsmr_plan* plan, int side, const float* dV, const void* dX
     const Plan& p = plan->p;
     const hipStream_t s = static_cast<hipStream_t>(stream);
     SpmmPanelArgs a{};
-    SideLists L{};
+    const PanelRed* reds = nullptr;
+    u32 nReds = 0;
     {
         std::lock_guard<std::mutex> g(p.layout_mu);
-        if (!side_ready(p, side, K)) {
-            const LaunchSite at{s, who, "bsmr_plan_prepare_spmm_panels", K, dtype};
-            const int st = lazy_build_guard(at);
-            if (st == BSMR_ERR_NOT_PREPARED)
-                set_error(std::string(who) + ": stream is capturing and the panel lists, the entry positions (or the scratch for K = " +
-                          std::to_string(K) + ") are not built; call bsmr_plan_prepare_spmm_panels first");
-            BSMR_CHECK(st);
-            BSMR_CHECK(build_side(p, side, K, "bsmr_plan_prepare_spmm_panels"));
-        }
+        const char* prep = "bsmr_plan_prepare_spmm_panels";
+        BSMR_CHECK(panel_build_missing(
+            LaunchSite{s, who, prep, K, dtype}, [&] { return side_ready(p, side, K); },
+            [&] { return "the panel lists, the entry positions (or the scratch for K = " + std::to_string(K) + ")"; },
+            [&] { return build_side(p, side, K, prep); }));
         const Plan::SpmmPanelsSide& S = p.spmm_panels[side - 1];
-        L = side_lists(p, side);
+        const Plan::PanelListState& L = p.panel_lists(side);
+        a.items = L.items.data();
+        a.steps = L.steps.data();
+        a.rows = L.rows.data();
+        a.nItems = L.nItems;
         a.base = S.base.data();
         a.pos = S.pos.data();
         a.pacc = S.scratch.data();
+        a.pm = a.pacc ? reinterpret_cast<int*>(a.pacc + static_cast<size_t>(L.partials) * PANEL_ROWS * K) : nullptr;
+        reds = L.reds.data();
+        nReds = L.nReds;
     }
-    a.items = L.items;
-    a.steps = L.steps;
-    a.rows = L.rows;
-    a.nItems = L.nItems;
-    a.pm = a.pacc ? reinterpret_cast<int*>(a.pacc + static_cast<size_t>(L.partials) * PANEL_ROWS * K) : nullptr;
     a.V = dV;
     a.X = static_cast<const char*>(dX);
     a.Y = dY;
     a.D = side == 1 ? p.M : p.N;
     a.K = K;
     const u32 slices = K > SPMM_PANEL_SLICE ? K / SPMM_PANEL_SLICE : 1u;
-    if (a.nItems) {
-        const SpmmPanelFn fn = dtype == BSMR_F16 ? pick_slice<BSMR_F16>(K) : pick_slice<BSMR_BF16>(K);
-        hipLaunchKernelGGL(fn, dim3((a.nItems + PANEL_WAVES - 1) / PANEL_WAVES, slices), dim3(PANEL_WAVES * 64), 0, s, a);
-        BSMR_HIP(hipGetLastError());
-    }
-    if (L.nReds) {
-        const size_t threads = static_cast<size_t>(L.nReds) * PANEL_ROWS * (K / 4u);
-        const dim3 rgrid(static_cast<u32>((threads + 255) / 256));
-        if (dtype == BSMR_F16)
-            hipLaunchKernelGGL(k_spmm_panels_reduce<true>, rgrid, dim3(256), 0, s, a, L.reds, L.nReds);
-        else
-            hipLaunchKernelGGL(k_spmm_panels_reduce<false>, rgrid, dim3(256), 0, s, a, L.reds, L.nReds);
-        BSMR_HIP(hipGetLastError());
-    }
-    return BSMR_OK;
+    const bool f16 = dtype == BSMR_F16;
+    return panel_launch(s, f16 ? pick_slice<BSMR_F16>(K) : pick_slice<BSMR_BF16>(K), a, a.nItems, dim3(1, slices),
+                        f16 ? k_spmm_panels_reduce<true> : k_spmm_panels_reduce<false>, reds, nReds, K / 4u, dim3(1));
 }
 
 int prepare_args(const char* who, const bsmr_plan* plan, u32 K, int sides) {
@@ -481,14 +445,8 @@ extern "C" int bsmr_plan_spmm_panels_stats(const bsmr_plan* plan, int side, bsmr
     const Plan& p = plan->p;
     std::lock_guard<std::mutex> g(p.layout_mu);
     *out = bsmr_spmm_panels_stats{};
-    if (p.spmm_panels[side - 1].built && lists_built(p, side)) {
-        const SideLists L = side_lists(p, side);
-        out->panels = L.panels;
-        out->items = L.nItems;
-        out->steps = L.nSteps;
-        out->split_panels = L.splitPanels;
-        out->partials = L.partials;
-        out->fill_permille = panel_fill_permille(p.nnz, L.nSteps);
-    }
+    const Plan::PanelListState& L = p.panel_lists(side);
+    if (p.spmm_panels[side - 1].built && L.built)
+        panel_list_stats(L, p.nnz, out->panels, out->items, out->steps, out->split_panels, out->partials, out->fill_permille);
     return BSMR_OK;
 }

@@ -63,7 +63,10 @@ extern "C" {
                               new declarations only; bsmr_spmm_panels, bsmr_spmm_t_panels,
                               bsmr_plan_prepare_spmm_panels, bsmr_plan_spmm_panels_prepared,
                               bsmr_plan_spmm_panels_stats and bsmr_spmm_panel_positions (the panel
-                              MFMA SpMM, the SDDMM gradients: new declarations only) */
+                              MFMA SpMM, the SDDMM gradients: new declarations only);
+                              bsmr_sddmm_mfma, bsmr_plan_prepare_sddmm_mfma,
+                              bsmr_plan_sddmm_mfma_prepared and bsmr_plan_sddmm_mfma_stats (the panel
+                              MFMA SDDMM: new declarations only) */
 
 typedef enum {
     BSMR_OK = 0,
@@ -988,6 +991,45 @@ int bsmr_plan_spmm_panels_stats(const bsmr_plan* plan, int side, bsmr_spmm_panel
 int bsmr_spmm_panel_positions(uint32_t M, uint32_t N, const uint32_t* rowptr, const uint32_t* colidx, int side,
                               const uint32_t* rows, const bsmr_attention_panel_step* steps, uint64_t nsteps,
                               const bsmr_attention_panel_item* items, uint64_t nitems, uint32_t* base, uint32_t* pos);
+
+/* ------------------------------------ SDDMM on matrix instructions, per panel ---- */
+/* bsmr_sddmm for fp16 / bf16 operands on v_mfma_f32_16x16x32_{f16,bf16}, opt-in:
+ * bsmr_sddmm never selects it. Per 16-row panel of the plan's row order (the very lists of
+ * bsmr_attention_panels, with the entry positions of bsmr_spmm_panels' rows side; each is built
+ * here when no earlier call built it, without the SpMM's scratch): a workgroup stages the panel's
+ * 16 rows of A once and its four waves take the item's steps of 32 union columns in turn, so every
+ * B row of a panel's union is loaded once per panel. (bsmr_sddmm_panels is the row-panel range
+ * launch of the shards and has nothing to do with this.) The contract is bsmr_sddmm's: A is M x K
+ * row-major, B is N rows of K, P is nnz fp32 values at CSR positions, every stored entry is written
+ * exactly once and nothing else is written, outputs are untouched on every error, no atomics,
+ * results are bitwise reproducible and equal between a lazily built and a prepared plan, and an
+ * unprepared call on a capturing stream gives BSMR_ERR_NOT_PREPARED and leaves the capture intact.
+ * What differs:
+ *   dtype is BSMR_F16 or BSMR_BF16 and K one of 32, 64, 128, 256, 512, 1024; anything else
+ *   (BSMR_F32 too) gives BSMR_ERR_UNSUPPORTED;
+ *   dA and dB must be 16-byte aligned and dP 4-byte aligned (BSMR_ERR_INVALID);
+ *   exactly one launch per call, whatever the pattern: split panels need no second one;
+ *   the summation order is the MFMA's: k-steps of 32 ascending into one fp32 accumulator, fixed by
+ *   (K, dtype) alone; the bits are not those of bsmr_sddmm, and P is the accumulator unconverted;
+ *   NaN / inf: containment is exact. An entry reads only its own A row and B row, so a non-finite
+ *   value in a B row reaches exactly the entries that store that column, and one in an A row
+ *   exactly that row's entries. */
+int bsmr_sddmm_mfma(const bsmr_plan* plan, const void* dA, const void* dB, uint32_t K, int dtype, float* dP,
+                    void* stream);
+/* Build now what the first launch would build: the row panel lists and the entry positions
+ * (nothing depends on K beyond its validity). Synchronous and idempotent. */
+int bsmr_plan_prepare_sddmm_mfma(const bsmr_plan* plan, uint32_t K);
+/* 1 when a launch at K would make no allocation, copy or synchronisation, else 0 (also 0 on bad
+ * arguments); no device call. */
+int bsmr_plan_sddmm_mfma_prepared(const bsmr_plan* plan, uint32_t K);
+typedef struct {
+    /* panels, items, steps, fill_permille: as bsmr_attention_panels_stats, of the row lists; waves:
+     * the waves the launch starts that get at least one step (an item's steps are dealt to the four
+     * waves of its workgroup: the sum over the items of min(steps, 4)) */
+    uint32_t panels, items, steps, waves, fill_permille;
+} bsmr_sddmm_mfma_stats;
+/* Zeros while the lists or the positions are not built. */
+int bsmr_plan_sddmm_mfma_stats(const bsmr_plan* plan, bsmr_sddmm_mfma_stats* out);
 
 /* Timing: run `iters` back-to-back SDDMMs on `stream`, timing each kernel with HIP events on
  * that stream (BSMR_ERR_UNSUPPORTED on a capturing stream). Outputs average ms per launch of the dense-tile kernel, the residual kernel and

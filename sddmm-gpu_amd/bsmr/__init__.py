@@ -187,6 +187,15 @@ class SpmmPanelsStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class SddmmMfmaStats(C.Structure):
+    """bsmr_sddmm_mfma_stats: the row panel lists as the MFMA SDDMM launches over them (zeros when not
+    built); waves: the waves that get at least one step."""
+    _fields_ = [(k, C.c_uint32) for k in ("panels", "items", "steps", "waves", "fill_permille")]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class AttentionBackwardStats(C.Structure):
     """bsmr_attention_backward_stats: the fused attention backward's row and column segment lists
     and plan-owned scratch (zeros when not built) and the library's constant chunks."""
@@ -281,6 +290,7 @@ EXPORTS = [
     "bsmr_attention_panels_kv8", "bsmr_attention_panels_kv8_heads",
     "bsmr_spmm_panels", "bsmr_spmm_t_panels", "bsmr_plan_prepare_spmm_panels", "bsmr_plan_spmm_panels_prepared",
     "bsmr_plan_spmm_panels_stats", "bsmr_spmm_panel_positions",
+    "bsmr_sddmm_mfma", "bsmr_plan_prepare_sddmm_mfma", "bsmr_plan_sddmm_mfma_prepared", "bsmr_plan_sddmm_mfma_stats",
 ]
 
 # include/bsmr.h BSMR_ATTENTION_MAX_BATCHES, BSMR_ATTENTION_MAX_HEADS
@@ -455,6 +465,13 @@ def lib():
     L.bsmr_plan_spmm_panels_stats.restype = C.c_int
     L.bsmr_spmm_panel_positions.argtypes = [C.c_uint32, C.c_uint32, vp, vp, C.c_int, vp, vp, C.c_uint64, vp, C.c_uint64, vp, vp]
     L.bsmr_spmm_panel_positions.restype = C.c_int
+    L.bsmr_sddmm_mfma.argtypes = [vp, vp, vp, C.c_uint32, C.c_int, vp, vp]
+    L.bsmr_sddmm_mfma.restype = C.c_int
+    for f in ("bsmr_plan_prepare_sddmm_mfma", "bsmr_plan_sddmm_mfma_prepared"):
+        getattr(L, f).argtypes = [vp, C.c_uint32]
+        getattr(L, f).restype = C.c_int
+    L.bsmr_plan_sddmm_mfma_stats.argtypes = [vp, C.POINTER(SddmmMfmaStats)]
+    L.bsmr_plan_sddmm_mfma_stats.restype = C.c_int
     L.bsmr_attention_backward_panels.argtypes = L.bsmr_attention_backward.argtypes
     L.bsmr_attention_backward_panels.restype = C.c_int
     L.bsmr_attention_backward_panels_heads.argtypes = L.bsmr_attention_backward_heads.argtypes
@@ -773,6 +790,25 @@ class Plan:
     def spmm_panels_stats(self, side):
         s = SpmmPanelsStats()
         _check(lib().bsmr_plan_spmm_panels_stats(self.h, side, C.byref(s)), "bsmr_plan_spmm_panels_stats")
+        return s.as_dict()
+
+    def sddmm_mfma(self, dA, dB, K, dP, stream=0, dtype=F16):
+        """bsmr_sddmm_mfma: sddmm's P for fp16 / bf16 A and B and K in 32 .. 1024 (powers of two), per
+        16-row panel on matrix instructions, one launch. The bits are those of
+        the MFMA's k order, not sddmm's."""
+        _check(lib().bsmr_sddmm_mfma(self.h, dA, dB, K, dtype, dP, stream or None), "bsmr_sddmm_mfma")
+
+    def prepare_sddmm_mfma(self, K):
+        """bsmr_plan_prepare_sddmm_mfma: build now the row panel lists and the entry positions, so
+        that the first sddmm_mfma launch can be captured."""
+        _check(lib().bsmr_plan_prepare_sddmm_mfma(self.h, K), "bsmr_plan_prepare_sddmm_mfma")
+
+    def sddmm_mfma_prepared(self, K):
+        return bool(lib().bsmr_plan_sddmm_mfma_prepared(self.h, K))
+
+    def sddmm_mfma_stats(self):
+        s = SddmmMfmaStats()
+        _check(lib().bsmr_plan_sddmm_mfma_stats(self.h, C.byref(s)), "bsmr_plan_sddmm_mfma_stats")
         return s.as_dict()
 
     def softmax(self, dP, dW, scale=1.0, stream=0):

@@ -1,6 +1,6 @@
 """torch.autograd binding of the plan-based SDDMM: P = sddmm(plan, A, B) with gradients.
 
-    forward   P[idx(i,j)] = dot(A[i,:], B[j,:])                 Plan.sddmm
+    forward   P[idx(i,j)] = dot(A[i,:], B[j,:])                 Plan.sddmm (forward="panels": Plan.sddmm_mfma)
     backward  dA = S(G) B (Plan.spmm), dB = S(G)^T A (Plan.spmm_t), G = dL/dP
 
 and, over the same plan, the row softmax, the SpMM and their composition into sparse attention:
@@ -32,11 +32,12 @@ _DTYPES = {torch.float32: F32, torch.float16: F16, torch.bfloat16: BF16}
 _PANEL_K = (32, 64, 128, 256, 512, 1024)  # include/bsmr.h, bsmr_spmm_panels
 
 
-def _validate_panels(who, arg, value, K, dtype):
-    """The SpMM form named by `arg`: "gather" (Plan.spmm / spmm_t) or "panels" (Plan.spmm_panels /
-    spmm_t_panels: float16 / bfloat16 and K in _PANEL_K); True for "panels"."""
-    if value not in ("gather", "panels"):
-        raise ValueError(f'{who}: {arg} must be "gather" or "panels", got {value!r}')
+def _validate_panels(who, arg, value, K, dtype, other="gather"):
+    """The form named by `arg`: `other` ("gather": Plan.spmm / spmm_t; "default": Plan.sddmm) or
+    "panels" (Plan.spmm_panels / spmm_t_panels / sddmm_mfma: float16 / bfloat16 and K in _PANEL_K);
+    True for "panels"."""
+    if value not in (other, "panels"):
+        raise ValueError(f'{who}: {arg} must be "{other}" or "panels", got {value!r}')
     if value == "panels" and (dtype == F32 or K not in _PANEL_K):
         raise ValueError(f'{who}: {arg}="panels" needs float16 or bfloat16 operands and K one of {_PANEL_K}, got K = {K}')
     return value == "panels"
@@ -77,10 +78,11 @@ def _validate(plan, A, B):
 
 class _Sddmm(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, A, B, plan, backward="gather"):
+    def forward(ctx, A, B, plan, backward="gather", forward="default"):
         K, dtype = _validate(plan, A, B)
         P = torch.empty(max(plan.nnz, 1), dtype=torch.float32, device=A.device)
-        plan.sddmm(A.data_ptr(), B.data_ptr(), K, P.data_ptr(), stream=_stream(), dtype=dtype)
+        launch = plan.sddmm_mfma if forward == "panels" else plan.sddmm
+        launch(A.data_ptr(), B.data_ptr(), K, P.data_ptr(), stream=_stream(), dtype=dtype)
         ctx.plan, ctx.K, ctx.dtype, ctx.backward_form = plan, K, dtype, backward
         ctx.save_for_backward(A, B)
         return P[:plan.nnz]
@@ -101,20 +103,25 @@ class _Sddmm(torch.autograd.Function):
                             gA.data_ptr() if gA is not None else 0,
                             gB.data_ptr() if gB is not None else 0,
                             stream=_stream(), dtype=ctx.dtype, backward=ctx.backward_form)
-        return (None if gA is None else gA.to(A.dtype), None if gB is None else gB.to(B.dtype), None, None)
+        return (None if gA is None else gA.to(A.dtype), None if gB is None else gB.to(B.dtype), None, None, None)
 
 
-def sddmm(plan, A, B, backward="gather"):
+def sddmm(plan, A, B, backward="gather", forward="default"):
     """P (nnz,) float32 = the plan's sampled A @ B.T, differentiable in A and B. A: (M, K), B:
     (N, K) (the header's column-major K x N), contiguous device tensors of one dtype out of
     float32, float16 and bfloat16; K a positive multiple of 16 (float32) or 32 (float16 /
     bfloat16: what the forward launch takes). Shape, dtype, device, contiguity and K errors raise
     ValueError before any launch and before any gather list is built. backward="panels" computes
     both gradients per 16-destination panel on matrix instructions (Plan.spmm_panels /
-    spmm_t_panels: float16 / bfloat16 and K in 32, 64, 128, 256, 512, 1024, else ValueError)."""
+    spmm_t_panels: float16 / bfloat16 and K in 32, 64, 128, 256, 512, 1024, else ValueError).
+    forward="panels" computes P per 16-row panel on matrix instructions in one launch
+    (Plan.sddmm_mfma: the same operand rule, else ValueError; its bits are those of the MFMA's k
+    order, not Plan.sddmm's); the two combine freely, and the gradients do not depend on the
+    forward's form."""
     K, dtype = _validate(plan, A, B)
     _validate_panels("sddmm", "backward", backward, K, dtype)
-    return _Sddmm.apply(A, B, plan, backward)
+    _validate_panels("sddmm", "forward", forward, K, dtype, other="default")
+    return _Sddmm.apply(A, B, plan, backward, forward)
 
 
 def _valid_scale(who, scale):

@@ -113,6 +113,14 @@ Verdict validate_launch_k(const char* who, Launch kind, uint32_t K) {
     return {};
 }
 
+Verdict validate_sddmm_mfma(const char* who, uint32_t K, int dtype) {
+    const bool k = K == 32 || K == 64 || K == 128 || K == 256 || K == 512 || K == 1024;
+    if ((dtype != LS_F16 && dtype != LS_BF16) || !k)
+        return {LS_ERR_UNSUPPORTED,
+                std::string(who) + ": dtype must be BSMR_F16 or BSMR_BF16 and K one of 32, 64, 128, 256, 512, 1024"};
+    return {};
+}
+
 Verdict check_panel_range(const char* who, uint32_t p0, uint32_t p1, uint32_t P, int slot, int dtype,
                           bool local) {
     if (p0 > p1 || p1 > P) return {LS_ERR_INVALID, std::string(who) + ": bad panel range"};

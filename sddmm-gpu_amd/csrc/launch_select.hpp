@@ -80,6 +80,9 @@ Verdict validate_kd(const char* who, uint32_t K, int dtype);
 // the further K rule of the launch chosen: the half column-major launch takes multiples of 32,
 // the panel-tile launch K in {64, 128, 256, 512}
 Verdict validate_launch_k(const char* who, Launch kind, uint32_t K);
+// the rule of bsmr_sddmm_mfma and its prepare calls (sddmm_panels.hip): fp16 / bf16 and a K that the
+// kernel is instantiated for
+Verdict validate_sddmm_mfma(const char* who, uint32_t K, int dtype);
 // the panel-range rules of bsmr_sddmm_panels / _panels_local and their prepare calls: [p0, p1)
 // within the plan's P panels; a non-empty range needs a row-block slot when the A rows are local
 // or the operands fp16/bf16 (fp32 falls back to the panel-major lists)

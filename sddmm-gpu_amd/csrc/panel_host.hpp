@@ -1,5 +1,5 @@
 // panel_host.hpp — what the panel families share on the host (attention_panels.hip and its e4m3
-// form, attention_bwd_panels.hip, spmm_panels.hip): the plan's two panel lists
+// form, attention_bwd_panels.hip, spmm_panels.hip, sddmm_panels.hip): the plan's two panel lists
 // (Plan::PanelListState) and their upload, the list counters of a stats record, the argument rules
 // of the attention families, the build of missing state at a launch and the launches themselves.
 #pragma once
@@ -20,6 +20,13 @@ int attn_panels_build_lists(const Plan& p, const char* who);
 // panel_cols (once): attention_panel_lists on the transposed pattern, M and N in each other's role
 // and no order, so a column panel is 16 consecutive columns. Defined in attention_bwd_panels.hip
 int attn_bwd_panels_build_col_lists(const Plan& p, const char* who);
+
+// A side's lists (1 rows, 2 columns: through the builder above when they are not built) and, once,
+// where in the caller's nnz-sized vector the entry of every set mask bit lies (SpmmPanelsSide's base
+// and pos, spmm_panels.hpp) with stepWaves; no scratch. layout_mu held; synchronous on the plan's
+// stream. The panel SpMM's sides and the MFMA SDDMM (sddmm_panels.hip, side 1) build through it.
+// Defined in spmm_panels.hip
+int spmm_panels_build_positions(const Plan& p, int side, const char* who);
 
 // What attention_panel_lists returned (st, err, L) into S: its faults mapped (2, past the lists'
 // capacity, and more than 2^31 items are BSMR_ERR_UNSUPPORTED), the four arrays uploaded, the

@@ -359,10 +359,13 @@ struct Plan {
     // in V the entry of every set mask bit lies (spmm_panels.hpp: base, 16 per step; pos, one per
     // entry) and the partial slots of the split panels: partials x 16 x scratchK floats followed by
     // partials x 16 running exponents. Built on first use or by bsmr_plan_prepare_spmm_panels, under
-    // layout_mu; the scratch grows and never shrinks; build_columns keeps all of it
+    // layout_mu; the scratch grows and never shrinks; build_columns keeps all of it. The MFMA SDDMM
+    // (sddmm_panels.hip; bsmr_sddmm_mfma) launches over panel_rows and the rows side's base / pos, built
+    // through the same builder without the scratch, and holds nothing of its own; stepWaves counts
+    // the waves that get a step when every item's steps are dealt to PANEL_WAVES waves (its stats)
     struct SpmmPanelsSide {
         bool built = false;
-        u32 scratchK = 0;
+        u32 scratchK = 0, stepWaves = 0;
         DevBuf<u32> base, pos;
         DevBuf<float> scratch;
     };

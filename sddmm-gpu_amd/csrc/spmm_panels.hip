@@ -42,6 +42,7 @@
 // (66 KiB per workgroup at KS = 256: two workgroups per CU, amdgpu_waves_per_eu(2)).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -294,45 +295,12 @@ bool side_ready(const Plan& p, int side, u32 K) {
     return S.built && L.built && (L.partials == 0 || S.scratchK >= K);
 }
 
-// the side's lists (through their owner's builder), its positions (once) and its scratch for K:
-// it grows and never shrinks; layout_mu held. Synchronous on the plan's stream.
+// the side's lists and positions (panel_host.hpp) and its scratch for K: it grows and never shrinks;
+// layout_mu held. Synchronous on the plan's stream.
 int build_side(const Plan& p, int side, u32 K, const char* who) {
+    BSMR_CHECK(spmm_panels_build_positions(p, side, who));
     Plan::SpmmPanelsSide& S = p.spmm_panels[side - 1];
-    const hipStream_t s = p.stream;
-    BSMR_CHECK(side == 1 ? attn_panels_build_lists(p, who) : attn_bwd_panels_build_col_lists(p, who));
     const Plan::PanelListState& L = p.panel_lists(side);
-    if (!S.built) {
-        // the lists as the device holds them: what the kernel walks is what the positions follow
-        std::vector<u32> hrp, hci, hrows, trp, tci, tpos, base, pos;
-        std::vector<PanelStep> steps;
-        std::vector<PanelItem> items;
-        BSMR_CHECK(p.rowptr.download(hrp, s));
-        BSMR_CHECK(p.colidx.download(hci, s));
-        BSMR_CHECK(L.steps.download(steps, s));
-        BSMR_CHECK(L.items.download(items, s));
-        std::string err;
-        int st;
-        if (side == 1) {
-            BSMR_CHECK(L.rows.download(hrows, s));
-            st = spmm_panel_positions(p.M, p.N, hrp.data(), hci.data(), nullptr, hrows.data(), steps.data(), steps.size(),
-                                      items.data(), items.size(), base, pos, err);
-        } else {
-            st = spmm_pattern_transpose_pos(p.M, p.N, hrp.data(), hci.data(), trp, tci, tpos, err);
-            hrows.resize(p.N);
-            for (u32 j = 0; j < p.N; ++j) hrows[j] = j;
-            if (!st)
-                st = spmm_panel_positions(p.N, p.M, trp.data(), tci.data(), tpos.data(), hrows.data(), steps.data(), steps.size(),
-                                          items.data(), items.size(), base, pos, err);
-        }
-        if (st) {
-            set_error(std::string(who) + ": " + err);
-            return BSMR_ERR_INVALID;
-        }
-        BSMR_CHECK(S.base.upload(base.data(), base.size(), s));
-        BSMR_CHECK(S.pos.upload(pos.data(), pos.size(), s));
-        BSMR_HIP(hipStreamSynchronize(s));
-        S.built = true;
-    }
     if (L.partials != 0 && S.scratchK < K) {
         BSMR_CHECK(S.scratch.grow(attn_sat_mul(attn_sat_mul(L.partials, PANEL_ROWS), static_cast<size_t>(K) + 1u)));
         S.scratchK = K;
@@ -404,6 +372,50 @@ int prepare_args(const char* who, const bsmr_plan* plan, u32 K, int sides) {
 }
 
 }  // namespace
+
+// panel_host.hpp: the side's lists (through their owner's builder) and its positions (once)
+int spmm_panels_build_positions(const Plan& p, int side, const char* who) {
+    Plan::SpmmPanelsSide& S = p.spmm_panels[side - 1];
+    const hipStream_t s = p.stream;
+    BSMR_CHECK(side == 1 ? attn_panels_build_lists(p, who) : attn_bwd_panels_build_col_lists(p, who));
+    const Plan::PanelListState& L = p.panel_lists(side);
+    if (S.built) return BSMR_OK;
+    // the lists as the device holds them: what the kernel walks is what the positions follow
+    std::vector<u32> hrp, hci, hrows, trp, tci, tpos, base, pos;
+    std::vector<PanelStep> steps;
+    std::vector<PanelItem> items;
+    BSMR_CHECK(p.rowptr.download(hrp, s));
+    BSMR_CHECK(p.colidx.download(hci, s));
+    BSMR_CHECK(L.steps.download(steps, s));
+    BSMR_CHECK(L.items.download(items, s));
+    std::string err;
+    int st;
+    if (side == 1) {
+        BSMR_CHECK(L.rows.download(hrows, s));
+        st = spmm_panel_positions(p.M, p.N, hrp.data(), hci.data(), nullptr, hrows.data(), steps.data(), steps.size(),
+                                  items.data(), items.size(), base, pos, err);
+    } else {
+        st = spmm_pattern_transpose_pos(p.M, p.N, hrp.data(), hci.data(), trp, tci, tpos, err);
+        hrows.resize(p.N);
+        for (u32 j = 0; j < p.N; ++j) hrows[j] = j;
+        if (!st)
+            st = spmm_panel_positions(p.N, p.M, trp.data(), tci.data(), tpos.data(), hrows.data(), steps.data(), steps.size(),
+                                      items.data(), items.size(), base, pos, err);
+    }
+    if (st) {
+        set_error(std::string(who) + ": " + err);
+        return BSMR_ERR_INVALID;
+    }
+    BSMR_CHECK(S.base.upload(base.data(), base.size(), s));
+    BSMR_CHECK(S.pos.upload(pos.data(), pos.size(), s));
+    BSMR_HIP(hipStreamSynchronize(s));
+    u64 waves = 0;
+    for (const PanelItem& it : items) waves += std::min(it.nsteps, PANEL_WAVES);
+    S.stepWaves = static_cast<u32>(std::min<u64>(waves, 0xFFFFFFFFu));
+    S.built = true;
+    return BSMR_OK;
+}
+
 }  // namespace bsmr
 
 using namespace bsmr;

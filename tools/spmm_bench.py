@@ -20,7 +20,10 @@ tensors and the same graph replays in alternation; per case and side it prints s
 (fill_permille, steps, items, split panels), graph_us of both forms, their ratio, the largest
 |Y_panels - Y_gather| and floor_us with each panel's union counted once: V, its positions and Y once,
 the step records and 32 dense rows per step, once per slice of 256 columns. C5 is the 2,048 x 2,048
-mask of 16 x 16 blocks.
+mask of 16 x 16 blocks. Each case's line also carries "sddmm": the panel MFMA SDDMM (Plan.sddmm_mfma,
+DESIGN.md section 23) against Plan.sddmm on the same plan and tensors, timed the same way, with
+sddmm_mfma_stats (fill_permille, items, waves), the largest |P_mfma - P_sddmm| and floor_us: A, the
+step records, the positions and P once and 32 B rows per step.
 --sweep adds the chunk sweep {128, 256, 512, 1024} on C2 side 2 (the skewed side), one plan per
 chunk, replayed in alternation.
 """
@@ -103,6 +106,8 @@ def main():
         plan = Plan(M, N, rp, ci, alpha=0.3, delta=0.3)
         plan.prepare_spmm(K, 3)
         plan.prepare_spmm_panels(K, 3)
+        plan.prepare(K, dt)
+        plan.prepare_sddmm_mfma(K)
         X = {1: torch.from_numpy(make_data(N * K)).to(dev).to(tdt).reshape(N, K),
              2: torch.from_numpy(make_data(M * K)).to(dev).to(tdt).reshape(M, K)}
         dV = torch.from_numpy(make_data(nnz) - np.float32(0.5)).to(dev)
@@ -121,6 +126,17 @@ def main():
                           "floor_us": round(floor, 3), "floor_fraction": round(floor / graph_us["panels"], 3),
                           "max_abs_diff": (out["panels"] - out["gather"]).abs().max().item(), "max_abs": out["gather"].abs().max().item(),
                           "graph_us_rounds": rounds}
+        forms = {"sddmm": plan.sddmm, "mfma": plan.sddmm_mfma}
+        out = {k: torch.zeros(max(nnz, 1), dtype=torch.float32, device=dev) for k in forms}
+        graphs = {k: graph_of(lambda s, f=f, k=k: f(X[2].data_ptr(), X[1].data_ptr(), K, out[k].data_ptr(), stream=s, dtype=dt))
+                  for k, f in forms.items()}
+        graph_us, rounds = alternate({k: g.replay for k, g in graphs.items()})
+        st = plan.sddmm_mfma_stats()
+        floor = (2 * M * K + 8 * nnz + st["steps"] * (256 + 32 * 2 * K)) / HBM_BYTES_PER_S * 1e6
+        line["sddmm"] = {"sddmm_mfma_stats": st, "graph_us": graph_us, "mfma_over_sddmm": round(graph_us["mfma"] / graph_us["sddmm"], 3),
+                         "floor_us": round(floor, 3), "floor_fraction": round(floor / graph_us["mfma"], 3),
+                         "max_abs_diff": (out["mfma"] - out["sddmm"]).abs().max().item(), "max_abs": out["sddmm"].abs().max().item(),
+                         "graph_us_rounds": rounds}
         print(json.dumps(line), flush=True)
     for case in () if args.panels else args.cases.split(","):
         if case == "C2":

@@ -66,7 +66,10 @@ extern "C" {
                               MFMA SpMM, the SDDMM gradients: new declarations only);
                               bsmr_sddmm_mfma, bsmr_plan_prepare_sddmm_mfma,
                               bsmr_plan_sddmm_mfma_prepared and bsmr_plan_sddmm_mfma_stats (the panel
-                              MFMA SDDMM: new declarations only) */
+                              MFMA SDDMM: new declarations only); bsmr_attention_panels_bias,
+                              bsmr_attention_backward_panels_bias, their heads forms and prepare /
+                              prepared calls (the panel MFMA attention with a per-entry bias: new
+                              declarations only) */
 
 typedef enum {
     BSMR_OK = 0,
@@ -937,6 +940,67 @@ int bsmr_plan_attention_backward_panels_stats(const bsmr_plan* plan, bsmr_attent
  * or a column >= N. */
 int bsmr_attention_pattern_transpose(uint32_t M, uint32_t N, const uint32_t* rowptr, const uint32_t* colidx,
                                      uint32_t* trowptr, uint32_t* tcolidx);
+
+/* ---------------- panel MFMA attention with a per-entry additive bias, forward and backward ---- */
+/* bsmr_attention_panels and bsmr_attention_backward_panels with one fp32 bias per stored entry
+ * (DESIGN.md §24): an edge bias, a relative-position or ALiBi term, a soft mask. dBias holds nnz
+ * fp32 values at CSR positions (the layout of bsmr_spmm's V and bsmr_sddmm's P), 4-byte aligned.
+ *   x_e = fl(p_e scale) + bias_e     p_e = dot(Q_i, K_j) from the MFMA; the product and the sum are
+ *                                    each rounded on their own (no fma)
+ *   W = softmax_row(x), O = W V, LSE_i = log sum_e exp(x_e)
+ *   GBias_e = w_e (g_e - delta_i)    the quantity the backward multiplies by scale to get dp_e
+ *   GQ, GK, GV as bsmr_attention_backward_panels defines them, with x and w as above.
+ * Conventions beyond the unbiased calls': bias_e = -inf removes the entry (w = 0, GBias_e = 0); a
+ * row whose entries are all -inf behaves as an empty row (O = 0, LSE = -inf, no NaN); a NaN or +inf
+ * bias makes exactly its own row NaN (O, LSE, GQ and the row's GBias; GK / GV only for the columns
+ * that row stores). An entry the pattern does not store issues no bias load and no GBias store;
+ * every stored entry's GBias is written exactly once, by plain stores (no atomics): bitwise
+ * reproducible, equal between a lazily built and a prepared plan, a heads slice and the single-slice
+ * call, a graph replay and the eager call. The bias is gathered through the entry positions of the
+ * panel SpMM (one copy per side in the plan, built here when no panel SpMM / MFMA SDDMM built them;
+ * no scratch of the panel SpMM is built).
+ * dtype is BSMR_F16 or BSMR_BF16 and D and Dv are each one of 32, 64, 128, forward and backward; the
+ * 256 forms of bsmr_attention_panels have no biased form (no registers left for the gather) and give
+ * BSMR_ERR_UNSUPPORTED, like BSMR_F32. bsmr_attention_panels_kv8 (e4m3 K / V) and the gather kernels
+ * (bsmr_attention, bsmr_attention_backward) take no bias.
+ * Heads: bias_slice_stride, in elements, is the distance between the biases of consecutive slices
+ * (slice = batch * heads + head); 0 means one bias shared by all slices, any other value must be
+ * >= nnz. gbias_slice_stride is >= nnz and never 0: a shared bias gets one gradient per slice and the
+ * caller sums them. Backward outputs: any of dGQ, dGK, dGV, dGBias may be NULL, not all four; the
+ * rows side runs when GQ or GBias is asked for. At most two (forward) and five (backward) launches.
+ * Errors as the unbiased calls', outputs untouched on every one: BSMR_ERR_INVALID for a null or
+ * misaligned dBias, a misaligned dGBias or a bad stride; BSMR_ERR_NOT_PREPARED on a capturing stream
+ * until the matching prepare call ran (the capture stays intact). */
+int bsmr_attention_panels_bias(const bsmr_plan* plan, const void* dQ, const void* dK, const void* dV,
+                               const float* dBias, uint32_t D, uint32_t Dv, int dtype, float scale, float* dO,
+                               float* dLse, void* stream);
+int bsmr_attention_panels_bias_heads(const bsmr_plan* plan, uint32_t batches, uint32_t heads,
+                                     const bsmr_attention_operand* Q, const bsmr_attention_operand* K,
+                                     const bsmr_attention_operand* V, const float* dBias,
+                                     uint64_t bias_slice_stride, uint32_t D, uint32_t Dv, int dtype, float scale,
+                                     const bsmr_attention_operand* O, float* dLse, void* stream);
+int bsmr_attention_backward_panels_bias(const bsmr_plan* plan, const void* dQ, const void* dK, const void* dV,
+                                        const float* dBias, const float* dO, const float* dGO, const float* dLse,
+                                        uint32_t D, uint32_t Dv, int dtype, float scale, float* dGQ, float* dGK,
+                                        float* dGV, float* dGBias, void* stream);
+int bsmr_attention_backward_panels_bias_heads(
+    const bsmr_plan* plan, uint32_t batches, uint32_t heads, const bsmr_attention_operand* Q,
+    const bsmr_attention_operand* K, const bsmr_attention_operand* V, const float* dBias, uint64_t bias_slice_stride,
+    const bsmr_attention_operand* O, const bsmr_attention_operand* GO, const float* dLse, uint32_t D, uint32_t Dv,
+    int dtype, float scale, const bsmr_attention_operand* GQ, const bsmr_attention_operand* GK,
+    const bsmr_attention_operand* GV, float* dGBias, uint64_t gbias_slice_stride, void* stream);
+/* The unbiased prepare calls plus the entry positions of the rows side (forward) or of both sides
+ * (backward). Synchronous and idempotent; the prepared calls make no device call. */
+int bsmr_plan_prepare_attention_panels_bias(const bsmr_plan* plan, uint32_t D, uint32_t Dv);
+int bsmr_plan_prepare_attention_panels_bias_heads(const bsmr_plan* plan, uint32_t D, uint32_t Dv, uint32_t slices);
+int bsmr_plan_attention_panels_bias_prepared(const bsmr_plan* plan, uint32_t D, uint32_t Dv);
+int bsmr_plan_attention_panels_bias_heads_prepared(const bsmr_plan* plan, uint32_t D, uint32_t Dv, uint32_t slices);
+int bsmr_plan_prepare_attention_backward_panels_bias(const bsmr_plan* plan, uint32_t D, uint32_t Dv);
+int bsmr_plan_prepare_attention_backward_panels_bias_heads(const bsmr_plan* plan, uint32_t D, uint32_t Dv,
+                                                           uint32_t slices);
+int bsmr_plan_attention_backward_panels_bias_prepared(const bsmr_plan* plan, uint32_t D, uint32_t Dv);
+int bsmr_plan_attention_backward_panels_bias_heads_prepared(const bsmr_plan* plan, uint32_t D, uint32_t Dv,
+                                                            uint32_t slices);
 
 /* ------------------------------------ SpMM on matrix instructions, per panel ---- */
 /* bsmr_spmm / bsmr_spmm_t for fp16 / bf16 dense operands on v_mfma_f32_16x16x32_{f16,bf16}

@@ -291,6 +291,12 @@ EXPORTS = [
     "bsmr_spmm_panels", "bsmr_spmm_t_panels", "bsmr_plan_prepare_spmm_panels", "bsmr_plan_spmm_panels_prepared",
     "bsmr_plan_spmm_panels_stats", "bsmr_spmm_panel_positions",
     "bsmr_sddmm_mfma", "bsmr_plan_prepare_sddmm_mfma", "bsmr_plan_sddmm_mfma_prepared", "bsmr_plan_sddmm_mfma_stats",
+    "bsmr_attention_panels_bias", "bsmr_attention_panels_bias_heads", "bsmr_attention_backward_panels_bias",
+    "bsmr_attention_backward_panels_bias_heads", "bsmr_plan_prepare_attention_panels_bias",
+    "bsmr_plan_prepare_attention_panels_bias_heads", "bsmr_plan_attention_panels_bias_prepared",
+    "bsmr_plan_attention_panels_bias_heads_prepared", "bsmr_plan_prepare_attention_backward_panels_bias",
+    "bsmr_plan_prepare_attention_backward_panels_bias_heads", "bsmr_plan_attention_backward_panels_bias_prepared",
+    "bsmr_plan_attention_backward_panels_bias_heads_prepared",
 ]
 
 # include/bsmr.h BSMR_ATTENTION_MAX_BATCHES, BSMR_ATTENTION_MAX_HEADS
@@ -484,6 +490,20 @@ def lib():
         getattr(L, f).restype = C.c_int
     L.bsmr_plan_attention_backward_panels_stats.argtypes = [vp, C.POINTER(AttentionBackwardPanelsStats)]
     L.bsmr_plan_attention_backward_panels_stats.restype = C.c_int
+    u32, u64 = C.c_uint32, C.c_uint64
+    L.bsmr_attention_panels_bias.argtypes = [vp] * 5 + [u32, u32, C.c_int, C.c_float, vp, vp, vp]
+    L.bsmr_attention_panels_bias_heads.argtypes = [vp, u32, u32, op, op, op, vp, u64, u32, u32, C.c_int, C.c_float, op, vp, vp]
+    L.bsmr_attention_backward_panels_bias.argtypes = [vp] * 8 + [u32, u32, C.c_int, C.c_float] + [vp] * 5
+    L.bsmr_attention_backward_panels_bias_heads.argtypes = [vp, u32, u32, op, op, op, vp, u64, op, op, vp, u32, u32, C.c_int,
+                                                            C.c_float, op, op, op, vp, u64, vp]
+    for f in ("bsmr_attention_panels_bias", "bsmr_attention_panels_bias_heads", "bsmr_attention_backward_panels_bias",
+              "bsmr_attention_backward_panels_bias_heads"):
+        getattr(L, f).restype = C.c_int
+    for stem in ("attention_panels_bias", "attention_backward_panels_bias"):
+        for f, n in ((f"bsmr_plan_prepare_{stem}", 2), (f"bsmr_plan_{stem}_prepared", 2),
+                     (f"bsmr_plan_prepare_{stem}_heads", 3), (f"bsmr_plan_{stem}_heads_prepared", 3)):
+            getattr(L, f).argtypes = [vp] + [u32] * n
+            getattr(L, f).restype = C.c_int
     L.bsmr_attention_pattern_transpose.argtypes = [C.c_uint32, C.c_uint32, vp, vp, vp, vp]
     L.bsmr_attention_pattern_transpose.restype = C.c_int
     L.bsmr_plan_check.argtypes = [vp, C.c_uint32, C.c_int, C.c_int]
@@ -1013,6 +1033,57 @@ class Plan:
         _check(lib().bsmr_plan_attention_backward_panels_stats(self.h, C.byref(s)),
                "bsmr_plan_attention_backward_panels_stats")
         return s.as_dict()
+
+    def attention_panels_bias(self, dQ, dK, dV, dBias, D, Dv, dO, dLse=0, scale=1.0, stream=0, dtype=F16):
+        """bsmr_attention_panels_bias: attention_panels with x = fl(p scale) + bias per stored entry;
+        dBias nnz float32 values at CSR positions. D, Dv in {32, 64, 128}. bias = -inf removes an entry."""
+        _check(lib().bsmr_attention_panels_bias(self.h, dQ, dK, dV, dBias or None, D, Dv, dtype, scale, dO, dLse or None,
+                                                stream or None), "bsmr_attention_panels_bias")
+
+    def attention_panels_bias_heads(self, batches, heads, Q, K, V, dBias, bias_stride, D, Dv, O, dLse=0, scale=1.0, stream=0,
+                                    dtype=F16):
+        """bsmr_attention_panels_bias_heads: attention_panels_bias over batches x heads slices; bias_stride
+        in elements between the slices' biases, 0 for one bias shared by all slices."""
+        ops = [AttentionOperand.of(x) for x in (Q, K, V, O)]
+        ref = [None if o is None else C.byref(o) for o in ops]
+        _check(lib().bsmr_attention_panels_bias_heads(self.h, batches, heads, ref[0], ref[1], ref[2], dBias or None, bias_stride,
+                                                      D, Dv, dtype, scale, ref[3], dLse or None, stream or None),
+               "bsmr_attention_panels_bias_heads")
+
+    def attention_backward_panels_bias(self, dQ, dK, dV, dBias, dO, dGO, dLse, D, Dv, dGQ=0, dGK=0, dGV=0, dGBias=0, scale=1.0,
+                                       stream=0, dtype=F16):
+        """bsmr_attention_backward_panels_bias: attention_backward_panels of the biased forward, and
+        dGBias (nnz float32 at CSR positions) = w (g - delta). Any output may be 0; not all four."""
+        _check(lib().bsmr_attention_backward_panels_bias(self.h, dQ, dK, dV, dBias or None, dO, dGO, dLse, D, Dv, dtype, scale,
+                                                         dGQ or None, dGK or None, dGV or None, dGBias or None, stream or None),
+               "bsmr_attention_backward_panels_bias")
+
+    def attention_backward_panels_bias_heads(self, batches, heads, Q, K, V, dBias, bias_stride, O, GO, dLse, D, Dv, GQ=None,
+                                             GK=None, GV=None, dGBias=0, gbias_stride=0, scale=1.0, stream=0, dtype=F16):
+        """bsmr_attention_backward_panels_bias_heads: attention_backward_panels_bias over batches x heads
+        slices; gbias_stride >= nnz elements between the slices' gradients (a shared bias gets one
+        gradient per slice: the caller sums)."""
+        ops = [AttentionOperand.of(x) for x in (Q, K, V, O, GO, GQ, GK, GV)]
+        ref = [None if o is None else C.byref(o) for o in ops]
+        _check(lib().bsmr_attention_backward_panels_bias_heads(
+            self.h, batches, heads, ref[0], ref[1], ref[2], dBias or None, bias_stride, ref[3], ref[4], dLse or None, D, Dv,
+            dtype, scale, ref[5], ref[6], ref[7], dGBias or None, gbias_stride, stream or None),
+            "bsmr_attention_backward_panels_bias_heads")
+
+    def prepare_attention_panels_bias(self, D, Dv, slices=None, backward=False):
+        """bsmr_plan_prepare_attention[_backward]_panels_bias[_heads]: the unbiased prepare plus the entry
+        positions the bias is gathered through, so that the first biased launch can be captured."""
+        stem = "bsmr_plan_prepare_attention_backward_panels_bias" if backward else "bsmr_plan_prepare_attention_panels_bias"
+        if slices is None:
+            _check(getattr(lib(), stem)(self.h, D, Dv), stem)
+        else:
+            _check(getattr(lib(), stem + "_heads")(self.h, D, Dv, slices), stem + "_heads")
+
+    def attention_panels_bias_prepared(self, D, Dv, slices=None, backward=False):
+        stem = "bsmr_plan_attention_backward_panels_bias" if backward else "bsmr_plan_attention_panels_bias"
+        if slices is None:
+            return bool(getattr(lib(), stem + "_prepared")(self.h, D, Dv))
+        return bool(getattr(lib(), stem + "_heads_prepared")(self.h, D, Dv, slices))
 
     def sddmm_backward(self, dG, dA, dB, K, dGA, dGB, stream=0, dtype=F32, backward="gather"):
         """The gradients of P = sddmm(A, B) from dG = dL/dP (fp32, nnz): dGA (M x K fp32) =

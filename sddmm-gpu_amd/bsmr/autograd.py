@@ -394,7 +394,87 @@ def _validate_backward_panels(who, Q, D, Dv):
                          f"{Q.dtype}, D = {D}, Dv = {Dv}")
 
 
-def attention_fused(plan, Q, K, V, scale=None, return_lse=False, backward="recompute", forward="gather"):
+def _validate_bias(who, plan, bias, Q, D, Dv, forward, backward, lead=None):
+    """The checks of a bias, before any launch: the biased kernels are the panel ones, so forward and
+    backward must both be "panels" (D, Dv in {32, 64, 128}); bias is float32 on Q's device, (nnz,) or,
+    for heads, lead[-k:] + (nnz,)."""
+    if forward != "panels":
+        raise ValueError(f"{who}: bias needs forward = \"panels\", got forward = {forward!r}")
+    if backward != "panels":
+        raise ValueError(f"{who}: bias needs backward = \"panels\", got backward = {backward!r}")
+    _validate_backward_panels(who, Q, D, Dv)  # (the biased forward has the backward's forms: no 256)
+    if plan.nnz == 0:  # (an empty bias tensor has no address to pass)
+        raise ValueError(f"{who}: bias needs a pattern with stored entries, the plan's has none")
+    if not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32 or bias.device != Q.device:
+        raise ValueError(f"{who}: bias must be a float32 tensor on {Q.device}")
+    shapes = [(plan.nnz,)] + ([lead[-k:] + (plan.nnz,) for k in range(1, len(lead) + 1)] if lead else [])
+    if tuple(bias.shape) not in shapes:
+        raise ValueError(f"{who}: bias must have one of the shapes {shapes}, got {tuple(bias.shape)}")
+
+
+class _AttentionFusedBias(torch.autograd.Function):
+    """attention_fused / attention_fused_heads with a bias: one Plan.attention_panels_bias[_heads] call
+    forward, which saves Q, K, V, the bias, O and LSE, and one Plan.attention_backward_panels_bias[_heads]
+    call backward. bias is (nnz,) (shared by all slices: its gradient is the sum over the slices, done
+    in torch) or lead + (nnz,), contiguous."""
+
+    @staticmethod
+    def forward(ctx, Q, K, V, bias, plan, scale, want_lse, lead, D, Dv, dtype):
+        B, H = (1,) * (2 - len(lead)) + lead
+        b = _launchable(bias.detach().contiguous().view(-1)).view(-1)
+        ctx.stride = 0 if bias.dim() == 1 else plan.nnz
+        lse = torch.empty(lead + (max(plan.M, 1),), dtype=torch.float32, device=Q.device)
+        if lead:
+            O = _dense_like(Q, lead + (plan.M, Dv))
+            plan.attention_panels_bias_heads(B, H, Q, K, V, b.data_ptr(), ctx.stride, D, Dv, O, lse.data_ptr(), scale,
+                                             stream=_stream(), dtype=dtype)
+        else:
+            O = torch.empty((plan.M, Dv), dtype=torch.float32, device=Q.device)
+            plan.attention_panels_bias(Q.data_ptr(), K.data_ptr(), V.data_ptr(), b.data_ptr(), D, Dv, O.data_ptr(),
+                                       lse.data_ptr(), scale, stream=_stream(), dtype=dtype)
+        ctx.plan, ctx.scale, ctx.dims, ctx.bias_shape = plan, scale, (lead, B, H, D, Dv, dtype), tuple(bias.shape)
+        ctx.save_for_backward(Q, K, V, b, O, lse)
+        lse = lse[..., :plan.M]
+        if not want_lse:
+            return O
+        ctx.mark_non_differentiable(lse)
+        return O, lse
+
+    @staticmethod
+    def backward(ctx, grad, *_):
+        Q, K, V, b, O, lse = ctx.saved_tensors
+        plan = ctx.plan
+        lead, B, H, D, Dv, dtype = ctx.dims
+        need = ctx.needs_input_grad[:4]
+        if not any(need):
+            return (None,) * 11
+        nnz = plan.nnz
+        gb = torch.empty((B * H, max(nnz, 1)), dtype=torch.float32, device=Q.device) if need[3] else None
+        if lead:
+            dO = grad if grad.dtype == torch.float32 else grad.float()
+            if dO.stride(-1) != 1 or attention_layout_check(dO, B, H, plan.M, Dv, 4, False) is not None:
+                dO = dO.contiguous()
+            out = [_dense_like(X, X.shape) if n else None for n, X in zip(need[:3], (Q, K, V))]
+            plan.attention_backward_panels_bias_heads(B, H, Q, K, V, b.data_ptr(), ctx.stride, O, dO, lse.data_ptr(), D, Dv,
+                                                      out[0], out[1], out[2], 0 if gb is None else gb.data_ptr(),
+                                                      gb.shape[1] if gb is not None else 0, ctx.scale, stream=_stream(),
+                                                      dtype=dtype)
+        else:
+            dO = grad.contiguous().float()
+            out = [torch.empty(shape, dtype=torch.float32, device=Q.device) if n else None
+                   for n, shape in zip(need[:3], ((plan.M, D), (plan.N, D), (plan.N, Dv)))]
+            ptr = [0 if t is None else t.data_ptr() for t in out]
+            plan.attention_backward_panels_bias(Q.data_ptr(), K.data_ptr(), V.data_ptr(), b.data_ptr(), O.data_ptr(),
+                                                dO.data_ptr(), lse.data_ptr(), D, Dv, ptr[0], ptr[1], ptr[2],
+                                                0 if gb is None else gb.data_ptr(), ctx.scale, stream=_stream(), dtype=dtype)
+        gQ, gK, gV = (None if t is None else t.to(X.dtype) for t, X in zip(out, (Q, K, V)))
+        if gb is not None:
+            gb = gb[:, :nnz]
+            gb = gb.sum(0) if len(ctx.bias_shape) == 1 else gb.reshape(ctx.bias_shape)
+        return (gQ, gK, gV, gb) + (None,) * 7
+
+
+def attention_fused(plan, Q, K, V, scale=None, return_lse=False, backward="recompute", forward="gather", bias=None):
     """O (M, Dv) float32 of attention(plan, Q, K, V, scale) from one fused forward launch
     (Plan.attention: no nnz-sized scores or weights are written), and with return_lse=True also
     LSE (M,) float32 = max * scale + ln(sum) per row (-inf for an empty row), returned
@@ -423,7 +503,13 @@ def attention_fused(plan, Q, K, V, scale=None, return_lse=False, backward="recom
     backward="panels": what backward="fused" saves, and the backward is one
     Plan.attention_backward_panels call (float16 / bfloat16, D and Dv in {32, 64, 128}; matrix
     instructions per 16-row and per 16-column panel; GO, the weights and the score gradients are
-    rounded once to the operand dtype). ValueError before any launch for float32 or another D / Dv."""
+    rounded once to the operand dtype). ValueError before any launch for float32 or another D / Dv.
+
+    bias: (nnz,) float32 on Q's device, one additive term per stored entry at its CSR position:
+    softmax(scale * S .* (Q @ K.T) + bias); -inf removes an entry. It needs forward="panels" and
+    backward="panels" (D, Dv in {32, 64, 128}): any other value raises ValueError naming the
+    argument, nothing is rerouted. bias.requires_grad yields bias.grad (Plan.attention_backward_panels_bias'
+    GBias). bias=None is the path as it was."""
     if backward not in ("recompute", "fused", "panels"):
         raise ValueError(f"attention_fused: backward = {backward!r} must be \"recompute\", \"fused\" or \"panels\"")
     if scale is None:
@@ -431,8 +517,11 @@ def attention_fused(plan, Q, K, V, scale=None, return_lse=False, backward="recom
             raise ValueError("attention_fused: Q must be an (M, D) tensor with D > 0")
         scale = Q.shape[1] ** -0.5
     scale = _valid_scale("attention_fused", scale)
-    D, Dv, _ = _validate_fused(plan, Q, K, V)
+    D, Dv, dtype = _validate_fused(plan, Q, K, V)
     panels = _validate_forward("attention_fused", forward, Q, D, Dv)
+    if bias is not None:
+        _validate_bias("attention_fused", plan, bias, Q, D, Dv, forward, backward)
+        return _AttentionFusedBias.apply(Q, K, V, bias, plan, scale, bool(return_lse), (), D, Dv, dtype)
     if backward == "panels":
         _validate_backward_panels("attention_fused", Q, D, Dv)
     if backward == "recompute":
@@ -527,7 +616,7 @@ class _AttentionFusedHeads(torch.autograd.Function):
         return gQ, gK, gV, None, None, None, None, None, None
 
 
-def attention_fused_heads(plan, Q, K, V, scale=None, return_lse=False, forward="gather", backward="fused"):
+def attention_fused_heads(plan, Q, K, V, scale=None, return_lse=False, forward="gather", backward="fused", bias=None):
     """attention_fused(..., backward="fused") over heads and an optional batch of one sparsity
     pattern: Q (H, M, D) or (B, H, M, D), K and V the same with N rows (V of width Dv). Returns O
     (..., M, Dv) float32 and, with return_lse=True, LSE (..., M) float32, non-differentiable.
@@ -548,7 +637,10 @@ def attention_fused_heads(plan, Q, K, V, scale=None, return_lse=False, forward="
     backward="fused") on contiguous copies of that slice. forward="panels" as in attention_fused:
     one Plan.attention_panels_heads call instead of Plan.attention_heads. backward="fused" (the
     default) is the backward above; backward="panels" is one Plan.attention_backward_panels_heads call
-    instead, under attention_fused's rules for it; any other value raises ValueError."""
+    instead, under attention_fused's rules for it; any other value raises ValueError.
+
+    bias: as in attention_fused, float32 of shape (nnz,) (one bias for all slices; its gradient is the
+    sum of the slices' gradients), (H, nnz) or (B, H, nnz); forward and backward must both be "panels"."""
     if backward not in ("fused", "panels"):
         raise ValueError(f"attention_fused_heads: backward = {backward!r} must be \"fused\" or \"panels\"")
     if scale is None:
@@ -558,6 +650,12 @@ def attention_fused_heads(plan, Q, K, V, scale=None, return_lse=False, forward="
     scale = _valid_scale("attention_fused_heads", scale)
     checked = _validate_heads(plan, Q, K, V)
     panels = _validate_forward("attention_fused_heads", forward, Q, checked[1], checked[2])
+    if bias is not None:
+        lead, D, Dv, dtype = checked
+        _validate_bias("attention_fused_heads", plan, bias, Q, D, Dv, forward, backward, lead)
+        if bias.dim() > 1:  # (a bias per head of a batched call: one copy per slice; torch sums its gradient)
+            bias = bias.expand(lead + (plan.nnz,)).contiguous()
+        return _AttentionFusedBias.apply(Q, K, V, bias, plan, scale, bool(return_lse), lead, D, Dv, dtype)
     if backward == "panels":
         _validate_backward_panels("attention_fused_heads", Q, checked[1], checked[2])
     return _AttentionFusedHeads.apply(Q, K, V, plan, scale, bool(return_lse), checked, panels, backward == "panels")

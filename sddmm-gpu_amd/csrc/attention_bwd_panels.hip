@@ -51,6 +51,7 @@
 #include "attention_common.hpp"
 #include "attention_layout.hpp"
 #include "attention_panels.hpp"
+#include "attention_panels_args.hpp"  // attn_panels_check_bias
 #include "panel_host.hpp"
 #include "panel_mfma.hpp"
 #include "plan.hpp"
@@ -74,14 +75,27 @@ struct BwdPanelArgs {
     float* P1;               // columns side: behind them, slices x partials x 16 x Dv
     u32 partials, heads, M, nDst, nItems;  // nDst: M on the rows side, N on the columns side
     float scale;
+    // the BIAS instantiations only (null / 0 elsewhere): the side's entry positions (spmm_panels.hpp:
+    // on the columns side the CSR index carried through the transpose), the bias and, on the rows
+    // side, GBias (null: not asked for), nnz fp32 values at CSR positions per slice, with their
+    // slice strides in elements (bias: 0 is one for all slices)
+    const u32* base;
+    const u32* pos;
+    const float* bias;
+    float* gbias;
+    u64 biasStride, gbiasStride;
 };
+
+constexpr u32 NO_ENTRY = 0xFFFFFFFFu;  // the position of a slot whose mask bit is clear
 
 // attention_bwd.hip's weight_of, every product and difference rounded on its own, and then the
 // forward's rule: exactly +0 where the entry is not stored, whatever the products were
+template <bool BIAS = false>
 __device__ __forceinline__ void panel_weight(float p, float g, float lse, float dl, float scale, bool stored, float& w,
-                                             float& dp) {
+                                             float& dp, float b = 0.f, float* h = nullptr) {
 #pragma clang fp contract(off)
-    const float x = p * scale;
+    float x = p * scale;
+    if constexpr (BIAS) x = x + b;  // (the biased form's x: the sum rounded on its own)
     const float d = x - lse;
     const float t = d * LOG2E_F;
     const float wv = lse == -INFINITY ? 0.f : exp2_hw(t);
@@ -90,6 +104,26 @@ __device__ __forceinline__ void panel_weight(float p, float g, float lse, float 
     const float dv = wg * scale;
     w = stored ? wv : 0.f;
     dp = stored ? dv : 0.f;
+    if constexpr (BIAS) *h = wg;  // GBias of a stored entry
+}
+
+// The biased form's gather (attention_panels_bias.hip): the positions of destination d's entries at
+// the lane's eight step slots, pos[base[d] + popcount(mask_d below the slot)], and the bias there;
+// each load predicated on the mask bit
+__device__ __forceinline__ void bias_positions(const u32* pos, u32 mask, u32 b, u32 g, u32* p) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const u32 c = panel_slot(g, j);
+        p[j] = NO_ENTRY;
+        if ((mask >> c) & 1u) p[j] = pos[b + __builtin_popcount(mask & ((1u << c) - 1u))];
+    }
+}
+__device__ __forceinline__ void bias_values(const float* bias, const u32* p, float* w) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        w[j] = 0.f;
+        if (p[j] != NO_ENTRY) w[j] = bias[p[j]];
+    }
 }
 
 // eight consecutive fp32 elements rounded once to the operand type
@@ -99,7 +133,7 @@ __device__ __forceinline__ uint4 load8_rounded(const char* p) {
     return make_uint4(pack2<DT>(lo.x, lo.y), pack2<DT>(lo.z, lo.w), pack2<DT>(hi.x, hi.y), pack2<DT>(hi.z, hi.w));
 }
 
-template <int DT, int D, int DV>
+template <int DT, int D, int DV, bool BIAS>
 __global__ __launch_bounds__(PANEL_WAVES * 64) __attribute__((amdgpu_waves_per_eu(2)))
 void k_attention_bwd_panels_rows(const BwdPanelArgs a) {
     constexpr int KS = D / 32;                 // k-steps of a score tile, and pairs of GQ tiles
@@ -154,6 +188,21 @@ void k_attention_bwd_panels_rows(const BwdPanelArgs a) {
         }
     };
     if (it.nsteps) load_kv(st);
+    // BIAS: the step's positions (kept for the GBias stores) and biases. The next step's positions
+    // are requested before the K rows are staged, its values once this step's weights are formed (the
+    // registers of this step's values take them: a second set spills at 128 / 128), so they are in
+    // flight under the second product
+    const u32* bs = BIAS ? a.base + static_cast<size_t>(it.step0) * PANEL_ROWS : nullptr;
+    const float* bias = BIAS ? a.bias + slice * a.biasStride : nullptr;
+    float* gbias = BIAS && a.gbias ? a.gbias + slice * a.gbiasStride : nullptr;
+    u32 pc[BIAS ? 8 : 1], pn[BIAS ? 8 : 1];
+    float b[BIAS ? 8 : 1];
+    if constexpr (BIAS) {
+        if (it.nsteps) {
+            bias_positions(a.pos, st->masks[r], bs[r], g, pc);
+            bias_values(bias, pc, b);
+        }
+    }
     for (u32 step = 0; step < it.nsteps; ++step, ++st) {
         const u32 colv = st->cols[lane & 31u];  // lane x holds step column x & 31
         const u32 mask = st->masks[r];
@@ -169,6 +218,10 @@ void k_attention_bwd_panels_rows(const BwdPanelArgs a) {
             g1 = mfma32<DT>(v1[s], go[s], g1);
         }
         if (step + 1 < it.nsteps) load_kv(st + 1);
+        if constexpr (BIAS) {
+            bs += PANEL_ROWS;
+            if (step + 1 < it.nsteps) bias_positions(a.pos, st[1].masks[r], bs[r], g, pn);
+        }
 
         // the step's K rows into LDS: chunk x = 64 u + lane is 16 bytes of row x / CPR. The reads of
         // the step before are done first
@@ -189,10 +242,31 @@ void k_attention_bwd_panels_rows(const BwdPanelArgs a) {
         }
 
         float w, dp[8];
+        if constexpr (BIAS) {
+            float h[8];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            panel_weight(s0[j], g0[j], lse, dl, a.scale, (mask >> panel_slot(g, j)) & 1u, w, dp[j]);
-            panel_weight(s1[j], g1[j], lse, dl, a.scale, (mask >> panel_slot(g, 4 + j)) & 1u, w, dp[4 + j]);
+            for (int j = 0; j < 4; ++j) {
+                panel_weight<true>(s0[j], g0[j], lse, dl, a.scale, (mask >> panel_slot(g, j)) & 1u, w, dp[j], b[j], &h[j]);
+                panel_weight<true>(s1[j], g1[j], lse, dl, a.scale, (mask >> panel_slot(g, 4 + j)) & 1u, w, dp[4 + j], b[4 + j],
+                                   &h[4 + j]);
+            }
+            // GBias: one 4-byte store per set mask bit; every stored entry lies in one step of one item
+            if (gbias) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j)
+                    if (pc[j] != NO_ENTRY) gbias[pc[j]] = h[j];
+            }
+            if (step + 1 < it.nsteps) {  // (the positions arrived under the K loads)
+#pragma unroll
+                for (int j = 0; j < 8; ++j) pc[j] = pn[j];
+                bias_values(bias, pc, b);
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                panel_weight(s0[j], g0[j], lse, dl, a.scale, (mask >> panel_slot(g, j)) & 1u, w, dp[j]);
+                panel_weight(s1[j], g1[j], lse, dl, a.scale, (mask >> panel_slot(g, 4 + j)) & 1u, w, dp[4 + j]);
+            }
         }
         const uint4 pb = pack8<DT>(dp);
 
@@ -206,13 +280,14 @@ void k_attention_bwd_panels_rows(const BwdPanelArgs a) {
         }
     }
     if (!live) return;
+    if (BIAS && !a.Y0.ptr) return;  // (only GBias was asked for)
     float* o = it.part == PANEL_DIRECT
                    ? reinterpret_cast<float*>(attn_slice_base(a.Y0, bat, head) + static_cast<size_t>(row) * a.Y0.row)
                    : a.P0 + ((slice * a.partials + it.part) * PANEL_ROWS + r) * D;
     store_acc<KS>(o + 8u * g, acc);
 }
 
-template <int DT, int D, int DV>
+template <int DT, int D, int DV, bool BIAS>
 __global__ __launch_bounds__(PANEL_WAVES * 64) __attribute__((amdgpu_waves_per_eu(2)))
 void k_attention_bwd_panels_cols(const BwdPanelArgs a) {
     constexpr int KS = D / 32;                  // k-steps of a score tile, and pairs of GK tiles
@@ -257,10 +332,20 @@ void k_attention_bwd_panels_cols(const BwdPanelArgs a) {
     for (int n = 0; n < 2 * VS; ++n) accV[n] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     const PanelStep* st = a.steps + it.step0;
+    const u32* bs = BIAS ? a.base + static_cast<size_t>(it.step0) * PANEL_ROWS : nullptr;
+    const float* bias = BIAS ? a.bias + slice * a.biasStride : nullptr;
     for (u32 step = 0; step < it.nsteps; ++step, ++st) {
         const u32 rowv = st->cols[lane & 31u];  // lane x holds step row x & 31 with its LSE and delta
         const u32 mask = st->masks[c];
         const float lsev = lses[rowv], dlv = deltas[rowv];
+        // BIAS: the positions of the column's entries at the lane's step rows are requested before the
+        // stage's loads and the values after them, so both rounds lie under the staging
+        u32 pc[BIAS ? 8 : 1];
+        float b[BIAS ? 8 : 1];
+        if constexpr (BIAS) {
+            bias_positions(a.pos, mask, bs[c], g, pc);
+            bs += PANEL_ROWS;
+        }
 
         // the step's Q rows and rounded GO rows into LDS; the reads of the step before are done first
         wave_lds_sync();
@@ -296,6 +381,7 @@ void k_attention_bwd_panels_cols(const BwdPanelArgs a) {
                 *reinterpret_cast<uint4*>(gl + (x / GCPR) * GROW + (x % GCPR) * 16u) = gg[u];
             }
         }
+        if constexpr (BIAS) bias_values(bias, pc, b);
         wave_lds_sync();
 
         f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = {0.f, 0.f, 0.f, 0.f}, g0 = {0.f, 0.f, 0.f, 0.f}, g1 = {0.f, 0.f, 0.f, 0.f};
@@ -314,8 +400,11 @@ void k_attention_bwd_panels_cols(const BwdPanelArgs a) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int r0 = static_cast<int>(4u * g + j), r1 = static_cast<int>(16u + 4u * g + j);
-            panel_weight(s0[j], g0[j], __shfl(lsev, r0), __shfl(dlv, r0), a.scale, (mask >> r0) & 1u, w[j], dp[j]);
-            panel_weight(s1[j], g1[j], __shfl(lsev, r1), __shfl(dlv, r1), a.scale, (mask >> r1) & 1u, w[4 + j], dp[4 + j]);
+            float h;
+            panel_weight<BIAS>(s0[j], g0[j], __shfl(lsev, r0), __shfl(dlv, r0), a.scale, (mask >> r0) & 1u, w[j], dp[j],
+                               BIAS ? b[j] : 0.f, &h);
+            panel_weight<BIAS>(s1[j], g1[j], __shfl(lsev, r1), __shfl(dlv, r1), a.scale, (mask >> r1) & 1u, w[4 + j], dp[4 + j],
+                               BIAS ? b[BIAS ? 4 + j : 0] : 0.f, &h);
         }
         const uint4 wb = pack8<DT>(w), pb = pack8<DT>(dp);
         // (the scheduler otherwise hoists both products' 16 (VS + KS) word reads over the weights: spills
@@ -385,24 +474,29 @@ __global__ __launch_bounds__(256) void k_attention_bwd_panels_reduce(const BwdPa
 
 using BwdPanelFn = void (*)(const BwdPanelArgs);
 
-template <int DT, int D>
+template <int DT, int D, bool BIAS>
 BwdPanelFn pick_dv(bool rows, u32 Dv) {
     switch (Dv) {
-        case 32: return rows ? k_attention_bwd_panels_rows<DT, D, 32> : k_attention_bwd_panels_cols<DT, D, 32>;
-        case 64: return rows ? k_attention_bwd_panels_rows<DT, D, 64> : k_attention_bwd_panels_cols<DT, D, 64>;
-        case 128: return rows ? k_attention_bwd_panels_rows<DT, D, 128> : k_attention_bwd_panels_cols<DT, D, 128>;
+        case 32: return rows ? k_attention_bwd_panels_rows<DT, D, 32, BIAS> : k_attention_bwd_panels_cols<DT, D, 32, BIAS>;
+        case 64: return rows ? k_attention_bwd_panels_rows<DT, D, 64, BIAS> : k_attention_bwd_panels_cols<DT, D, 64, BIAS>;
+        case 128: return rows ? k_attention_bwd_panels_rows<DT, D, 128, BIAS> : k_attention_bwd_panels_cols<DT, D, 128, BIAS>;
         default: return nullptr;
     }
 }
 
-template <int DT>
+template <int DT, bool BIAS>
 BwdPanelFn pick_d(bool rows, u32 D, u32 Dv) {
     switch (D) {
-        case 32: return pick_dv<DT, 32>(rows, Dv);
-        case 64: return pick_dv<DT, 64>(rows, Dv);
-        case 128: return pick_dv<DT, 128>(rows, Dv);
+        case 32: return pick_dv<DT, 32, BIAS>(rows, Dv);
+        case 64: return pick_dv<DT, 64, BIAS>(rows, Dv);
+        case 128: return pick_dv<DT, 128, BIAS>(rows, Dv);
         default: return nullptr;
     }
+}
+
+template <bool BIAS>
+BwdPanelFn pick_kernel(bool rows, u32 D, u32 Dv, int dtype) {
+    return dtype == BSMR_F16 ? pick_d<BSMR_F16, BIAS>(rows, D, Dv) : pick_d<BSMR_BF16, BIAS>(rows, D, Dv);
 }
 
 size_t bwdp_row_floats(const Plan& p, u32 D, u32 slices) {
@@ -435,9 +529,31 @@ struct BwdPanelOperands {
     const bsmr_attention_operand *Q, *K, *V, *O, *GO, *GQ, *GK, *GV;  // the last three may be null, not all
 };
 
-// the launches of bsmr_attention_backward_panels and its heads form, arguments already validated
+// the per-entry bias of a biased backward and its gradient (null: not asked for), nnz fp32 values at
+// CSR positions per slice, strides in elements (bias: 0 is one for all slices)
+struct BwdPanelBias {
+    const float* bias;
+    u64 biasStride;
+    float* gbias;
+    u64 gbiasStride;
+};
+
+// the biased backward also needs both sides' entry positions (the one copy in Plan::spmm_panels,
+// spmm_panels_build_positions; no scratch of the panel SpMM)
+bool bwdp_bias_ready(const Plan& p, u32 D, u32 Dv, u32 slices) {
+    return bwdp_ready(p, D, Dv, slices) && p.spmm_panels[0].built && p.spmm_panels[1].built;
+}
+
+int build_bwdp_bias(const Plan& p, u32 D, u32 Dv, u32 slices, const char* who) {
+    BSMR_CHECK(build_bwdp(p, D, Dv, slices, who));
+    BSMR_CHECK(spmm_panels_build_positions(p, 1, who));
+    return spmm_panels_build_positions(p, 2, who);
+}
+
+// the launches of bsmr_attention_backward_panels, its heads form and their biased forms (`bias`),
+// arguments already validated
 int bwdp_launch(const char* who, const char* prep, const bsmr_plan* plan, u32 batches, u32 heads, const BwdPanelOperands& x,
-                const float* dLse, u32 D, u32 Dv, int dtype, float scale, void* stream) {
+                const float* dLse, u32 D, u32 Dv, int dtype, float scale, void* stream, const BwdPanelBias* bias = nullptr) {
     const Plan& p = plan->p;
     const hipStream_t s = static_cast<hipStream_t>(stream);
     const u32 slices = batches * heads;  // (both at most 65535)
@@ -448,12 +564,14 @@ int bwdp_launch(const char* who, const char* prep, const bsmr_plan* plan, u32 ba
     {
         std::lock_guard<std::mutex> g(p.layout_mu);
         BSMR_CHECK(panel_build_missing(
-            LaunchSite{s, who, prep, D, dtype}, [&] { return bwdp_ready(p, D, Dv, slices); },
+            LaunchSite{s, who, prep, D, dtype},
+            [&] { return bias ? bwdp_bias_ready(p, D, Dv, slices) : bwdp_ready(p, D, Dv, slices); },
             [&] {
-                return "the panel backward's lists (or their scratch for D = " + std::to_string(D) + ", Dv = " + std::to_string(Dv) +
+                return std::string("the panel backward's lists") + (bias ? ", the entry positions" : "") +
+                       " (or their scratch for D = " + std::to_string(D) + ", Dv = " + std::to_string(Dv) +
                        panel_slices_clause(slices) + ")";
             },
-            [&] { return build_bwdp(p, D, Dv, slices, prep); }));
+            [&] { return bias ? build_bwdp_bias(p, D, Dv, slices, prep) : build_bwdp(p, D, Dv, slices, prep); }));
         const Plan::PanelListState &R = p.panel_rows, &C = p.panel_cols;
         const Plan::AttentionBwdPanelsState& B = p.attention_bwd_panels;
         r.items = R.items.data();
@@ -472,6 +590,18 @@ int bwdp_launch(const char* who, const char* prep, const bsmr_plan* plan, u32 ba
         creds = C.reds.data();
         colReds = C.nReds;
         delta = B.delta.data();
+        if (bias) {
+            r.base = p.spmm_panels[0].base.data();
+            r.pos = p.spmm_panels[0].pos.data();
+            cs.base = p.spmm_panels[1].base.data();
+            cs.pos = p.spmm_panels[1].pos.data();
+        }
+    }
+    if (bias) {
+        r.bias = cs.bias = bias->bias;
+        r.biasStride = cs.biasStride = bias->biasStride;
+        r.gbias = bias->gbias;
+        r.gbiasStride = bias->gbiasStride;
     }
     cs.P1 = cs.P0 ? cs.P0 + static_cast<size_t>(slices) * cs.partials * PANEL_ROWS * D : nullptr;
     r.Q = cs.Q = attn_op_bytes(x.Q, batches, heads, p.M, 2u);
@@ -490,13 +620,13 @@ int bwdp_launch(const char* who, const char* prep, const bsmr_plan* plan, u32 ba
     cs.Y1 = attn_op_bytes(x.GV, batches, heads, p.N, 4u);
 
     BSMR_CHECK(attn_bwd_launch_delta(r.GO, attn_op_bytes(x.O, batches, heads, p.M, 4u), delta, batches, heads, p.M, D, Dv, 2u, s));
-    const bool f16 = dtype == BSMR_F16;
     auto side = [&](const BwdPanelArgs& a, bool rows, const PanelRed* reds, u32 nReds, u32 q4) {
         const dim3 outer(1, heads, batches);
-        return panel_launch(s, f16 ? pick_d<BSMR_F16>(rows, D, Dv) : pick_d<BSMR_BF16>(rows, D, Dv), a, a.nItems, outer,
-                            k_attention_bwd_panels_reduce, reds, nReds, q4, outer, D, Dv);
+        return panel_launch(s, bias ? pick_kernel<true>(rows, D, Dv, dtype) : pick_kernel<false>(rows, D, Dv, dtype), a, a.nItems,
+                            outer, k_attention_bwd_panels_reduce, reds, nReds, q4, outer, D, Dv);
     };
-    if (x.GQ) BSMR_CHECK(side(r, true, rreds, rowReds, D / 4u));
+    // (the rows side also runs for GBias alone: it then stores no GQ and has nothing to reduce)
+    if (x.GQ || (bias && bias->gbias)) BSMR_CHECK(side(r, true, rreds, x.GQ ? rowReds : 0u, D / 4u));
     if (x.GK || x.GV) BSMR_CHECK(side(cs, false, creds, colReds, (x.GK ? D / 4u : 0u) + (x.GV ? Dv / 4u : 0u)));
     return BSMR_OK;
 }
@@ -643,4 +773,124 @@ extern "C" int bsmr_plan_attention_backward_panels_stats(const bsmr_plan* plan, 
         out->delta_bytes = B.delta.size() * sizeof(float);
     }
     return BSMR_OK;
+}
+
+// ---- the biased forms (x = fl(p scale) + bias; attention_panels_bias.hip is the forward) ----
+
+// what the biased entry points check beyond the unbiased ones: dBias, dGBias and their strides
+static int bwd_bias_check(const char* who, const bsmr_plan* plan, const float* dBias, u64 biasStride, const float* dGBias,
+                          u64 gbiasStride) {
+    BSMR_CHECK(attn_panels_check_bias(who, plan, dBias, biasStride));
+    if (reinterpret_cast<uintptr_t>(dGBias) & 3u) {
+        set_error(std::string(who) + ": dGBias must be 4-byte aligned");
+        return BSMR_ERR_INVALID;
+    }
+    if (dGBias && gbiasStride < plan->p.nnz) {
+        set_error(std::string(who) + ": gbias_slice_stride must be at least nnz (a shared bias gets one gradient per slice)");
+        return BSMR_ERR_INVALID;
+    }
+    return BSMR_OK;
+}
+
+extern "C" int bsmr_attention_backward_panels_bias(const bsmr_plan* plan, const void* dQ, const void* dK, const void* dV,
+                                                   const float* dBias, const float* dO, const float* dGO, const float* dLse,
+                                                   uint32_t D, uint32_t Dv, int dtype, float scale, float* dGQ, float* dGK,
+                                                   float* dGV, float* dGBias, void* stream) {
+    const char* who = "bsmr_attention_backward_panels_bias";
+    if (!plan) {
+        set_error(std::string(who) + ": null plan");
+        return BSMR_ERR_INVALID;
+    }
+    if (!dQ || !dK || !dV || !dO || !dGO || !dLse) {
+        set_error(std::string(who) + ": null device pointer");
+        return BSMR_ERR_INVALID;
+    }
+    if (!dGQ && !dGK && !dGV && !dGBias) {
+        set_error(std::string(who) + ": dGQ, dGK, dGV and dGBias are all null: nothing to compute");
+        return BSMR_ERR_INVALID;
+    }
+    if (!attn_aligned16(dQ) || !attn_aligned16(dK) || !attn_aligned16(dV) || !attn_aligned16(dO) ||
+        !attn_aligned16(dGO) || !attn_aligned16(dGQ) || !attn_aligned16(dGK) || !attn_aligned16(dGV) ||
+        (reinterpret_cast<uintptr_t>(dLse) & 3u)) {
+        set_error(std::string(who) + ": dQ, dK, dV, dO, dGO, dGQ, dGK and dGV must be 16-byte aligned");
+        return BSMR_ERR_INVALID;
+    }
+    const Plan& p = plan->p;
+    BSMR_CHECK(bwd_bias_check(who, plan, dBias, 0, dGBias, p.nnz));
+    float c;
+    BSMR_CHECK(attn_validate_scale(who, scale, &c));
+    BSMR_CHECK(panel_validate_dims(who, D, Dv, dtype, false));
+    const bsmr_attention_operand q = attention_dense_operand(dQ, 1, p.M, D), k = attention_dense_operand(dK, 1, p.N, D),
+                                 v = attention_dense_operand(dV, 1, p.N, Dv), o = attention_dense_operand(dO, 1, p.M, Dv),
+                                 go = attention_dense_operand(dGO, 1, p.M, Dv), gq = attention_dense_operand(dGQ, 1, p.M, D),
+                                 gk = attention_dense_operand(dGK, 1, p.N, D), gv = attention_dense_operand(dGV, 1, p.N, Dv);
+    const BwdPanelOperands x{&q, &k, &v, &o, &go, dGQ ? &gq : nullptr, dGK ? &gk : nullptr, dGV ? &gv : nullptr};
+    const BwdPanelBias b{dBias, 0, dGBias, p.nnz};
+    return bwdp_launch(who, "bsmr_plan_prepare_attention_backward_panels_bias", plan, 1, 1, x, dLse, D, Dv, dtype, scale, stream,
+                       &b);
+}
+
+extern "C" int bsmr_attention_backward_panels_bias_heads(
+    const bsmr_plan* plan, uint32_t batches, uint32_t heads, const bsmr_attention_operand* Q, const bsmr_attention_operand* K,
+    const bsmr_attention_operand* V, const float* dBias, uint64_t bias_slice_stride, const bsmr_attention_operand* O,
+    const bsmr_attention_operand* GO, const float* dLse, uint32_t D, uint32_t Dv, int dtype, float scale,
+    const bsmr_attention_operand* GQ, const bsmr_attention_operand* GK, const bsmr_attention_operand* GV, float* dGBias,
+    uint64_t gbias_slice_stride, void* stream) {
+    const char* who = "bsmr_attention_backward_panels_bias_heads";
+    if (!plan) {
+        set_error(std::string(who) + ": null plan");
+        return BSMR_ERR_INVALID;
+    }
+    if (!dLse || (reinterpret_cast<uintptr_t>(dLse) & 3u)) {
+        set_error(std::string(who) + ": dLse must be non-null and 4-byte aligned");
+        return BSMR_ERR_INVALID;
+    }
+    if (!GQ && !GK && !GV && !dGBias) {
+        set_error(std::string(who) + ": GQ, GK, GV and dGBias are all null: nothing to compute");
+        return BSMR_ERR_INVALID;
+    }
+    BSMR_CHECK(bwd_bias_check(who, plan, dBias, bias_slice_stride, dGBias, gbias_slice_stride));
+    float c;
+    BSMR_CHECK(attn_validate_scale(who, scale, &c));
+    BSMR_CHECK(panel_validate_dims(who, D, Dv, dtype, false));
+    const Plan& p = plan->p;
+    BSMR_CHECK(attn_check_operand(who, "Q", Q, batches, heads, p.M, D, 2u, false));
+    BSMR_CHECK(attn_check_operand(who, "K", K, batches, heads, p.N, D, 2u, false));
+    BSMR_CHECK(attn_check_operand(who, "V", V, batches, heads, p.N, Dv, 2u, false));
+    BSMR_CHECK(attn_check_operand(who, "O", O, batches, heads, p.M, Dv, 4u, false));
+    BSMR_CHECK(attn_check_operand(who, "GO", GO, batches, heads, p.M, Dv, 4u, false));
+    if (GQ) BSMR_CHECK(attn_check_operand(who, "GQ", GQ, batches, heads, p.M, D, 4u, true));
+    if (GK) BSMR_CHECK(attn_check_operand(who, "GK", GK, batches, heads, p.N, D, 4u, true));
+    if (GV) BSMR_CHECK(attn_check_operand(who, "GV", GV, batches, heads, p.N, Dv, 4u, true));
+    const BwdPanelOperands x{Q, K, V, O, GO, GQ, GK, GV};
+    const BwdPanelBias b{dBias, bias_slice_stride, dGBias, gbias_slice_stride};
+    return bwdp_launch(who, "bsmr_plan_prepare_attention_backward_panels_bias_heads", plan, batches, heads, x, dLse, D, Dv, dtype,
+                       scale, stream, &b);
+}
+
+extern "C" int bsmr_plan_prepare_attention_backward_panels_bias_heads(const bsmr_plan* plan, uint32_t D, uint32_t Dv,
+                                                                      uint32_t slices) {
+    const char* who = "bsmr_plan_prepare_attention_backward_panels_bias_heads";
+    BSMR_CHECK(panel_prepare_args(who, plan, D, Dv, slices, false));
+    std::lock_guard<std::mutex> g(plan->p.layout_mu);
+    return build_bwdp_bias(plan->p, D, Dv, slices, who);
+}
+
+extern "C" int bsmr_plan_prepare_attention_backward_panels_bias(const bsmr_plan* plan, uint32_t D, uint32_t Dv) {
+    const char* who = "bsmr_plan_prepare_attention_backward_panels_bias";
+    BSMR_CHECK(panel_prepare_args(who, plan, D, Dv, 1, false));
+    std::lock_guard<std::mutex> g(plan->p.layout_mu);
+    return build_bwdp_bias(plan->p, D, Dv, 1, who);
+}
+
+extern "C" int bsmr_plan_attention_backward_panels_bias_heads_prepared(const bsmr_plan* plan, uint32_t D, uint32_t Dv,
+                                                                       uint32_t slices) {
+    if (panel_prepare_args("bsmr_plan_attention_backward_panels_bias_heads_prepared", plan, D, Dv, slices, false) != BSMR_OK)
+        return 0;
+    std::lock_guard<std::mutex> g(plan->p.layout_mu);
+    return bwdp_bias_ready(plan->p, D, Dv, slices) ? 1 : 0;
+}
+
+extern "C" int bsmr_plan_attention_backward_panels_bias_prepared(const bsmr_plan* plan, uint32_t D, uint32_t Dv) {
+    return bsmr_plan_attention_backward_panels_bias_heads_prepared(plan, D, Dv, 1);
 }

@@ -275,6 +275,15 @@ int build_panels(const Plan& p, u32 Dv, u32 slices, const char* who) {
     return p.attention_panels.scratch.grow(panels_scratch_floats(p, Dv, slices));
 }
 
+// the biased form: the lists and scratch above and the rows side's entry positions (the one copy in
+// Plan::spmm_panels[0], spmm_panels_build_positions; no scratch of the panel SpMM)
+bool panels_bias_ready(const Plan& p, u32 Dv, u32 slices) { return panels_ready(p, Dv, slices) && p.spmm_panels[0].built; }
+
+int build_panels_bias(const Plan& p, u32 Dv, u32 slices, const char* who) {
+    BSMR_CHECK(build_panels(p, Dv, slices, who));
+    return spmm_panels_build_positions(p, 1, who);
+}
+
 // the 16-bit form's kernel; the dims are validated
 PanelFn panels_kernel(u32 D, u32 Dv, int dtype) { return dtype == BSMR_F16 ? pick_d<BSMR_F16>(D, Dv) : pick_d<BSMR_BF16>(D, Dv); }
 
@@ -332,7 +341,7 @@ int attn_panels_check_heads(const char* who, const bsmr_plan* plan, const float*
 int attn_panels_launch(const char* who, const char* prep, const bsmr_plan* plan, PanelFn fn, u32 batches, u32 heads,
                        const bsmr_attention_operand& Q, const bsmr_attention_operand& K, const bsmr_attention_operand& V,
                        u32 kvBytes, u32 D, u32 Dv, int dtype, float scale, float c, float vscale,
-                       const bsmr_attention_operand& O, float* dLse, void* stream) {
+                       const bsmr_attention_operand& O, float* dLse, void* stream, const PanelBiasIn* bias) {
     const Plan& p = plan->p;
     const hipStream_t s = static_cast<hipStream_t>(stream);
     const Plan::PanelListState& L = p.panel_rows;
@@ -343,9 +352,12 @@ int attn_panels_launch(const char* who, const char* prep, const bsmr_plan* plan,
     {
         std::lock_guard<std::mutex> g(p.layout_mu);
         BSMR_CHECK(panel_build_missing(
-            LaunchSite{s, who, prep, D, dtype}, [&] { return panels_ready(p, Dv, slices); },
-            [&] { return "the panel lists (or their scratch for Dv = " + std::to_string(Dv) + panel_slices_clause(slices) + ")"; },
-            [&] { return build_panels(p, Dv, slices, prep); }));
+            LaunchSite{s, who, prep, D, dtype}, [&] { return bias ? panels_bias_ready(p, Dv, slices) : panels_ready(p, Dv, slices); },
+            [&] {
+                return std::string("the panel lists") + (bias ? ", the entry positions" : "") + " (or their scratch for Dv = " +
+                       std::to_string(Dv) + panel_slices_clause(slices) + ")";
+            },
+            [&] { return bias ? build_panels_bias(p, Dv, slices, prep) : build_panels(p, Dv, slices, prep); }));
         a.items = L.items.data();
         a.steps = L.steps.data();
         a.rows = L.rows.data();
@@ -354,6 +366,15 @@ int attn_panels_launch(const char* who, const char* prep, const bsmr_plan* plan,
         a.pacc = p.attention_panels.scratch.data();
         reds = L.reds.data();
         nReds = L.nReds;
+        if (bias) {
+            a.base = p.spmm_panels[0].base.data();
+            a.pos = p.spmm_panels[0].pos.data();
+        }
+    }
+    if (bias) {
+        a.bias = bias->bias;
+        a.biasStride = bias->stride;
+        a.xscale = bias->scale;
     }
     a.pml = a.pacc ? a.pacc + static_cast<size_t>(slices) * a.partials * PANEL_ROWS * Dv : nullptr;
     a.Q = attn_op_bytes(&Q, batches, heads, p.M, 2u);
@@ -470,6 +491,40 @@ extern "C" int bsmr_plan_attention_panels_heads_prepared(const bsmr_plan* plan, 
 
 extern "C" int bsmr_plan_attention_panels_prepared(const bsmr_plan* plan, uint32_t D, uint32_t Dv) {
     return bsmr_plan_attention_panels_heads_prepared(plan, D, Dv, 1);
+}
+
+// a biased prepare's (D, Dv): the forms attention_panels_bias.hip builds
+static int bias_prepare_args(const char* who, const bsmr_plan* plan, uint32_t D, uint32_t Dv, uint32_t slices) {
+    BSMR_CHECK(panel_prepare_args(who, plan, D, Dv, slices, true));
+    if (!panels_bias_kernel(D, Dv, BSMR_F16)) {
+        set_error(std::string(who) + ": the biased form of D = " + std::to_string(D) + ", Dv = " + std::to_string(Dv) + " is not built");
+        return BSMR_ERR_UNSUPPORTED;
+    }
+    return BSMR_OK;
+}
+
+extern "C" int bsmr_plan_prepare_attention_panels_bias_heads(const bsmr_plan* plan, uint32_t D, uint32_t Dv, uint32_t slices) {
+    const char* who = "bsmr_plan_prepare_attention_panels_bias_heads";
+    BSMR_CHECK(bias_prepare_args(who, plan, D, Dv, slices));
+    std::lock_guard<std::mutex> g(plan->p.layout_mu);
+    return build_panels_bias(plan->p, Dv, slices, who);
+}
+
+extern "C" int bsmr_plan_prepare_attention_panels_bias(const bsmr_plan* plan, uint32_t D, uint32_t Dv) {
+    const char* who = "bsmr_plan_prepare_attention_panels_bias";
+    BSMR_CHECK(bias_prepare_args(who, plan, D, Dv, 1));
+    std::lock_guard<std::mutex> g(plan->p.layout_mu);
+    return build_panels_bias(plan->p, Dv, 1, who);
+}
+
+extern "C" int bsmr_plan_attention_panels_bias_heads_prepared(const bsmr_plan* plan, uint32_t D, uint32_t Dv, uint32_t slices) {
+    if (bias_prepare_args("bsmr_plan_attention_panels_bias_heads_prepared", plan, D, Dv, slices) != BSMR_OK) return 0;
+    std::lock_guard<std::mutex> g(plan->p.layout_mu);
+    return panels_bias_ready(plan->p, Dv, slices) ? 1 : 0;
+}
+
+extern "C" int bsmr_plan_attention_panels_bias_prepared(const bsmr_plan* plan, uint32_t D, uint32_t Dv) {
+    return bsmr_plan_attention_panels_bias_heads_prepared(plan, D, Dv, 1);
 }
 
 extern "C" int bsmr_plan_attention_panels_stats(const bsmr_plan* plan, bsmr_attention_panels_stats* out) {

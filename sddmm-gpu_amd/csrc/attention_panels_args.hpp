@@ -23,6 +23,21 @@ struct PanelArgs {
     u32 partials, heads, M, nItems;
     float c, scale;  // scale log2(e), rounded once from double; scale
     float vscale;    // multiplies 1 / l once, rounded, before the product with acc (1: the 16-bit form)
+    // the biased form only (attention_panels_bias.hip; null / 0 elsewhere): the rows side's entry
+    // positions (spmm_panels.hpp), the bias with its slice stride in elements (0: one for all slices)
+    // and the scale of the scores; c is then log2(e) and scale 1, the softmax running in x's units
+    const u32* base;
+    const u32* pos;
+    const float* bias;
+    u64 biasStride;
+    float xscale;
+};
+
+// the per-entry bias of a biased launch: nnz fp32 values at CSR positions per slice
+struct PanelBiasIn {
+    const float* bias;
+    u64 stride;   // elements between the slices' biases; 0: one bias shared by all slices
+    float scale;  // the scale of the scores
 };
 
 using PanelFn = void (*)(const PanelArgs);
@@ -41,10 +56,16 @@ int attn_panels_check_heads(const char* who, const bsmr_plan* plan, const float*
 // The launches of a panel forward, arguments already validated: `fn` over the plan's items, then
 // k_attention_panels_reduce over its split panels. K and V hold elements of kvBytes bytes; the
 // lists and the scratch are built first unless `stream` is capturing (BSMR_ERR_NOT_PREPARED, naming
-// `prep`). Defined in attention_panels.hip
+// `prep`). With `bias` (the biased form: c is log2(e) and scale 1) the rows side's entry positions
+// are built with them. Defined in attention_panels.hip
 int attn_panels_launch(const char* who, const char* prep, const bsmr_plan* plan, PanelFn fn, u32 batches, u32 heads,
                        const bsmr_attention_operand& Q, const bsmr_attention_operand& K, const bsmr_attention_operand& V,
                        u32 kvBytes, u32 D, u32 Dv, int dtype, float scale, float c, float vscale,
-                       const bsmr_attention_operand& O, float* dLse, void* stream);
+                       const bsmr_attention_operand& O, float* dLse, void* stream, const PanelBiasIn* bias = nullptr);
+
+// the biased form's checks of dBias and its stride, and its kernel for (D, Dv, dtype): null where the
+// form is not built. Defined in attention_panels_bias.hip
+PanelFn panels_bias_kernel(u32 D, u32 Dv, int dtype);
+int attn_panels_check_bias(const char* who, const bsmr_plan* plan, const float* dBias, u64 stride);
 
 }  // namespace bsmr

@@ -362,7 +362,10 @@ struct Plan {
     // layout_mu; the scratch grows and never shrinks; build_columns keeps all of it. The MFMA SDDMM
     // (sddmm_panels.hip; bsmr_sddmm_mfma) launches over panel_rows and the rows side's base / pos, built
     // through the same builder without the scratch, and holds nothing of its own; stepWaves counts
-    // the waves that get a step when every item's steps are dealt to PANEL_WAVES waves (its stats)
+    // the waves that get a step when every item's steps are dealt to PANEL_WAVES waves (its stats).
+    // The biased panel attention (attention_panels_bias.hip, the BIAS kernels of
+    // attention_bwd_panels.hip) gathers its bias through the same base / pos, the rows side's forward
+    // and both sides' backward, built the same way without the scratch: one copy per side and plan
     struct SpmmPanelsSide {
         bool built = false;
         u32 scratchK = 0, stepWaves = 0;

@@ -87,6 +87,21 @@ DESIGN.md section 20) and one Plan.attention_panels on the same plan, the same Q
 V quantised by bsmr.autograd.quantize_kv and widened again (scale x k_scale as its scale), by the
 same protocol. Per case: graph_us of both, kv8_over_panels16, floor_us of both with section 18's
 count (one byte per K / V element for kv8) and the largest |O_kv8 - v_scale O_panels16|.
+
+    python3 tools/attention_bench.py --forward panels --bias [--cases C2,C5,C3] [--dtype f16|bf16] [--d 64|128]
+    python3 tools/attention_bench.py --backward panels --bias ...
+
+With --bias the tool times, in one run, on one plan and the same tensors and by the
+same protocol, three forms of the forward or of the backward with a per-entry fp32 bias in [-2, 2):
+  * panels: the unbiased Plan.attention_panels / attention_backward_panels (another function: the yardstick
+    for what the gather costs);
+  * bias: Plan.attention_panels_bias / attention_backward_panels_bias (all four gradients);
+  * composed: what a user writes without it. Forward: sddmm, one torch op for P scale + bias, softmax at
+    scale 1, spmm. Backward, from the forward's W: sddmm and spmm_t for dW and dV, softmax_backward at scale
+    1 (the bias gradient), one torch product with scale, spmm and spmm_t for dQ and dK.
+Per case graph_us of the three, bias_over_panels, bias_over_composed, the floors of the unbiased and the
+biased form (the unbiased count plus, per stored entry and per side that gathers, 4 bytes of position and 4
+of bias, and 4 for GBias), and the largest difference of every result between bias and composed.
 """
 import argparse
 import json
@@ -112,6 +127,7 @@ def main():
     ap.add_argument("--forward", default="gather", choices=["gather", "panels"])
     ap.add_argument("--backward", default="gather", choices=["gather", "panels"])
     ap.add_argument("--kv8", action="store_true")
+    ap.add_argument("--bias", action="store_true")
     ap.add_argument("--layout", default="bmhd", choices=["bmhd", "bhmd"])
     ap.add_argument("--baseline-only", action="store_true")
     ap.add_argument("--order-probe", action="store_true")
@@ -123,6 +139,8 @@ def main():
         raise SystemExit("--kv8 goes with --forward panels and --d 64, 128 or 256")
     if args.backward == "panels" and (args.dtype == "f32" or args.d not in (32, 64, 128)):
         raise SystemExit("--backward panels takes --dtype f16 or bf16 and --d 32, 64 or 128")
+    if args.bias and ("panels" not in (args.forward, args.backward) or args.kv8 or args.d not in (32, 64, 128)):
+        raise SystemExit("--bias goes with --forward panels or --backward panels and --d 32, 64 or 128")
     if "panels" not in (args.forward, args.backward) and args.dtype == "bf16":
         raise SystemExit("--dtype bf16 is for --forward panels and --backward panels only")
     if args.package:
@@ -175,6 +193,9 @@ def main():
 
     D = args.d
     scale = D ** -0.5
+    if args.bias:
+        bias_bench(args, torch, dev, graph_of, alternate)
+        return
     if args.backward == "panels":
         panels_bwd_bench(args, torch, dev, graph_of, alternate)
         return
@@ -438,6 +459,93 @@ def panels_bwd_bench(args, torch, dev, graph_of, alternate):
                 "panels_over_gather": round(graph_us["panels"] / graph_us["gather"], 3), "floor_us": round(floor, 3),
                 "floor_fraction": round(floor / graph_us["panels"], 3),
                 "max_abs_diff": {n: (a - b).abs().max().item() for n, a, b in zip(("GQ", "GK", "GV"), out["panels"], out["gather"])}}
+        print(json.dumps(line), flush=True)
+
+
+def bias_bench(args, torch, dev, graph_of, alternate):
+    """The --bias mode of --forward panels and --backward panels (module docstring)."""
+    from bsmr import BF16, F16, Plan, make_data, synth
+
+    D, back = args.d, args.backward == "panels"
+    scale = D ** -0.5
+    tdt, dtype = (torch.bfloat16, BF16) if args.dtype == "bf16" else (torch.float16, F16)
+    p = lambda t: t.data_ptr()  # noqa: E731
+    patterns = {"C2": synth.nips_like, "C3": synth.cop20k_like, "C5": lambda: synth.dlmc_like("block")}
+    for case in args.cases.split(","):
+        if case not in patterns:
+            raise SystemExit(f"unknown case {case}")
+        M, N, rp, ci = patterns[case]()
+        nnz = len(ci)
+        plan = Plan(M, N, rp, ci, alpha=0.3, delta=0.3)
+        plan.prepare(D, dtype)
+        plan.prepare_spmm(D, 3)
+        plan.prepare_softmax()
+        plan.prepare_attention_panels(D, D)
+        plan.prepare_attention_panels_bias(D, D)
+        if back:
+            plan.prepare_attention_backward_panels(D, D)
+            plan.prepare_attention_panels_bias(D, D, backward=True)
+        data = lambda n: torch.from_numpy(make_data(n)).to(dev) - 1.0  # noqa: E731
+        Q, K, V, GO = (data(r * D).reshape(r, D) for r in (M, N, N, M))
+        GOh = GO.to(tdt)  # the composed chain's SDDMM and SpMM take both operands in the operand type
+        Q, K, V = Q.to(tdt), K.to(tdt), V.to(tdt)
+        bias = 2.0 * data(nnz)
+        z = lambda *shape: torch.zeros(shape, device=dev)  # noqa: E731
+        P, X, W, gW, gX, gP = (z(nnz) for _ in range(6))
+        forms = ("panels", "bias", "composed")
+        O, L = {k: z(M, D) for k in forms}, {k: z(M) for k in forms}
+
+        def composed_fwd(s):
+            plan.sddmm(p(Q), p(K), D, p(P), stream=s, dtype=dtype)
+            torch.add(bias, P, alpha=scale, out=X)
+            plan.softmax(p(X), p(W), 1.0, stream=s)
+            plan.spmm(p(W), p(V), D, p(O["composed"]), stream=s, dtype=dtype)
+
+        fwd = {"panels": lambda s: plan.attention_panels(p(Q), p(K), p(V), D, D, p(O["panels"]), p(L["panels"]), scale,
+                                                         stream=s, dtype=dtype),
+               "bias": lambda s: plan.attention_panels_bias(p(Q), p(K), p(V), p(bias), D, D, p(O["bias"]), p(L["bias"]), scale,
+                                                            stream=s, dtype=dtype),
+               "composed": composed_fwd}
+        if back:  # one forward of every form leaves its O and LSE, and the composed chain's W
+            for f in fwd.values():
+                f(torch.cuda.current_stream().cuda_stream)
+            torch.cuda.synchronize()
+        else:
+            graphs = {k: graph_of(f) for k, f in fwd.items()}
+        st = plan.attention_panels_stats()
+        floor = 2 * D * M + 4 * D * M + 4 * M + st["steps"] * (192 + 2 * 2 * D * 32)
+        extra, diff = 8 * nnz, {"O": (O["bias"] - O["composed"]).abs().max().item()}
+        if back:
+            G = {k: [z(r, D) for r in (M, N, N)] + [z(nnz)] for k in forms}
+
+            def composed_bwd(s):
+                plan.sddmm(p(GOh), p(V), D, p(gW), stream=s, dtype=dtype)
+                plan.spmm_t(p(W), p(GOh), D, p(G["composed"][2]), stream=s, dtype=dtype)
+                plan.softmax_backward(p(W), p(gW), p(G["composed"][3]), 1.0, stream=s)
+                torch.mul(G["composed"][3], scale, out=gP)
+                plan.spmm(p(gP), p(K), D, p(G["composed"][0]), stream=s, dtype=dtype)
+                plan.spmm_t(p(gP), p(Q), D, p(G["composed"][1]), stream=s, dtype=dtype)
+
+            bwd = {"panels": lambda s: plan.attention_backward_panels(p(Q), p(K), p(V), p(O["panels"]), p(GO), p(L["panels"]), D, D,
+                                                                      *(p(t) for t in G["panels"][:3]), scale, stream=s, dtype=dtype),
+                   "bias": lambda s: plan.attention_backward_panels_bias(p(Q), p(K), p(V), p(bias), p(O["bias"]), p(GO), p(L["bias"]),
+                                                                         D, D, *(p(t) for t in G["bias"]), scale, stream=s,
+                                                                         dtype=dtype),
+                   "composed": composed_bwd}
+            graphs = {k: graph_of(f) for k, f in bwd.items()}
+            st = plan.attention_backward_panels_stats()
+            rows_side = 2 * D * M + 4 * D * M + 8 * M + 4 * D * M + st["row_steps"] * (192 + 2 * 2 * D * 32)
+            cols_side = 2 * 2 * D * N + 2 * 4 * D * N + st["col_steps"] * (192 + (2 * D + 4 * D + 8) * 32)
+            floor, extra = 8 * D * M + 4 * M + rows_side + cols_side, (8 + 8 + 4) * nnz
+            diff = {n: (a - b).abs().max().item() for n, a, b in zip(("GQ", "GK", "GV", "GBias"), G["bias"], G["composed"])}
+        graph_us = alternate({k: g.replay for k, g in graphs.items()})
+        us = lambda b: round(b / HBM_BYTES_PER_S * 1e6, 3)  # noqa: E731
+        line = {"case": case, "mode": "backward_panels_bias" if back else "panels_bias", "M": M, "N": N, "nnz": nnz, "D": D,
+                "dtype": args.dtype, "steps": args.steps, "rounds": args.rounds, "stats": st, "graph_us": graph_us,
+                "bias_over_panels": round(graph_us["bias"] / graph_us["panels"], 3),
+                "bias_over_composed": round(graph_us["bias"] / graph_us["composed"], 3),
+                "floor_us": {"panels": us(floor), "bias": us(floor + extra)},
+                "floor_fraction": round(us(floor + extra) / graph_us["bias"], 3), "max_abs_diff_vs_composed": diff}
         print(json.dumps(line), flush=True)
 
 

@@ -60,7 +60,9 @@ extern "C" {
                               prepared / stats calls and bsmr_attention_pattern_transpose (the panel
                               MFMA backward: new declarations only); bsmr_attention_panels_kv8, its
                               heads form and the bsmr_kv_dtype enum: the panel MFMA forward over e4m3 K / V,
-                              new declarations only; bsmr_spmm_panels, bsmr_spmm_t_panels,
+                              new declarations only; bsmr_attention_panels_kv4 and its heads form
+                              (the same over an MXFP4 K / V cache: new declarations only);
+                              bsmr_spmm_panels, bsmr_spmm_t_panels,
                               bsmr_plan_prepare_spmm_panels, bsmr_plan_spmm_panels_prepared,
                               bsmr_plan_spmm_panels_stats and bsmr_spmm_panel_positions (the panel
                               MFMA SpMM, the SDDMM gradients: new declarations only);
@@ -869,6 +871,49 @@ int bsmr_attention_panels_kv8_heads(const bsmr_plan* plan, uint32_t batches, uin
                                     const bsmr_attention_operand* V8, uint32_t D, uint32_t Dv, int dtype, int kv_dtype,
                                     float scale, float k_scale, float v_scale, const bsmr_attention_operand* O,
                                     float* dLse, void* stream);
+
+/* ------------------------------ the panel forward over an MXFP4 K / V cache ---- */
+/* bsmr_attention_panels_kv8 for a K / V cache in the OCP microscaling fp4 format (DESIGN.md §25;
+ * forward only): 4-bit e2m1 elements (values 0, 0.5, 1, 1.5, 2, 3, 4, 6 and their negatives) with
+ * one e8m0 scale byte per block of 32 consecutive elements of a row, and one positive finite float
+ * scale per tensor on top, as in kv8:
+ *   O = v_scale softmax_row(scale k_scale S .* (Q K4^T)) V4,  LSE of that softmax.
+ * A row of width W (D for K4, Dv for V4) is one record of R(W) = round_up(W / 2 + W / 32, 16)
+ * bytes, R(128) = 80 and R(256) = 144, so that a gathered row is one contiguous fetch:
+ *   bytes [0, W / 2)               the elements: element 2 c in the low nibble of byte c, element
+ *                                  2 c + 1 in the high nibble (torch.float4_e2m1fn_x2's order);
+ *   bytes [W / 2, W / 2 + W / 32)  scale byte b scales the elements [32 b, 32 b + 32);
+ *   the rest                       zero padding.
+ * dK4 is N records of R(D) bytes and dV4 N records of R(Dv) bytes. An element's value is
+ * fl_dtype(e2m1 x 2^(s - 127)) with `dtype` Q's: what gfx950's packed fp4 convert gives.
+ *   s = 0xFF    NaN: the whole block is NaN;
+ *   s = 0       2^-127, e8m0's smallest scale and nothing else: no "zero block" meaning. It lies
+ *               outside the exact range below (BSMR_F16: every element a signed zero; BSMR_BF16:
+ *               subnormals of bf16). A block of zeros is written with zero nibbles and any scale;
+ *   exactness   the widening is exact, and the result that of bsmr_attention_panels on the widened
+ *               tensors within §25's bounds, only where e2m1 x 2^(s - 127) is a normal number of
+ *               `dtype` for every e2m1 value: s - 127 in -13 .. 13 for BSMR_F16, -125 .. 125 for
+ *               BSMR_BF16. Outside it the value follows the instruction's rounding (overflow to
+ *               inf, denormal results) and nothing is promised. k_scale and v_scale exist so that
+ *               a quantiser can keep the block exponents near zero.
+ * D and Dv are each one of 128, 256. 32 and 64 are BSMR_ERR_UNSUPPORTED, like BSMR_F32: at 64 a
+ * record would be 48 bytes against 64 of e4m3, and a V row has too few 32-bit words for the
+ * kernel's read mapping (one word per lane of a 16-lane group).
+ * Everything else is bsmr_attention_panels_kv8's: the scale rules (BSMR_ERR_INVALID), the pointer
+ * rules (dK4 and dV4 16-byte aligned), the plan state (bsmr_plan_prepare_attention_panels(_heads)
+ * prepares this call too; BSMR_ERR_NOT_PREPARED on a capturing stream otherwise), untouched outputs
+ * on every error. NaN: a 0xFF scale byte of a K record reaches exactly the rows that store the
+ * column; one of a V record the rows of the panels whose column union holds the column. */
+int bsmr_attention_panels_kv4(const bsmr_plan* plan, const void* dQ, const void* dK4, const void* dV4, uint32_t D,
+                              uint32_t Dv, int dtype, float scale, float k_scale, float v_scale, float* dO, float* dLse,
+                              void* stream);
+/* The same over batches x heads slices in one call: K4 and V4 follow the layout rules as operands of
+ * one-byte elements, R(D) and R(Dv) wide; every slice equals the single-slice call bit for bit. */
+int bsmr_attention_panels_kv4_heads(const bsmr_plan* plan, uint32_t batches, uint32_t heads,
+                                    const bsmr_attention_operand* Q, const bsmr_attention_operand* K4,
+                                    const bsmr_attention_operand* V4, uint32_t D, uint32_t Dv, int dtype, float scale,
+                                    float k_scale, float v_scale, const bsmr_attention_operand* O, float* dLse,
+                                    void* stream);
 
 /* -------------------- fused sparse attention backward on matrix instructions, per panel ---- */
 /* The gradients of bsmr_attention_backward, for fp16 / bf16 operands, on

@@ -248,6 +248,13 @@ SOFTMAX_WAVE = 0x100
 SOFTMAX_BLOCK = 0x200
 
 ABI_VERSION = 13  # include/bsmr.h BSMR_ABI_VERSION
+
+
+def mx4_record_bytes(width):
+    """R(W): the bytes of one MXFP4 row of `width` elements (include/bsmr.h, bsmr_attention_panels_kv4)."""
+    return (width // 2 + width // 32 + 15) // 16 * 16
+
+
 KV_F8_E4M3 = 0  # bsmr_kv_dtype: the K / V format of Plan.attention_panels_kv8
 
 # every symbol include/bsmr.h declares (tests check the library exports all of them)
@@ -288,6 +295,7 @@ EXPORTS = [
     "bsmr_plan_attention_backward_panels_prepared", "bsmr_plan_attention_backward_panels_heads_prepared",
     "bsmr_plan_attention_backward_panels_stats", "bsmr_attention_pattern_transpose",
     "bsmr_attention_panels_kv8", "bsmr_attention_panels_kv8_heads",
+    "bsmr_attention_panels_kv4", "bsmr_attention_panels_kv4_heads",
     "bsmr_spmm_panels", "bsmr_spmm_t_panels", "bsmr_plan_prepare_spmm_panels", "bsmr_plan_spmm_panels_prepared",
     "bsmr_plan_spmm_panels_stats", "bsmr_spmm_panel_positions",
     "bsmr_sddmm_mfma", "bsmr_plan_prepare_sddmm_mfma", "bsmr_plan_sddmm_mfma_prepared", "bsmr_plan_sddmm_mfma_stats",
@@ -458,6 +466,12 @@ def lib():
     L.bsmr_attention_panels_kv8_heads.argtypes = [vp, C.c_uint32, C.c_uint32, op, op, op, C.c_uint32, C.c_uint32, C.c_int,
                                                   C.c_int, C.c_float, C.c_float, C.c_float, op, vp, vp]
     L.bsmr_attention_panels_kv8_heads.restype = C.c_int
+    L.bsmr_attention_panels_kv4.argtypes = [vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_int, C.c_float, C.c_float, C.c_float,
+                                            vp, vp, vp]
+    L.bsmr_attention_panels_kv4.restype = C.c_int
+    L.bsmr_attention_panels_kv4_heads.argtypes = [vp, C.c_uint32, C.c_uint32, op, op, op, C.c_uint32, C.c_uint32, C.c_int,
+                                                  C.c_float, C.c_float, C.c_float, op, vp, vp]
+    L.bsmr_attention_panels_kv4_heads.restype = C.c_int
     u64p = C.POINTER(C.c_uint64)
     L.bsmr_attention_panel_lists.argtypes = [C.c_uint32, C.c_uint32, vp, vp, vp, C.c_uint32, vp, vp, u64p, vp, u64p, vp, u64p]
     L.bsmr_attention_panel_lists.restype = C.c_int
@@ -972,6 +986,27 @@ class Plan:
         _check(lib().bsmr_attention_panels_kv8_heads(self.h, batches, heads, ref[0], ref[1], ref[2], D, Dv, dtype,
                                                      KV_F8_E4M3, scale, k_scale, v_scale, ref[3], dLse or None,
                                                      stream or None), "bsmr_attention_panels_kv8_heads")
+
+    def attention_panels_kv4(self, dQ, dK4, dV4, D, Dv, dO, dLse=0, scale=1.0, k_scale=1.0, v_scale=1.0, stream=0,
+                             dtype=F16):
+        """bsmr_attention_panels_kv4: attention_panels over an MXFP4 K / V cache. dQ (M x D) fp16 / bf16;
+        dK4 and dV4 N records of mx4_record_bytes(D) / (Dv) bytes each: e2m1 nibbles, then one e8m0
+        scale byte per 32 elements (bsmr.autograd.quantize_kv_mx4 writes them), with one float scale
+        per tensor on top: O = v_scale softmax(scale k_scale S .* (Q K4^T)) V4. D, Dv in {128, 256};
+        forward only; prepare_attention_panels prepares it."""
+        _check(lib().bsmr_attention_panels_kv4(self.h, dQ, dK4, dV4, D, Dv, dtype, scale, k_scale, v_scale, dO,
+                                               dLse or None, stream or None), "bsmr_attention_panels_kv4")
+
+    def attention_panels_kv4_heads(self, batches, heads, Q, K4, V4, D, Dv, O, dLse=0, scale=1.0, k_scale=1.0, v_scale=1.0,
+                                   stream=0, dtype=F16):
+        """bsmr_attention_panels_kv4_heads: attention_panels_kv4 over batches x heads slices in one
+        call; K4 and V4 are uint8 operands whose rows are records, one k_scale and one v_scale for
+        all slices."""
+        ops = [AttentionOperand.of(x) for x in (Q, K4, V4, O)]
+        ref = [None if o is None else C.byref(o) for o in ops]
+        _check(lib().bsmr_attention_panels_kv4_heads(self.h, batches, heads, ref[0], ref[1], ref[2], D, Dv, dtype, scale,
+                                                     k_scale, v_scale, ref[3], dLse or None, stream or None),
+               "bsmr_attention_panels_kv4_heads")
 
     def prepare_attention_panels(self, D, Dv):
         """bsmr_plan_prepare_attention_panels: the panel lists and the scratch of the split panels

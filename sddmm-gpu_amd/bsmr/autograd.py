@@ -20,13 +20,17 @@ and, over the same plan, the row softmax, the SpMM and their composition into sp
     quantize_kv(K, V)                (K8, V8, k_scale, v_scale): per-tensor e4m3 quantisation (torch ops)
     attention_fused_kv8(plan, Q, K8, V8, k_scale, v_scale)   the panel forward over that fp8 cache
                                      (Plan.attention_panels_kv8_heads); inference only, no backward
+    quantize_kv_mx4(K, V)            (K4, V4, k_scale, v_scale): MXFP4 records, e2m1 elements with one e8m0
+                                     scale per 32 (torch ops); dequantize_mx4(X4, W, dtype) is their values
+    attention_fused_kv4(plan, Q, K4, V4, k_scale, v_scale)   the panel forward over that fp4 cache
+                                     (Plan.attention_panels_kv4_heads); inference only, no backward
 
 Every direction is the library's HIP kernels on torch.cuda.current_stream(); torch only owns the
 tensors. Importing this module imports torch (`import bsmr` alone does not).
 """
 import torch
 
-from . import BF16, F16, F32, attention_heads_limits, attention_layout_check, attention_limits
+from . import BF16, F16, F32, attention_heads_limits, attention_layout_check, attention_limits, mx4_record_bytes
 
 _DTYPES = {torch.float32: F32, torch.float16: F16, torch.bfloat16: BF16}
 _PANEL_K = (32, 64, 128, 256, 512, 1024)  # include/bsmr.h, bsmr_spmm_panels
@@ -691,33 +695,44 @@ def attention_fused_kv8(plan, Q, K8, V8, k_scale, v_scale, scale=None, return_ls
     widened tensors to train). ValueError, before any launch, also for K8 / V8 of another dtype, a Q
     that is not float16 / bfloat16, wrong shapes, scales that are not finite and > 0 or a layout the
     library refuses."""
-    who = "attention_fused_kv8"
-    for name, X in (("Q", Q), ("K8", K8), ("V8", V8)):
+    return _fused_quantised("attention_fused_kv8", plan, Q, K8, V8, k_scale, v_scale, scale, return_lse, ("K8", "V8"),
+                            torch.float8_e4m3fn, (64, 128, 256), lambda W: W, plan.attention_panels_kv8_heads)
+
+
+def _fused_quantised(who, plan, Q, Kq, Vq, k_scale, v_scale, scale, return_lse, names, kv_dtype, dims, stored, launch):
+    """attention_fused_kv8 / attention_fused_kv4: Kq and Vq (called names[0] and names[1]) of
+    kv_dtype, a row of W elements stored as stored(W) of them, D and Dv each one of dims; launch is
+    the Plan's heads call."""
+    kn, vn = names
+    for name, X in (("Q", Q), (kn, Kq), (vn, Vq)):
         if not isinstance(X, torch.Tensor) or not X.is_cuda:
             raise ValueError(f"{who}: {name} must be a device tensor")
     if Q.dtype not in (torch.float16, torch.bfloat16):
         raise ValueError(f"{who}: Q must be float16 or bfloat16, got {Q.dtype}")
-    if K8.dtype != torch.float8_e4m3fn or V8.dtype != torch.float8_e4m3fn:
-        raise ValueError(f"{who}: K8 and V8 must be torch.float8_e4m3fn, got {K8.dtype} and {V8.dtype}")
+    if Kq.dtype != kv_dtype or Vq.dtype != kv_dtype:
+        raise ValueError(f"{who}: {kn} and {vn} must be {kv_dtype}, got {Kq.dtype} and {Vq.dtype}")
     if torch.is_grad_enabled() and Q.requires_grad:
         raise ValueError(f"{who}: Q requires grad, but this path has no backward (inference only): call it under "
                          "torch.no_grad() or detach Q")
-    if Q.dim() not in (2, 3, 4) or not (Q.dim() == K8.dim() == V8.dim()):
-        raise ValueError(f"{who}: Q, K8 and V8 must all be (rows, W), (H, rows, W) or (B, H, rows, W)")
+    if Q.dim() not in (2, 3, 4) or not (Q.dim() == Kq.dim() == Vq.dim()):
+        raise ValueError(f"{who}: Q, {kn} and {vn} must all be (rows, W), (H, rows, W) or (B, H, rows, W)")
     flat = Q.dim() == 2
     if flat:
-        Q, K8, V8 = Q.unsqueeze(0), K8.unsqueeze(0), V8.unsqueeze(0)
-    lead, D, Dv = tuple(Q.shape[:-2]), Q.shape[-1], V8.shape[-1]
-    for name, X, rows, W in (("Q", Q, plan.M, D), ("K8", K8, plan.N, D), ("V8", V8, plan.N, Dv)):
+        Q, Kq, Vq = Q.unsqueeze(0), Kq.unsqueeze(0), Vq.unsqueeze(0)
+    lead, D = tuple(Q.shape[:-2]), Q.shape[-1]
+    Dv = next((W for W in dims if stored(W) == Vq.shape[-1]), None)
+    if D not in dims or Dv is None:
+        raise ValueError(f"{who}: D = {D} and Dv (a {vn} row of {Vq.shape[-1]}) must each be one of "
+                         f"{', '.join(map(str, dims))}")
+    operands = (("Q", Q, plan.M, D), (kn, Kq, plan.N, stored(D)), (vn, Vq, plan.N, stored(Dv)))
+    for name, X, rows, W in operands:
         if tuple(X.shape) != lead + (rows, W):
             raise ValueError(f"{who}: {name} must be {lead + (rows, W)}, got {tuple(X.shape)}")
-    if D not in (64, 128, 256) or Dv not in (64, 128, 256):
-        raise ValueError(f"{who}: D = {D} and Dv = {Dv} must each be one of 64, 128, 256")
     lim = attention_heads_limits()
     B, H = (1,) * (2 - len(lead)) + lead
     if not (1 <= B <= lim["max_batches"] and 1 <= H <= lim["max_heads"]):
         raise ValueError(f"{who}: batch = {B} and heads = {H} must be 1 .. {lim['max_batches']} and 1 .. {lim['max_heads']}")
-    for name, X, rows, W in (("Q", Q, plan.M, D), ("K8", K8, plan.N, D), ("V8", V8, plan.N, Dv)):
+    for name, X, rows, W in operands:
         if X.stride(-1) != 1 or min(X.stride()) < 0:
             raise ValueError(f"{who}: {name} must have a contiguous last dimension, got strides {tuple(X.stride())}")
         bad = attention_layout_check(X, B, H, rows, W, X.element_size(), False)
@@ -727,8 +742,67 @@ def attention_fused_kv8(plan, Q, K8, V8, k_scale, v_scale, scale=None, return_ls
     k_scale, v_scale = _valid_scale(who, k_scale), _valid_scale(who, v_scale)
     O = _dense_like(Q, lead + (plan.M, Dv))
     lse = torch.empty(lead + (plan.M,), dtype=torch.float32, device=Q.device)
-    plan.attention_panels_kv8_heads(B, H, Q.detach(), K8, V8, D, Dv, O, lse.data_ptr(), scale, k_scale, v_scale,
-                                    stream=_stream(), dtype=_DTYPES[Q.dtype])
+    launch(B, H, Q.detach(), Kq, Vq, D, Dv, O, lse.data_ptr(), scale, k_scale, v_scale, stream=_stream(),
+           dtype=_DTYPES[Q.dtype])
     if flat:
         O, lse = O[0], lse[0]
     return (O, lse) if return_lse else O
+
+
+E2M1_MAX = 6.0  # the largest e2m1 value; the grid is 0, 0.5, 1, 1.5, 2, 3, 4, 6 and the negatives
+_MX_BLOCK = 32
+
+
+def quantize_kv_mx4(K, V):
+    """(K4, V4, k_scale, v_scale): K and V as MXFP4 records (include/bsmr.h, bsmr_attention_panels_kv4):
+    uint8 tensors of shape (..., rows, mx4_record_bytes(W)), W = 128 or 256, with one scale per tensor
+    on top, scale = amax / 6 (1.0 for a tensor of zeros), so that X is about dequantize_mx4(X4) * scale.
+    Per block of 32 elements of X / scale the exponent is floor(log2(block amax)) - 2, one more where
+    the block's largest element would pass 6, clamped to [-12, 0]: the largest element of a block lands
+    in (3, 6], float16's exact range is never left, and a block too small for exponent -12 rounds
+    towards zero on that grid. Elements are rounded to the nearest e2m1 value, ties to the even
+    mantissa. Torch ops only: CPU and device tensors alike."""
+    out = []
+    for X in (K, V):
+        W = X.shape[-1]
+        if W % _MX_BLOCK:
+            raise ValueError(f"quantize_kv_mx4: the last dimension {W} must be a multiple of {_MX_BLOCK}")
+        amax = X.detach().abs().max().float() if X.numel() else torch.zeros(())
+        s = float(amax / E2M1_MAX) if float(amax) > 0.0 else 1.0
+        Y = (X.detach().float() / s).reshape(X.shape[:-1] + (W // _MX_BLOCK, _MX_BLOCK))
+        bmax = Y.abs().amax(-1, keepdim=True)
+        e = torch.frexp(bmax).exponent - 3  # floor(log2(bmax)) - 2: bmax / 2^e in [4, 8)
+        e = torch.where(bmax > torch.ldexp(torch.full_like(bmax, E2M1_MAX), e), e + 1, e).clamp(-12, 0)
+        z = torch.ldexp(Y.abs(), -e)  # exact
+        code = torch.where(z < 2, (2 * z).round(), torch.where(z < 4, z.round() + 2, (z / 2).round() + 4)).clamp(max=7)
+        nib = (code.to(torch.uint8) | ((Y < 0).to(torch.uint8) << 3)).reshape(X.shape[:-1] + (W // 2, 2))
+        rec = torch.zeros(X.shape[:-1] + (mx4_record_bytes(W),), dtype=torch.uint8, device=X.device)
+        rec[..., :W // 2] = nib[..., 0] | (nib[..., 1] << 4)
+        rec[..., W // 2:W // 2 + W // _MX_BLOCK] = (e.squeeze(-1) + 127).to(torch.uint8)
+        out.append((rec, s))
+    return out[0][0], out[1][0], out[0][1], out[1][1]
+
+
+def dequantize_mx4(X4, W, dtype):
+    """The values of MXFP4 records X4 (..., rows, mx4_record_bytes(W)) as a (..., rows, W) tensor of
+    `dtype`: fl_dtype(e2m1 2^(s - 127)) per element, NaN for a block whose scale byte is 0xFF; what
+    the kernel's convert makes of a record inside its exact range, without the per-tensor scale."""
+    if X4.dtype != torch.uint8 or X4.shape[-1] != mx4_record_bytes(W):
+        raise ValueError(f"dequantize_mx4: X4 must be uint8 with a last dimension of {mx4_record_bytes(W)}")
+    grid = torch.tensor([0, 0.5, 1, 1.5, 2, 3, 4, 6], dtype=torch.float64, device=X4.device)
+    b = X4[..., :W // 2]
+    nib = torch.stack((b & 15, b >> 4), -1).reshape(X4.shape[:-1] + (W // _MX_BLOCK, _MX_BLOCK)).long()
+    s = X4[..., W // 2:W // 2 + W // _MX_BLOCK].to(torch.int32).unsqueeze(-1)
+    v = torch.ldexp(torch.where(nib >= 8, -grid[nib & 7], grid[nib & 7]), s - 127)
+    v = torch.where(s == 255, torch.full_like(v, float("nan")), v)
+    return v.reshape(X4.shape[:-1] + (W,)).to(dtype)
+
+
+def attention_fused_kv4(plan, Q, K4, V4, k_scale, v_scale, scale=None, return_lse=False):
+    """attention_fused_kv8 over an MXFP4 cache: O = v_scale softmax(scale k_scale S .* (Q K4^T)) V4 in
+    float32 from one Plan.attention_panels_kv4_heads call, and with return_lse=True also LSE. K4 and V4
+    are torch.uint8 records (quantize_kv_mx4 makes them) with N rows, a last dimension of
+    mx4_record_bytes(D) / mx4_record_bytes(Dv) and Q's leading dimensions; D and Dv in {128, 256}.
+    Inference only, strided views and ValueError before any launch as in attention_fused_kv8."""
+    return _fused_quantised("attention_fused_kv4", plan, Q, K4, V4, k_scale, v_scale, scale, return_lse, ("K4", "V4"),
+                            torch.uint8, (128, 256), mx4_record_bytes, plan.attention_panels_kv4_heads)

@@ -1,6 +1,7 @@
 // attention_panels_args.hpp — what the forms of the panel attention forward share: the kernels'
 // argument record, the softmax conventions and the one launch routine (attention_panels.hip, the
-// 16-bit K / V form and the reduce; attention_panels_kv8.hip, the e4m3 K / V form).
+// 16-bit K / V form and the reduce; attention_panels_kv8.hip, the e4m3 K / V form;
+// attention_panels_kv4.hip, the MXFP4 K / V form).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -62,6 +63,25 @@ int attn_panels_launch(const char* who, const char* prep, const bsmr_plan* plan,
                        const bsmr_attention_operand& Q, const bsmr_attention_operand& K, const bsmr_attention_operand& V,
                        u32 kvBytes, u32 D, u32 Dv, int dtype, float scale, float c, float vscale,
                        const bsmr_attention_operand& O, float* dLse, void* stream, const PanelBiasIn* bias = nullptr);
+
+// The scale rules of the quantised K / V forms (kv8, kv4). INVALID: a k_scale or v_scale that is not
+// finite and > 0, or an effective score scale scale k_scale (the exact double product of the two
+// floats) that attn_validate_scale's rule refuses. *eff is that product rounded once to float and *c
+// its product with log2(e), rounded once from double
+inline int attn_panels_kv_scales(const char* who, float scale, float k_scale, float v_scale, float* eff, float* c) {
+    if (!(k_scale > 0.f) || !std::isfinite(k_scale) || !(v_scale > 0.f) || !std::isfinite(v_scale)) {
+        set_error(std::string(who) + ": k_scale and v_scale must be finite and > 0");
+        return BSMR_ERR_INVALID;
+    }
+    const double e = static_cast<double>(scale) * static_cast<double>(k_scale);
+    *eff = static_cast<float>(e);
+    *c = static_cast<float>(e * 1.4426950408889634);
+    if (!(scale > 0.f) || !std::isfinite(scale) || !(*eff > 0.f) || !std::isfinite(*eff) || !std::isfinite(*c)) {
+        set_error(std::string(who) + ": scale and scale * k_scale must be finite and > 0 (and scale * k_scale * log2(e) finite)");
+        return BSMR_ERR_INVALID;
+    }
+    return BSMR_OK;
+}
 
 // the biased form's checks of dBias and its stride, and its kernel for (D, Dv, dtype): null where the
 // form is not built. Defined in attention_panels_bias.hip

@@ -254,10 +254,7 @@ PanelFn pick_d(u32 D, u32 Dv) {
 }
 
 // The argument rules the two entry points share. UNSUPPORTED: a Q dtype other than fp16 / bf16, D or
-// Dv outside the built forms, another K / V format. INVALID: a k_scale or v_scale that is not finite
-// and > 0, or an effective score scale scale k_scale (the exact double product of the two floats)
-// that attn_validate_scale's rule refuses. *eff is that product rounded once to float and *c its
-// product with log2(e), rounded once from double
+// Dv outside the built forms, another K / V format. The scales, *eff and *c: attn_panels_kv_scales
 int kv8_validate(const char* who, u32 D, u32 Dv, int dtype, int kv_dtype, float scale, float k_scale, float v_scale,
                  float* eff, float* c, PanelFn* fn) {
     *fn = dtype == BSMR_F16 ? pick_d<BSMR_F16>(D, Dv) : dtype == BSMR_BF16 ? pick_d<BSMR_BF16>(D, Dv) : nullptr;
@@ -266,18 +263,7 @@ int kv8_validate(const char* who, u32 D, u32 Dv, int dtype, int kv_dtype, float 
                                      "BSMR_KV_F8_E4M3");
         return BSMR_ERR_UNSUPPORTED;
     }
-    if (!(k_scale > 0.f) || !std::isfinite(k_scale) || !(v_scale > 0.f) || !std::isfinite(v_scale)) {
-        set_error(std::string(who) + ": k_scale and v_scale must be finite and > 0");
-        return BSMR_ERR_INVALID;
-    }
-    const double e = static_cast<double>(scale) * static_cast<double>(k_scale);
-    *eff = static_cast<float>(e);
-    *c = static_cast<float>(e * 1.4426950408889634);
-    if (!(scale > 0.f) || !std::isfinite(scale) || !(*eff > 0.f) || !std::isfinite(*eff) || !std::isfinite(*c)) {
-        set_error(std::string(who) + ": scale and scale * k_scale must be finite and > 0 (and scale * k_scale * log2(e) finite)");
-        return BSMR_ERR_INVALID;
-    }
-    return BSMR_OK;
+    return attn_panels_kv_scales(who, scale, k_scale, v_scale, eff, c);
 }
 
 }  // namespace

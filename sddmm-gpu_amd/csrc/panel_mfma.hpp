@@ -1,6 +1,6 @@
 // panel_mfma.hpp — what the panel kernels share on the device (attention_panels.hip, the attention
-// forward; attention_panels_kv8.hip, its e4m3 K / V form; attention_bwd_panels.hip, the backward's
-// rows and columns kernels; spmm_panels.hip, the SpMM of the SDDMM gradients), and the one place
+// forward; attention_panels_kv8.hip and attention_panels_kv4.hip, its e4m3 and MXFP4 K / V forms;
+// attention_bwd_panels.hip, the backward's rows and columns kernels; spmm_panels.hip, the SpMM of the SDDMM gradients), and the one place
 // that states their lane mapping, k-slot order and stage layout.
 //
 // Lane mapping. A wave takes an item: up to PANEL_ITEM_STEPS steps of 32 sources (columns; union
@@ -92,6 +92,29 @@ __device__ __forceinline__ u32 widen2(u32 w) {
 template <int DT>
 __device__ __forceinline__ uint4 widen8(u32 lo, u32 hi) {
     return make_uint4(widen2<DT, false>(lo), widen2<DT, true>(lo), widen2<DT, false>(hi), widen2<DT, true>(hi));
+}
+
+// An e8m0 scale byte s as the float the fp4 convert takes: bits s << 23, that is 2^(s - 127) for
+// s = 1 .. 254, +inf for 0xFF (the convert reads the exponent field alone and makes the block NaN)
+// and +0 for 0 (read as 2^-127)
+__device__ __forceinline__ float mx_scale(u32 s) { return __builtin_bit_cast(float, s << 23); }
+
+// Byte SEL of w, two e2m1 nibbles, times `scale` (mx_scale) widened to the operand type by gfx950's
+// packed convert: the low nibble lands in the low half. Exact where nibble x scale is a normal
+// number of the type (fp16: block exponents -13 .. 13 for every nibble; bf16: -125 .. 125)
+template <int DT, int SEL>
+__device__ __forceinline__ u32 widen2_fp4(u32 w, float scale) {
+    if constexpr (DT == BSMR_F16)
+        return __builtin_bit_cast(u32, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, scale, SEL));
+    else
+        return __builtin_bit_cast(u32, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, SEL));
+}
+
+// a word of eight e2m1 nibbles of one block as an operand of mfma32, in element order
+template <int DT>
+__device__ __forceinline__ uint4 widen8_fp4(u32 w, float scale) {
+    return make_uint4(widen2_fp4<DT, 0>(w, scale), widen2_fp4<DT, 1>(w, scale), widen2_fp4<DT, 2>(w, scale),
+                      widen2_fp4<DT, 3>(w, scale));
 }
 
 __device__ __forceinline__ uint4 load16(const char* p) { return *reinterpret_cast<const uint4*>(p); }

@@ -88,6 +88,15 @@ V quantised by bsmr.autograd.quantize_kv and widened again (scale x k_scale as i
 same protocol. Per case: graph_us of both, kv8_over_panels16, floor_us of both with section 18's
 count (one byte per K / V element for kv8) and the largest |O_kv8 - v_scale O_panels16|.
 
+    python3 tools/attention_bench.py --forward panels --kv4 [--cases C2,C5,C3] [--dtype f16|bf16] [--d 128|256]
+
+With --forward panels --kv4 the run times three forwards on one plan and the same Q by the same
+protocol: Plan.attention_panels_kv4 on K and V as MXFP4 records (bsmr.autograd.quantize_kv_mx4,
+DESIGN.md section 25), Plan.attention_panels_kv8 on their e4m3 quantisation and Plan.attention_panels
+on the 16-bit K and V. Per case: graph_us of the three, kv4_over_kv8, kv4_over_panels16, floor_us of
+each with section 18's count (a K / V row is R(D) = round_up(D / 2 + D / 32, 16) bytes for kv4) and
+the largest |O_kv4 - v_scale O_panels16| with the 16-bit forward on the records' values.
+
     python3 tools/attention_bench.py --forward panels --bias [--cases C2,C5,C3] [--dtype f16|bf16] [--d 64|128]
     python3 tools/attention_bench.py --backward panels --bias ...
 
@@ -127,6 +136,7 @@ def main():
     ap.add_argument("--forward", default="gather", choices=["gather", "panels"])
     ap.add_argument("--backward", default="gather", choices=["gather", "panels"])
     ap.add_argument("--kv8", action="store_true")
+    ap.add_argument("--kv4", action="store_true")
     ap.add_argument("--bias", action="store_true")
     ap.add_argument("--layout", default="bmhd", choices=["bmhd", "bhmd"])
     ap.add_argument("--baseline-only", action="store_true")
@@ -137,6 +147,8 @@ def main():
         raise SystemExit("--forward panels takes --dtype f16 or bf16")
     if args.kv8 and (args.forward != "panels" or args.d not in (64, 128, 256)):
         raise SystemExit("--kv8 goes with --forward panels and --d 64, 128 or 256")
+    if args.kv4 and (args.forward != "panels" or args.kv8 or args.bias or args.d not in (128, 256)):
+        raise SystemExit("--kv4 goes with --forward panels and --d 128 or 256")
     if args.backward == "panels" and (args.dtype == "f32" or args.d not in (32, 64, 128)):
         raise SystemExit("--backward panels takes --dtype f16 or bf16 and --d 32, 64 or 128")
     if args.bias and ("panels" not in (args.forward, args.backward) or args.kv8 or args.d not in (32, 64, 128)):
@@ -373,6 +385,9 @@ def panels_bench(args, torch, dev, graph_of, alternate):
         plan.prepare_attention_panels(D, D)
         data = lambda rows: (torch.from_numpy(make_data(rows * D)).to(dev) - 1.0).reshape(rows, D).to(tdt)  # noqa: E731
         Q, K, V = data(M), data(N), data(N)
+        if args.kv4:
+            kv4_case(args, torch, plan, case, Q, K, V, scale, dtype, graph_of, alternate)
+            continue
         if args.kv8:
             kv8_case(args, torch, plan, case, Q, K, V, scale, dtype, graph_of, alternate)
             continue
@@ -417,6 +432,42 @@ def kv8_case(args, torch, plan, case, Q, K, V, scale, dtype, graph_of, alternate
             "floor_us": {k: round(v, 3) for k, v in floor.items()},
             "floor_fraction": {k: round(floor[k] / graph_us[k], 3) for k in floor},
             "max_abs_diff": (out["kv8"][0] - vs * out["panels16"][0]).abs().max().item()}
+    print(json.dumps(line), flush=True)
+
+
+def kv4_case(args, torch, plan, case, Q, K, V, scale, dtype, graph_of, alternate):
+    """One case of --forward panels --kv4 (module docstring)."""
+    from bsmr import mx4_record_bytes
+    from bsmr.autograd import dequantize_mx4, quantize_kv, quantize_kv_mx4
+
+    D, M = args.d, plan.M
+    p = lambda t: t.data_ptr()  # noqa: E731
+    K4, V4, ks4, vs4 = quantize_kv_mx4(K, V)
+    K8, V8, ks8, vs8 = quantize_kv(K, V)
+    out = {k: (torch.zeros(M, D, device=Q.device), torch.zeros(M, device=Q.device)) for k in ("panels16", "kv8", "kv4")}
+    ours = {"panels16": lambda s, k=K, v=V, sc=scale: plan.attention_panels(p(Q), p(k), p(v), D, D, p(out["panels16"][0]),
+                                                                            p(out["panels16"][1]), sc, stream=s, dtype=dtype),
+            "kv8": lambda s: plan.attention_panels_kv8(p(Q), p(K8), p(V8), D, D, p(out["kv8"][0]), p(out["kv8"][1]), scale, ks8,
+                                                       vs8, stream=s, dtype=dtype),
+            "kv4": lambda s: plan.attention_panels_kv4(p(Q), p(K4), p(V4), D, D, p(out["kv4"][0]), p(out["kv4"][1]), scale, ks4,
+                                                       vs4, stream=s, dtype=dtype)}
+    graphs = {k: graph_of(f) for k, f in ours.items()}
+    graph_us = alternate({k: g.replay for k, g in graphs.items()})
+    st = plan.attention_panels_stats()
+    floor = {k: (2 * D * M + 4 * D * M + 4 * M + 192 * st["steps"] + 2 * row * 32 * st["steps"]) / HBM_BYTES_PER_S * 1e6
+             for k, row in (("panels16", 2 * D), ("kv8", D), ("kv4", mx4_record_bytes(D)))}
+    Kw, Vw = dequantize_mx4(K4, D, Q.dtype), dequantize_mx4(V4, D, Q.dtype)  # exact: what the kv4 kernel widens to
+    s0 = torch.cuda.current_stream().cuda_stream
+    ours["kv4"](s0)
+    ours["panels16"](s0, Kw, Vw, scale * ks4)
+    torch.cuda.synchronize()
+    line = {"case": case, "mode": "panels_kv4", "M": M, "N": plan.N, "D": D, "dtype": args.dtype, "steps": args.steps,
+            "rounds": args.rounds, "attention_panels_stats": st, "k_scale": ks4, "v_scale": vs4, "graph_us": graph_us,
+            "kv4_over_kv8": round(graph_us["kv4"] / graph_us["kv8"], 3),
+            "kv4_over_panels16": round(graph_us["kv4"] / graph_us["panels16"], 3),
+            "floor_us": {k: round(v, 3) for k, v in floor.items()},
+            "floor_fraction": {k: round(floor[k] / graph_us[k], 3) for k in floor},
+            "max_abs_diff": (out["kv4"][0] - vs4 * out["panels16"][0]).abs().max().item()}
     print(json.dumps(line), flush=True)
 
 
